@@ -12,7 +12,14 @@ request descriptors and gathers the int16 PCM over RCCL (fishmi/dp.py), weak sca
 
 Weights are seeded synthetic bf16 at the S2-Pro shapes (there is no checkpoint on the box).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure,
+ms_per_step, first-sample latency, the step's breakdown).  --dump-outputs DIR also writes what the
+last timed step returned as DIR/<name>.npy.  --full adds every other leg after the timed steps:
+the decode GEMV / frame / codec rooflines (with their rocprofv3 passes), configs 3 and 5, the codec
+encode, the int8 / int4 legs, the measured stream peak and the CPU baseline (the --no-* and leg
+options below trim it).
 """
 from __future__ import annotations
 
@@ -42,7 +49,13 @@ def parse():
     ap.add_argument("--prompt-len", type=int, default=64)
     ap.add_argument("--first-chunk", type=int, default=1,
                     help="frames in the first vocoded chunk (later chunks grow 4x)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (pcm, codes; "
+                         "gathered_pcm at N>1) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: rooflines and their rocprofv3 passes, "
+                         "configs 3 and 5, codec encode, int8 / int4, stream peak, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline leg")
     ap.add_argument("--cpu-frames", type=int, default=0,
                     help="oracle decode frames timed (0: the whole utterance, --frames)")
     ap.add_argument("--cpu-codec-frames", type=int, default=0,
@@ -70,7 +83,10 @@ def parse():
                     help="skip the in-run rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes on the GEMV")
     ap.add_argument("--encode-seconds", type=float, default=30.0,
                     help="encode leg: seconds of reference audio through the codec encoder (0: skip)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def make_prompt(cfg, T, seed):
@@ -91,7 +107,8 @@ def utterance(llm, codec, prompt, sp, frames, first_chunk, voc=None):
     scheduler.StreamVocoder), the chunks after the first are vocoded on its host thread, on the
     codec's own HIP stream, while the next chunk decodes; the first chunk's PCM is waited for (the
     first-sample latency), the rest at the end.  timings: decode = host time in decode_frames,
-    codec = time inside the codec calls after the first chunk."""
+    codec = time inside the codec calls after the first chunk; "codes" holds the [frames, 1 + codebooks]
+    columns the decode returned (what --dump-outputs writes beside the PCM)."""
     t0 = time.perf_counter()
     col0 = llm.prefill(0, prompt, sp)
     t1 = time.perf_counter()
@@ -108,6 +125,7 @@ def utterance(llm, codec, prompt, sp, frames, first_chunk, voc=None):
     else:
         voc.submit(codec.stream_reset)
     pcm, jobs, done, n = [], [], 0, min(first_chunk, frames)
+    kept = []
     cols = col0[None]
     first = decode = 0.0
     while done < frames:
@@ -129,6 +147,7 @@ def utterance(llm, codec, prompt, sp, frames, first_chunk, voc=None):
         else:
             decode += tb - ta
         done += n
+        kept.append(cols)
         cols = cols[:0]
         n = min(4 * n, frames - done)
     for ev, box in jobs:
@@ -138,7 +157,7 @@ def utterance(llm, codec, prompt, sp, frames, first_chunk, voc=None):
         pcm.append(box[0])
     t4 = time.perf_counter()
     return np.concatenate(pcm), dict(first=first, prefill=t1 - t0, head=first - (t1 - t0), decode=decode,
-                                     codec=float(sum(durs[1:])), total=t4 - t0)
+                                     codec=float(sum(durs[1:])), total=t4 - t0, codes=kept)
 
 
 def throughput_leg(llm, codec, cfg, batch, frames, waves, sync, dist, world, vocode_chunk=128):
@@ -681,6 +700,8 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
+    last = {}
+
     def one_step(step):
         # rank 0 owns the request list; each rank gets one utterance (weak scaling)
         if dist is not None:
@@ -692,8 +713,8 @@ def main():
         sp = DualARModel.sampling(temperature=0.8, top_p=0.8, top_k=30, seed=7919 * step + rank,
                                   mask_im_end=True)
         pcm, tm = utterance(llm, codec, prompt, sp, args.frames, args.first_chunk, voc2)
-        if dist is not None:
-            dp.gather_pcm(dp.pcm_to_int16(pcm))
+        gathered = dp.gather_pcm(dp.pcm_to_int16(pcm)) if dist is not None else None
+        last.update(pcm=pcm, codes=tm["codes"], gathered_pcm=gathered)  # what the caller of this step received
         return tm
 
     from fishmi import scheduler as S
@@ -717,6 +738,68 @@ def main():
         fl = [torch.zeros_like(f) for _ in range(world)]
         dist.all_gather(fl, f)
         firsts = torch.cat(fl).cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last)
+
+    extra = full_legs(args, cfg, ccfg, llm, codec, tms, sync, dist, world, rank, local) if args.full else None
+
+    if rank == 0:
+        audio_s = world * args.steps * args.frames / FRAME_RATE
+        out = {
+            "metric": METRIC,
+            "value": round(audio_s / elapsed, 4),
+            "unit": "audio-sec/wall-sec",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "bf16",
+            "data": "synthetic: seeded random bf16 weights at S2-Pro 4B shapes, random prompt ids, "
+                    "<|im_end|> masked (fixed length)",
+            "config": {"workload": f"BASELINE config 2 per GPU: one utterance = {args.prompt_len}-token "
+                                   f"prompt + {args.frames} Dual-AR frames (top_k 30, top_p 0.8, temp 0.8) "
+                                   f"+ codec decode [1,10,{args.frames}] -> {args.frames * 2048} samples",
+                       "global_batch": world, "frames": args.frames, "prompt_len": args.prompt_len,
+                       "first_chunk_frames": args.first_chunk, "vocoder_chunks": "first_chunk_frames, then growing 4x",
+                       "vocoder": "serial" if not args.overlap_vocode else
+                                  "host thread, codec HIP stream overlapped with the next chunk's decode",
+                       "parallelism": f"dp{world}"},
+            "p50_first_sample_ms": round(float(np.median(firsts)) * 1e3, 2),
+            "p90_first_sample_ms": round(float(np.percentile(firsts, 90)) * 1e3, 2),
+            "per_stream_rtf": round(args.frames / FRAME_RATE / np.mean([t["total"] for t in tms]), 4),
+            "breakdown_ms": {k: round(float(np.mean([t[k] for t in tms])) * 1e3, 2)
+                             for k in ("prefill", "head", "decode", "codec", "total")},
+            "full": bool(args.full),
+        }
+        if extra is not None:
+            out.update(extra)
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: what the last timed step handed its caller, one float32 .npy per array.
+    pcm: the utterance's waveform [samples]; codes: the decoded columns [frames, 1 + codebooks]
+    (token id, then the codebook indices; all below 2^24, so exact in float32); gathered_pcm (N>1
+    only): the int16 PCM of every rank as rank 0 received it, [ranks, samples]."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"pcm": np.asarray(last["pcm"]), "codes": np.concatenate(last["codes"], axis=0)}
+    if last.get("gathered_pcm") is not None:
+        arrays["gathered_pcm"] = np.stack(last["gathered_pcm"])
+    assert sum(a.size for a in arrays.values()) * 4 <= 64 << 20, "dump larger than 64 MB"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def full_legs(args, cfg, ccfg, llm, codec, tms, sync, dist, world, rank, local):
+    """--full: everything beside the headline, after the timed steps.  Every rank calls it (the
+    throughput leg is collective); rank 0 gets the extra keys of the result line, the others None."""
+    from fishmi.llm import DualARModel
 
     # ---- roofline of the dominant kernel: the decode GEMV ("linear" class).  One decode frame's
     # GEMV launches (exact args, weights and shapes of the timed frames) are recorded and
@@ -786,39 +869,13 @@ def main():
 
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        del llm, codec
+        llm.close()  # free the device models before the host-side run
+        codec.close()
         cpu = cpu_baseline(cfg, ccfg, make_prompt(cfg, args.prompt_len, 0), args.frames,
                            args.cpu_frames, args.cpu_codec_frames, args.seed)
 
     if rank == 0:
-        audio_s = world * args.steps * args.frames / FRAME_RATE
-        out = {
-            "metric": METRIC,
-            "value": round(audio_s / elapsed, 4),
-            "unit": "audio-sec/wall-sec",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16",
-            "data": "synthetic: seeded random bf16 weights at S2-Pro 4B shapes, random prompt ids, "
-                    "<|im_end|> masked (fixed length)",
-            "config": {"workload": f"BASELINE config 2 per GPU: one utterance = {args.prompt_len}-token "
-                                   f"prompt + {args.frames} Dual-AR frames (top_k 30, top_p 0.8, temp 0.8) "
-                                   f"+ codec decode [1,10,{args.frames}] -> {args.frames * 2048} samples",
-                       "global_batch": world, "frames": args.frames, "prompt_len": args.prompt_len,
-                       "first_chunk_frames": args.first_chunk, "vocoder_chunks": "first_chunk_frames, then growing 4x",
-                       "vocoder": "serial" if not args.overlap_vocode else
-                                  "host thread, codec HIP stream overlapped with the next chunk's decode",
-                       "parallelism": f"dp{world}"},
-            "p50_first_sample_ms": round(float(np.median(firsts)) * 1e3, 2),
-            "p90_first_sample_ms": round(float(np.percentile(firsts, 90)) * 1e3, 2),
-            "per_stream_rtf": round(args.frames / FRAME_RATE / np.mean([t["total"] for t in tms]), 4),
-            "breakdown_ms": {k: round(float(np.mean([t[k] for t in tms])) * 1e3, 2)
-                             for k in ("prefill", "head", "decode", "codec", "total")},
+        return {
             "roofline": {"kernel": "decode linear layers: gemv_kernel (16-row MFMA tiles: w1||w3, heads, first-layer "
                                    "wqkv) + rowgemv_kernel (row blocks: wo / w2 with the residual epilogue, wqkv "
                                    "with the RMSNorm prologue)",
@@ -854,10 +911,7 @@ def main():
             "cpu_baseline": cpu,
             "box": box,
         }
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    return None
 
 
 if __name__ == "__main__":
