@@ -323,9 +323,23 @@ struct FmTuning {
     int row_copies = 1;      // 1: fm_llm_finalize keeps a row-major copy of every linear the row-block GEMV can take, so any
                              // rowgemv bits work later (bf16 S2-Pro: ~3.7 GB beside the packed tiles); 0: only the copies the
                              // rowgemv / rowgemv_q4 bits in force at finalize select (w1 || w3 bf16 / int8: ~3.6 GB saved)
+    int prefix_vec = 1;      // voice prefix copy (fm_prefix.hip): 1 16-byte accesses where the runs allow, 0 the scalar path
     unsigned long long* dbg = nullptr;  // device buffer of per-block phase timestamps (debug_ts)
 };
 FmTuning& fm_tuning();
+// Voice prefix cache (fm_prefix.hip): rows [0, npos) of every (layer, K | V, kv head) of the listed
+// slots' slow caches <-> one compact store [layer][K|V][kv head][npos][hd]; strides in bytes.
+struct KvPrefixArgs {
+    char *kc, *vc;       // the slow K / V caches [slot][layer][kv head][S][hd]
+    char* store;         // the prefix entry
+    const int* slots;    // device: the slots of the call (blockIdx.z indexes it)
+    size_t slot_stride_b, layer_stride_b, head_stride_b;
+    size_t run_bytes;    // npos * hd * element size
+    int64_t run_units;   // (launcher) run_bytes in access units
+    int nkv;
+    int to_store;        // 1: slot -> store (save), 0: store -> slots (load)
+};
+void launch_kv_prefix_copy(hipStream_t s, const KvPrefixArgs& a, int n_layer, int nslots);
 // PRO_FATT staging: raw q|k|v row, cached K/V rows [nkv][2][S-1][hd], qk-norm weights, RoPE row
 inline size_t fatt_lds_bytes(int ldqkv, int nkv, int S, int hd, size_t esz) {
     return ((size_t)ldqkv + (size_t)nkv * 2 * (S - 1) * hd + 2 * (size_t)hd) * esz + (size_t)hd * 4 + 64;

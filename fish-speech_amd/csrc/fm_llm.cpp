@@ -187,6 +187,16 @@ struct fm_llm {
     uint32_t* fxt = nullptr;                // fused fast attention + wo: tagged attention words [nh * hd]
     void* fout_rm = nullptr;                // the codebook head row-major (int8 / int4: codes), row-block GEMV
     int32_t* fiota = nullptr;               // [16]: fiota[c] = c - 1 (the fast KV prefetch's last cached row)
+    // voice prefix cache (fm_llm_prefix_*): id -> a compact snapshot [layer][K|V][kv head][npos][hd] of
+    // the slow-stack rows [0, npos) some slot held, one device buffer each (freed at drop / close)
+    struct Prefix {
+        void* buf = nullptr;
+        int npos = 0;
+        size_t bytes = 0;
+    };
+    std::map<int, Prefix> prefixes;
+    int next_prefix_id = 1;
+    int* pfx_slots = nullptr;  // device [max_slots]: the slot list of one prefix copy launch
     const QInfo* qinfo(const void* W) const {
         auto it = qmap.find(W);
         return it == qmap.end() ? nullptr : &it->second;
@@ -200,6 +210,7 @@ struct fm_llm {
             if (kv.second.q) (void)hipFree(kv.second.q);
         }
         for (void* p : allocs) (void)hipFree(p);
+        for (auto& kv : prefixes) (void)hipFree(kv.second.buf);
         if (h_cols) (void)hipHostFree(h_cols);
         if (h_hist) (void)hipHostFree(h_hist);
         if (h_chain_err) (void)hipHostFree(h_chain_err);
@@ -1436,12 +1447,12 @@ template <typename T> struct Run {
         return (const char*)m->x + (size_t)last * m->c.dim * E;
     }
 
-    // Several prompts (one slot each, positions from 0) through the slow stack together: their rows
+    // Several prompts (one slot each, positions from pos0[i], or from 0) through the slow stack together: their rows
     // packed into PREFILL_CHUNK-row chunks, so every linear is one GEMM over all of them (a prompt
     // may span chunks: its earlier rows are in the KV cache by then); the attention runs per prompt
     // segment (segs); the last row of prompt i is copied to plast row i.
     std::vector<std::array<int, 2>> segs;  // (first row, rows) of each prompt inside the current chunk
-    void prefill_multi(int n, const int32_t* slots, const int32_t* const* toks, const int* Ts) {
+    void prefill_multi(int n, const int32_t* slots, const int32_t* const* toks, const int* Ts, const int* pos0) {
         const int C1 = m->C1, dim = m->c.dim;
         std::vector<int32_t> rows((size_t)PREFILL_CHUNK * C1);
         std::vector<int> rs(PREFILL_CHUNK), rp(PREFILL_CHUNK);
@@ -1456,7 +1467,7 @@ template <typename T> struct Run {
                 for (int r = 0; r < take; ++r) {
                     for (int q = 0; q < C1; ++q) rows[(size_t)(R + r) * C1 + q] = toks[i][(size_t)q * Ts[i] + t + r];
                     rs[R + r] = slots[i];
-                    rp[R + r] = t + r;
+                    rp[R + r] = (pos0 ? pos0[i] : 0) + t + r;
                 }
                 R += take;
                 t += take;
@@ -1958,6 +1969,7 @@ static void finalize(fm_llm* m) {
     m->frame_pos = (int*)m->dalloc(n * 4);
     m->prow_slot = (int*)m->dalloc(PREFILL_CHUNK * 4);
     m->prow_pos = (int*)m->dalloc(PREFILL_CHUNK * 4);
+    m->pfx_slots = (int*)m->dalloc((size_t)n * 4);
     m->tok_in = (int32_t*)m->dalloc((size_t)n * m->C1 * 4);
     m->cols = (int32_t*)m->dalloc((size_t)n * m->C1 * 4);
     m->ptok = (int32_t*)m->dalloc((size_t)PREFILL_CHUNK * m->C1 * 4);
@@ -2253,18 +2265,21 @@ static void do_prefill(fm_llm* m, int slot, const int32_t* tokens, int T, const 
     if (first_col) memcpy(first_col, m->h_cols, (size_t)m->C1 * 4);
 }
 
-// Several requests prefilled together (each from position 0 of its own slot): one pass of the slow
-// stack over all their prompt rows, then one batched first frame (head + fast model + samplers) for
-// their last rows -- the same columns as n separate do_prefill calls.
+// Several requests prefilled together (each from position 0 of its own slot, or -- pos0 given --
+// request i after its slot's cached positions [0, pos0[i])): one pass of the slow stack over all
+// their prompt rows, then one batched first frame (head + fast model + samplers) for their last
+// rows -- the same columns as n separate do_prefill calls.
 static void do_prefill_batch(fm_llm* m, int n, const int32_t* slots, const int32_t* tokens, const int32_t* T,
-                             const fm_sampling* sps, int32_t* first_cols) {
+                             const fm_sampling* sps, int32_t* first_cols, const int32_t* pos0 = nullptr) {
     FMCHECK(n >= 1 && n <= m->max_slots, "bad request count");
     std::vector<const int32_t*> tk(n);
     size_t off = 0;
     for (int i = 0; i < n; ++i) {
         FMCHECK(slots[i] >= 0 && slots[i] < m->max_slots, "bad slot");
         for (int j = 0; j < i; ++j) FMCHECK(slots[j] != slots[i], "duplicate slot");
-        FMCHECK(T[i] >= 1 && T[i] < m->c.max_seq_len, "prompt must end before max_seq_len");
+        const int p0 = pos0 ? pos0[i] : 0;
+        FMCHECK(T[i] >= 1 && p0 >= 0 && (int64_t)p0 + T[i] < m->c.max_seq_len, "prompt must end before max_seq_len");
+        FMCHECK(p0 <= m->host_pos[slots[i]], "prefix reuse past the slot's cached positions");
         tk[i] = tokens + off;
         check_tokens(m, tk[i], T[i]);
         off += (size_t)m->C1 * T[i];
@@ -2273,7 +2288,7 @@ static void do_prefill_batch(fm_llm* m, int n, const int32_t* slots, const int32
     m->uploaded_slots.clear();
     HIPCHK(hipMemcpyAsync(m->frame_slot, slots, (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
     with_prec(m, [&](auto& r) {
-        r.prefill_multi(n, slots, tk.data(), T);
+        r.prefill_multi(n, slots, tk.data(), T, pos0);
         if (n <= GEMV_MAX_ROWS) {
             const void* hid = r.head_small(m->plast, false, n, 1);
             r.frame_tail_small(n, false, true, hid);
@@ -2285,7 +2300,7 @@ static void do_prefill_batch(fm_llm* m, int n, const int32_t* slots, const int32
         }
     });
     std::vector<int> pos(n);
-    for (int i = 0; i < n; ++i) pos[i] = T[i] - 1;  // finish() advances it
+    for (int i = 0; i < n; ++i) pos[i] = (pos0 ? pos0[i] : 0) + T[i] - 1;  // finish() advances it
     HIPCHK(hipMemcpyAsync(m->frame_pos, pos.data(), (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
     launch_finish(m->stream, n, m->frame_slot, m->frame_pos, m->cols, m->C1, m->tok_in, m->ras, m->C1 * 10,
                   m->C1, 0, m->sp);
@@ -2293,7 +2308,7 @@ static void do_prefill_batch(fm_llm* m, int n, const int32_t* slots, const int32
     HIPCHK(hipStreamSynchronize(m->stream));
     m->prof.collect();
     for (int i = 0; i < n; ++i) {
-        m->host_pos[slots[i]] = T[i];
+        m->host_pos[slots[i]] = (pos0 ? pos0[i] : 0) + T[i];
         m->host_step[slots[i]] = 1;
     }
     m->uploaded_slots.clear();
@@ -2307,6 +2322,116 @@ int fm_llm_prefill_batch(fm_llm* m, int n, const int32_t* slots, const int32_t* 
         HIPCHK(hipSetDevice(m->device));
         finalize(m);
         do_prefill_batch(m, n, slots, tokens, T, sp, first_cols);
+    });
+}
+
+int fm_llm_prefill_batch_at(fm_llm* m, int n, const int32_t* slots, const int32_t* tokens, const int32_t* T,
+                            const int32_t* pos0, const fm_sampling* sp, int32_t* first_cols) {
+    return fm_guard([&] {
+        FMCHECK(m && slots && tokens && T && pos0, "null argument");
+        HIPCHK(hipSetDevice(m->device));
+        finalize(m);
+        do_prefill_batch(m, n, slots, tokens, T, sp, first_cols, pos0);
+    });
+}
+
+// one launch of the prefix copy kernel between entry `e` and the listed slots (checked by the caller)
+static void prefix_copy(fm_llm* m, const fm_llm::Prefix& e, const int32_t* slots, int n, bool to_store) {
+    const StackDims& d = m->sd;
+    HIPCHK(hipMemcpyAsync(m->pfx_slots, slots, (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
+    KvPrefixArgs a{};
+    a.kc = (char*)m->kc;
+    a.vc = (char*)m->vc;
+    a.store = (char*)e.buf;
+    a.slots = m->pfx_slots;
+    a.slot_stride_b = m->slot_stride * m->esz;
+    a.layer_stride_b = m->layer_stride * m->esz;
+    a.head_stride_b = (size_t)m->S * d.hd * m->esz;
+    a.run_bytes = (size_t)e.npos * d.hd * m->esz;
+    a.nkv = d.nkv;
+    a.to_store = to_store ? 1 : 0;
+    launch_kv_prefix_copy(m->stream, a, d.n_layer, n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(m->stream));  // the caller's slot list is free again; a failed copy fails here
+}
+
+static fm_llm::Prefix& prefix_of(fm_llm* m, int id) {
+    auto it = m->prefixes.find(id);
+    FMCHECK(it != m->prefixes.end(), "unknown or dropped prefix id " + std::to_string(id));
+    return it->second;
+}
+
+int fm_llm_prefix_save(fm_llm* m, int slot, int npos, int* prefix_id) {
+    return fm_guard([&] {
+        FMCHECK(m && prefix_id, "null argument");
+        FMCHECK(m->finalized, "prefix_save before any prefill");
+        HIPCHK(hipSetDevice(m->device));
+        FMCHECK(slot >= 0 && slot < m->max_slots, "bad slot");
+        FMCHECK(npos >= 1 && npos <= m->host_pos[slot],
+                "prefix_save: npos " + std::to_string(npos) + " outside [1, " + std::to_string(m->host_pos[slot]) +
+                    "], the slot's cached positions");
+        fm_llm::Prefix e;
+        e.npos = npos;
+        e.bytes = (size_t)m->sd.n_layer * 2 * m->sd.nkv * npos * m->sd.hd * m->esz;
+        const hipError_t err = hipMalloc(&e.buf, e.bytes);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();  // the failed allocation is reported here, not by the next launch
+            throw FmError{FM_ERR_OOM, "prefix_save: hipMalloc(" + std::to_string(e.bytes) + ") failed: " +
+                                          hipGetErrorString(err)};
+        }
+        try {
+            const int32_t one = slot;
+            prefix_copy(m, e, &one, 1, true);
+        } catch (...) {
+            (void)hipFree(e.buf);
+            throw;
+        }
+        const int id = m->next_prefix_id++;
+        m->prefixes[id] = e;
+        *prefix_id = id;
+    });
+}
+
+int fm_llm_prefix_load(fm_llm* m, int prefix_id, const int32_t* slots, int n) {
+    return fm_guard([&] {
+        FMCHECK(m && slots, "null argument");
+        FMCHECK(m->finalized, "prefix_load before any prefill");
+        HIPCHK(hipSetDevice(m->device));
+        const fm_llm::Prefix& e = prefix_of(m, prefix_id);
+        FMCHECK(n >= 1 && n <= m->max_slots, "bad slot count");
+        for (int i = 0; i < n; ++i) {
+            FMCHECK(slots[i] >= 0 && slots[i] < m->max_slots, "bad slot");
+            for (int j = 0; j < i; ++j) FMCHECK(slots[j] != slots[i], "duplicate slot");
+        }
+        FMCHECK(e.npos <= m->S, "prefix longer than the slot cache");
+        prefix_copy(m, e, slots, n, false);
+        // the slots now hold the prefix as if they had just run those positions; their sampling records
+        // and RAS windows stay as they are (the prefill that follows resets them)
+        for (int i = 0; i < n; ++i) {
+            m->host_pos[slots[i]] = e.npos;
+            m->host_step[slots[i]] = 0;
+        }
+        m->uploaded_slots.clear();  // the frame rows on the device still carry the old positions
+    });
+}
+
+int fm_llm_prefix_drop(fm_llm* m, int prefix_id) {
+    return fm_guard([&] {
+        FMCHECK(m, "null handle");
+        HIPCHK(hipSetDevice(m->device));
+        const fm_llm::Prefix e = prefix_of(m, prefix_id);
+        HIPCHK(hipStreamSynchronize(m->stream));
+        m->prefixes.erase(prefix_id);
+        HIPCHK(hipFree(e.buf));
+    });
+}
+
+int fm_llm_prefix_info(fm_llm* m, int prefix_id, int* npos, int64_t* bytes) {
+    return fm_guard([&] {
+        FMCHECK(m, "null handle");
+        const fm_llm::Prefix& e = prefix_of(m, prefix_id);
+        if (npos) *npos = e.npos;
+        if (bytes) *bytes = (int64_t)e.bytes;
     });
 }
 
@@ -2577,6 +2702,8 @@ int fm_tune(const char* key, int value) {
             t.attn_cap = value;
         } else if (k == "prefill_attn") {
             t.prefill_attn = value != 0;
+        } else if (k == "prefix_vec") {
+            t.prefix_vec = value != 0;
         } else if (k == "prompt_qkv_slab") {
             t.prompt_qkv_slab = value != 0;
         } else if (k == "prompt_unroll") {

@@ -52,8 +52,9 @@ class _Slot:
 
 
 class BatchedWorker:
-    def __init__(self, model, max_slots: Optional[int] = None, tick_frames: int = 8):
+    def __init__(self, model, max_slots: Optional[int] = None, tick_frames: int = 8, prefix_cache=None):
         self.m = model
+        self.cache = prefix_cache  # fishmi.prefix_cache.PrefixCache, or None: today's flow exactly
         self.max_slots = max_slots or model.max_slots
         if self.max_slots > model.max_slots:
             raise ValueError(f"max_slots {self.max_slots} > the model's {model.max_slots}")
@@ -137,7 +138,38 @@ class BatchedWorker:
         return self._advance(slot)
 
     # ---- device work ------------------------------------------------------------------------------
+    def _prefill_cached(self, slots: List[int]):
+        """_prefill with a voice prefix cache: every distinct hit entry is loaded into all of its slots
+        with one call, hits and misses are prefilled together at their own start positions, and the
+        misses' base blocks are stored right after (two requests for a new voice in one tick both miss:
+        the second insert finds the first's entry)."""
+        plans = {s: self.active[s].plan for s in slots}
+        groups: Dict[int, list] = {}
+        for s in slots:
+            p = plans[s]
+            if p.prefix is None:
+                continue
+            if not self.cache.holds(p.prefix):  # evicted since the plan was made: prefill the whole prompt
+                p.L, p.prefix = 0, None
+                continue
+            groups.setdefault(p.prefix.pid, []).append(s)
+        for pid, ss in groups.items():
+            self.m.load_prefix(pid, ss)
+        if len(slots) > 1:
+            firsts = self.m.prefill_batch(slots, [plans[s].enc[:, plans[s].L:] for s in slots],
+                                          [plans[s].sp for s in slots], pos0=[plans[s].L for s in slots])
+            for s, col in zip(slots, firsts):
+                self._take(self.active[s], col)
+        else:
+            s, p = slots[0], plans[slots[0]]
+            self._take(self.active[s], self.m.prefill(s, p.enc[:, p.L:], p.sp, pos0=p.L))
+        for s in slots:
+            if plans[s].insert_len:
+                self.cache.insert(s, plans[s].enc[:, :plans[s].insert_len])
+
     def _prefill(self, slots: List[int]):
+        if self.cache is not None:
+            return self._prefill_cached(slots)
         fresh = [s for s in slots if self.active[s].plan.L == 0]
         if len(fresh) > 1:
             firsts = self.m.prefill_batch(fresh, [self.active[s].plan.enc for s in fresh],
@@ -174,7 +206,9 @@ class BatchedWorker:
             item = self.pending.popleft()
             slot = self.free.pop()
             try:
-                self.active[slot] = _Slot(item, ConversationJob(self.m, **item.request))
+                job = ConversationJob(self.m, **item.request) if self.cache is None else \
+                    ConversationJob(self.m, prefix_cache=self.cache, **item.request)
+                self.active[slot] = _Slot(item, job)
                 if self._advance(slot):
                     starting.append(slot)
             except Exception as e:

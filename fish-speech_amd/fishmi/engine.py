@@ -76,6 +76,10 @@ class BatchPlan:
     sp: object           # the slot's sampling record (model.sampling(...))
     max_new: int         # most columns to emit, the prefill's included (inference.py:262-271)
     text: str
+    # voice prefix cache (fishmi.prefix_cache): a hit's entry, whose rows the slot must be loaded with
+    # before the prefill at pos0 = L = entry.P; a miss's base block length, to insert after the batch
+    prefix: object = None
+    insert_len: int = 0
 
 
 class ConversationJob:
@@ -89,7 +93,8 @@ class ConversationJob:
                  max_new_tokens: int = 0, top_p: float = 0.9, top_k: int = 30, repetition_penalty: float = 1.1,
                  temperature: float = 1.0, compile: bool = False, iterative_prompt: bool = True,
                  chunk_length: int = 512, prompt_text=None, prompt_tokens=None, seed: Optional[int] = None,
-                 reuse_prefix: bool = False, stream_frames: int = 0, mask_im_end: bool = False):
+                 reuse_prefix: bool = False, stream_frames: int = 0, mask_im_end: bool = False,
+                 prefix_cache=None):
         if not (0 < top_p <= 1):
             raise AssertionError("top_p must be in (0, 1]")
         if not (0 < temperature < 2):
@@ -108,6 +113,12 @@ class ConversationJob:
         else:
             ptoks = None
         self.base = P.base_conversation(prompt_text, ptoks)
+        # voice prefix cache: the system message with the reference voice, encoded alone.  Encoding
+        # concatenates per-part tokens, so it is a column prefix of every batch prompt (checked per batch).
+        self.prefix_cache = prefix_cache
+        self.base_block = None
+        if prefix_cache is not None and any(isinstance(p, P.VQPart) for m in self.base.messages for p in m.parts):
+            self.base_block = self.base.encode_for_inference(self.tok, num_codebooks=self.C)[0].astype(np.int32)
         turns = P.split_text_by_speaker(text)
         self.batches = P.group_turns_into_batches(turns, max_speakers=5, max_bytes=chunk_length) if turns else [text]
         log.info("Split into %d turns, grouped into %d batches", len(turns), len(self.batches))
@@ -149,10 +160,24 @@ class ConversationJob:
             same = np.all(self.cached[:, :n] == enc[:, :n], axis=0)
             L = int(n if same.all() else np.argmin(same))
         T = enc.shape[1]
+        prefix, insert_len = None, 0
+        if self.base_block is not None and self.cached is None:
+            n = self.base_len
+            if n <= T - 1 and np.array_equal(enc[:, :n], self.base_block):
+                prefix = self.prefix_cache.lookup(enc)
+                if prefix is not None:
+                    L = prefix.P
+                else:
+                    insert_len = n
         mx = self.max_new_tokens if (self.max_new_tokens and T + self.max_new_tokens <= max_len) else max_len - T
         self.plan = BatchPlan(enc, L, self.model.sampling(self.temperature, self.top_p, self.top_k, s,
-                                                          self.mask_im_end), mx, batch_text)
+                                                          self.mask_im_end), mx, batch_text, prefix, insert_len)
         return self.plan
+
+    @property
+    def base_len(self) -> int:
+        """Positions of the system message (0 without voice references or without a cache)."""
+        return 0 if self.base_block is None else self.base_block.shape[1]
 
     def finish_batch(self, y: np.ndarray, fed_cols: np.ndarray) -> np.ndarray:
         """y: (C+1, n) the emitted columns (generate()'s seq[:, T:]); fed_cols: the columns the slot
@@ -177,7 +202,7 @@ def generate_long(*, model, text: str, tokenizer: Optional[P.FishTokenizer] = No
                   chunk_length: int = 512, prompt_text: Optional[Union[str, List[str]]] = None,
                   prompt_tokens=None, seed: Optional[int] = None,
                   reuse_prefix: bool = False, stream_frames: int = 0, stream_growth: int = 1,
-                  stream_max: int = 0, mask_im_end: bool = False) -> Iterator[GenerateResponse]:
+                  stream_max: int = 0, mask_im_end: bool = False, prefix_cache=None) -> Iterator[GenerateResponse]:
     """inference.py:523-733 on the native model (slot 0).  `device`, `decode_one_token`, `compile`,
     `iterative_prompt` and `repetition_penalty` are accepted for signature compatibility; like
     the reference, repetition_penalty is not applied (RAS is, inside the sampler).
@@ -198,12 +223,16 @@ def generate_long(*, model, text: str, tokenizer: Optional[P.FishTokenizer] = No
     that many times the previous one (up to stream_max frames when > 0) -- a first chunk of one
     frame reaches the vocoder right after the prompt, and a chunk of k frames always takes less
     time to generate than the audio already streamed takes to play.  mask_im_end: fixed-length
-    generation for benchmarks (the semantic bias keeps <|im_end|> at -inf)."""
+    generation for benchmarks (the semantic bias keeps <|im_end|> at -inf).
+
+    prefix_cache (fishmi.prefix_cache.PrefixCache, opt-in): a request with voice references whose
+    system message is cached loads its KV rows into slot 0 and prefills only the rest of the prompt;
+    one whose message is not cached yet runs as without a cache and stores the rows afterwards."""
     job = ConversationJob(model, text=text, tokenizer=tokenizer, num_samples=num_samples,
                           max_new_tokens=max_new_tokens, top_p=top_p, top_k=top_k, temperature=temperature,
                           chunk_length=chunk_length, prompt_text=prompt_text, prompt_tokens=prompt_tokens,
                           seed=seed, reuse_prefix=reuse_prefix, stream_frames=stream_frames,
-                          mask_im_end=mask_im_end)
+                          mask_im_end=mask_im_end, prefix_cache=prefix_cache)
     while True:
         plan = job.next_batch()
         if plan is None:
@@ -212,6 +241,8 @@ def generate_long(*, model, text: str, tokenizer: Optional[P.FishTokenizer] = No
             yield GenerateResponse(action="next")
             continue
         enc, L = plan.enc, plan.L
+        if plan.prefix is not None:
+            model.load_prefix(plan.prefix.pid, [0])
         if stream_frames > 0:
             y, fed_cols = yield from _stream_batch(model, enc, L, max_new_tokens, stream_frames, plan.text, plan.sp,
                                                    stream_growth, stream_max)
@@ -224,6 +255,8 @@ def generate_long(*, model, text: str, tokenizer: Optional[P.FishTokenizer] = No
                                    seed=plan.sp.seed, mask_im_end=mask_im_end)
             fed = model.slot_pos() - enc.shape[1] if reuse_prefix else 0  # columns fed back while decoding
             fed_cols = y[:, :fed]
+        if plan.insert_len:  # decode frames never rewrite prompt rows: the base block's rows are still the prefill's
+            prefix_cache.insert(0, enc[:, :plan.insert_len])
         codes = job.finish_batch(y, fed_cols)
         if stream_frames <= 0:
             yield GenerateResponse(action="sample", codes=codes, text=plan.text)
@@ -294,13 +327,16 @@ def load_model(checkpoint_path: str, device=0, precision="bf16", max_slots: int 
 
 
 def launch_thread_safe_queue(checkpoint_path, device, precision, compile: bool = False,
-                             model=None, max_slots: int = 1, tick_frames: int = 8) -> "queue.Queue":
+                             model=None, max_slots: int = 1, tick_frames: int = 8,
+                             voice_cache_mb: int = 0) -> "queue.Queue":
     """inference.py:748-799: a daemon worker owning the model; returns its input queue once the
     model is loaded.  `model` (optional) hands in an already-built DualARModel (tests).
 
     max_slots == 1: the reference's worker, one request at a time (generate_long on slot 0).
     max_slots > 1: fishmi.batching.BatchedWorker -- up to max_slots requests decode together on
-    their own KV slots (batched hipGraph frames), same queue contract (BASELINE config 3)."""
+    their own KV slots (batched hipGraph frames), same queue contract (BASELINE config 3).
+    voice_cache_mb > 0: either worker keeps a fishmi.prefix_cache.PrefixCache of that many MiB of device
+    memory, built on the worker thread (0: off, the reference's flow)."""
     ready = threading.Event()
     failure: List[BaseException] = []
     holder: dict = {}
@@ -312,10 +348,15 @@ def launch_thread_safe_queue(checkpoint_path, device, precision, compile: bool =
             failure.append(e)
             ready.set()
             return
+        cache = None
+        if voice_cache_mb > 0:
+            from .prefix_cache import PrefixCache
+
+            cache = PrefixCache(m, int(voice_cache_mb) << 20)
         if max_slots > 1:
             from .batching import BatchedWorker
 
-            w = BatchedWorker(m, max_slots, tick_frames)
+            w = BatchedWorker(m, max_slots, tick_frames, prefix_cache=cache)
             holder["q"] = w.input
             ready.set()
             w.run()
@@ -328,7 +369,7 @@ def launch_thread_safe_queue(checkpoint_path, device, precision, compile: bool =
             if item is None:
                 break
             try:
-                for chunk in generate_long(model=m, **item.request):
+                for chunk in generate_long(model=m, prefix_cache=cache, **item.request):
                     item.response_queue.put(WrappedGenerateResponse(status="success", response=chunk))
             except Exception as e:
                 log.error(traceback.format_exc())

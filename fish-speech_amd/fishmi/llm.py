@@ -182,9 +182,11 @@ class DualARModel:
                                                      ctypes.byref(sampling), native.i32p(col)))
         return col
 
-    def prefill_batch(self, slots, prompts, samplings) -> np.ndarray:
+    def prefill_batch(self, slots, prompts, samplings, pos0=None) -> np.ndarray:
         """Prefill several requests together (fm_llm_prefill_batch): slots distinct, prompts (C+1, T_i),
-        one sampling record each; returns the first columns (n, C+1), as n prefill() calls would."""
+        one sampling record each; returns the first columns (n, C+1), as n prefill() calls would.
+        pos0 (one start position per request, fm_llm_prefill_batch_at): prompt i is the suffix that runs
+        after its slot's cached positions [0, pos0[i])."""
         n = len(slots)
         assert n == len(prompts) == len(samplings) and n >= 1
         s = np.ascontiguousarray(slots, dtype=np.int32)
@@ -194,9 +196,42 @@ class DualARModel:
         tok = np.ascontiguousarray(np.concatenate([p.ravel() for p in ps]))
         sp = (native.SamplingC * n)(*samplings)
         out = np.zeros((n, self.C1), np.int32)
+        if pos0 is not None:
+            p0 = np.ascontiguousarray(pos0, dtype=np.int32)
+            assert p0.shape == (n,)
+            native.check(native.lib().fm_llm_prefill_batch_at(self.h, n, native.i32p(s), native.i32p(tok),
+                                                              native.i32p(T), native.i32p(p0), sp, native.i32p(out)))
+            return out
         native.check(native.lib().fm_llm_prefill_batch(self.h, n, native.i32p(s), native.i32p(tok), native.i32p(T),
                                                        sp, native.i32p(out)))
         return out
+
+    # ---- voice prefix cache (fishmi.prefix_cache.PrefixCache drives these) ----------------
+    def save_prefix(self, slot: int, npos: int) -> int:
+        """Snapshot the slow-stack KV rows [0, npos) of `slot` (fm_llm_prefix_save); returns the id."""
+        pid = ctypes.c_int(0)
+        native.check(native.lib().fm_llm_prefix_save(self.h, int(slot), int(npos), ctypes.byref(pid)))
+        return pid.value
+
+    def load_prefix(self, pid: int, slots) -> None:
+        """Write prefix `pid` into rows [0, npos) of the (distinct) slots, one launch; each slot's
+        cached position becomes npos (fm_llm_prefix_load)."""
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        native.check(native.lib().fm_llm_prefix_load(self.h, int(pid), native.i32p(s), s.size))
+
+    def drop_prefix(self, pid: int) -> None:
+        native.check(native.lib().fm_llm_prefix_drop(self.h, int(pid)))
+
+    def prefix_bytes(self, npos: int) -> int:
+        """Device bytes a prefix of `npos` positions takes (K and V of every slow layer and kv head)."""
+        c = self.cfg
+        return c.n_layer * 2 * c.n_local_heads * c.head_dim * (2 if self.precision == "bf16" else 4) * int(npos)
+
+    def prefix_info(self, pid: int):
+        """(positions, device bytes) of prefix `pid`."""
+        n, b = ctypes.c_int(0), ctypes.c_int64(0)
+        native.check(native.lib().fm_llm_prefix_info(self.h, int(pid), ctypes.byref(n), ctypes.byref(b)))
+        return n.value, b.value
 
     def decode(self, slots) -> np.ndarray:
         s = np.ascontiguousarray(slots, dtype=np.int32)

@@ -30,11 +30,15 @@ ABI_SYMBOLS = [
     "fm_codec_profile_read", "fm_codec_debug_read", "fm_codec_enable_encoder", "fm_codec_encode",
     "fm_codec_close", "fm_llm_force", "fm_llm_read_logits", "fm_op_rmsnorm", "fm_op_qk_rope", "fm_op_decode_attn", "fm_op_prompt_attn",
     "fm_op_embed", "fm_op_quant4", "fm_rope_table",
+    "fm_llm_prefix_save", "fm_llm_prefix_load", "fm_llm_prefix_drop", "fm_llm_prefix_info", "fm_llm_prefill_batch_at",
 ]
 
 
+FM_ERR_OOM = -4
+
+
 class FishMIError(RuntimeError):
-    pass
+    code = None  # the FM_ERR_* a failed library call returned (check())
 
 
 def tree_source_hash() -> str:
@@ -118,6 +122,11 @@ def lib():
                                      ctypes.POINTER(ctypes.c_int)]
     L.fm_llm_prefill_at.argtypes = [vp, i32, pi32, i32, i32, ctypes.POINTER(SamplingC), pi32]
     L.fm_llm_slot_pos.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int)]
+    L.fm_llm_prefix_save.argtypes = [vp, i32, i32, ctypes.POINTER(ctypes.c_int)]
+    L.fm_llm_prefix_load.argtypes = [vp, i32, pi32, i32]
+    L.fm_llm_prefix_drop.argtypes = [vp, i32]
+    L.fm_llm_prefix_info.argtypes = [vp, i32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64)]
+    L.fm_llm_prefill_batch_at.argtypes = [vp, i32, pi32, pi32, pi32, pi32, ctypes.POINTER(SamplingC), pi32]
     L.fm_llm_teacher_step.argtypes = [vp, i32, pi32, i32, i32, pi32, pf32, pf32, pf32]
     L.fm_llm_frame_bytes.argtypes = [vp, i32, i32]
     L.fm_llm_frame_bytes.restype = i64
@@ -167,7 +176,9 @@ def lib():
 
 def check(rc: int):
     if rc != 0:
-        raise FishMIError(f"libfishmi error {rc}: {lib().fm_last_error().decode()}")
+        e = FishMIError(f"libfishmi error {rc}: {lib().fm_last_error().decode()}")
+        e.code = rc
+        raise e
     return rc
 
 

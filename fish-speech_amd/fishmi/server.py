@@ -286,15 +286,18 @@ def create_app(engine: "TTS.TTSInferenceEngine", max_text_length: int = 0, api_k
 
 def build_engine(llama_checkpoint_path: str, decoder_checkpoint_path: str, device=0, precision="bf16",
                  compile: bool = False, max_frames: int = 2048, slots: int = 1, reuse_prefix: bool = False,
-                 llama_queue=None):
+                 llama_queue=None, voice_cache_mb: int = 0):
     """ModelManager (tools/server/model_manager.py): the LLM worker + the codec with its encoder.
     slots > 1: concurrent requests decode together on their own KV slots (fishmi.batching).
+    voice_cache_mb > 0: the worker keeps the prompt KV of reference voices on the device, up to that many
+    MiB (fishmi.prefix_cache); not wired through an already-launched llama_queue.
     llama_queue: an already-launched worker queue (the multi-GPU worker's, rank 0)."""
     from .codec import FishMICodec
     from .engine import launch_thread_safe_queue
 
     q = llama_queue if llama_queue is not None else \
-        launch_thread_safe_queue(llama_checkpoint_path, device, precision, compile, max_slots=slots)
+        launch_thread_safe_queue(llama_checkpoint_path, device, precision, compile, max_slots=slots,
+                                 voice_cache_mb=voice_cache_mb)
     codec = FishMICodec.from_checkpoint(decoder_checkpoint_path, device, precision, max_frames, encoder=True)
     return TTS.TTSInferenceEngine(q, codec, precision, compile, reuse_prefix=reuse_prefix)
 
@@ -316,6 +319,9 @@ def main(argv=None):
                     help="concurrent requests decoded together on one GPU (KV slots); 1 = the reference's serial worker")
     ap.add_argument("--reuse-prefix", action="store_true",
                     help="keep a request's conversation KV across its text batches (opt-in; default re-prefills)")
+    ap.add_argument("--voice-cache-mb", type=int, default=0,
+                    help="device MiB for the voice prefix cache: a reference voice's prompt KV is kept and copied "
+                         "into later requests' slots instead of being prefilled again (0 = off)")
     a = ap.parse_args(argv)
     import uvicorn
 
@@ -332,10 +338,14 @@ def main(argv=None):
         log.warning("--half: fp16 is not built; the HIP path runs bf16 (the reference's default precision)")
     if a.compile:
         log.info("--compile: decode frames are always hipGraph-captured; the flag changes nothing")
+    if a.voice_cache_mb < 0:
+        ap.error("--voice-cache-mb must be >= 0")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        if a.voice_cache_mb:
+            ap.error("--voice-cache-mb: the voice prefix cache is not wired through the multi-GPU worker")
         return _main_distributed(a)
     engine = build_engine(a.llama_checkpoint_path, a.decoder_checkpoint_path, _device_index(a.device), "bf16",
-                          slots=a.slots, reuse_prefix=a.reuse_prefix)
+                          slots=a.slots, reuse_prefix=a.reuse_prefix, voice_cache_mb=a.voice_cache_mb)
     host, port = a.listen.rsplit(":", 1)
     uvicorn.run(create_app(engine, a.max_text_length, a.api_key), host=host, port=int(port), workers=1)
 

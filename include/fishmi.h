@@ -158,6 +158,26 @@ int fm_llm_prefill_at(fm_llm* h, int slot, const int32_t* suffix, int T, int pos
                       int32_t* first_col);
 /* positions of the slot whose KV is written (prompt + fed columns of its last generate) */
 int fm_llm_slot_pos(fm_llm* h, int slot, int* pos);
+/* Voice prefix cache (no reference counterpart: the reference prefills the whole conversation,
+   system message with the reference voice included, for every request, inference.py:620-724).
+   prefix_save snapshots the slow-stack K/V rows [0, npos) of `slot` into a device buffer owned by
+   the handle, laid out [layer][K|V][kv head][npos][head_dim] in the handle's storage type;
+   1 <= npos <= the slot's cached positions.  The slot is not modified.  FM_ERR_OOM when the buffer
+   cannot be allocated: no id is issued and earlier entries stay intact. */
+int fm_llm_prefix_save(fm_llm* h, int slot, int npos, int* prefix_id);
+/* write a saved prefix into rows [0, npos) of n distinct slots (one launch for all of them) and
+   set each slot's cached position to npos, as if it had just run those positions; the slots'
+   rows >= npos and every other slot are untouched.  Follow with fm_llm_prefill_at /
+   fm_llm_prefill_batch_at at pos0 <= npos. */
+int fm_llm_prefix_load(fm_llm* h, int prefix_id, const int32_t* slots, int n);
+int fm_llm_prefix_drop(fm_llm* h, int prefix_id);
+int fm_llm_prefix_info(fm_llm* h, int prefix_id, int* npos, int64_t* bytes);
+/* fm_llm_prefill_batch with a start position per request: request i keeps its slot's cached
+   positions [0, pos0[i]) and prefills its T[i] suffix columns at pos0[i]..; pos0 all zero is
+   exactly fm_llm_prefill_batch. */
+int fm_llm_prefill_batch_at(fm_llm* h, int n, const int32_t* slots, const int32_t* tokens,
+                            const int32_t* T, const int32_t* pos0, const fm_sampling* sp,
+                            int32_t* first_cols);
 /* teacher forcing for parity: run S positions of x ((C+1) x S) from pos0 on slot (pos0 == 0
    resets the slot), return the last position's slow logits (V, with the semantic bias NOT
    applied), the fast hidden (fast_dim), and -- when next_col != NULL -- the fast logits
@@ -202,7 +222,7 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    "fd_nw_batched" 4|8|16, "attn_wo" 0|1,
    "batched_fused_attn" 0|1; batched linears "bstream" 0|1, "bstream_acc" 0|1, "bstream_chain" 0|1, "bstream_kparts" n, "bstream_nw" n, "bs_dummy" 0|1|2, "bs_qkv_slab" 0|1,
    "bs_xfirst" 0|1, "bs_vec_epi" 0|1,
-   "linear_u32" n, "linear_fill" n; prompt "prefill_attn", "prompt_gemm"; codec "conv2",
+   "linear_u32" n, "linear_fill" n; prompt "prefill_attn", "prompt_gemm"; voice prefix copy "prefix_vec" 0|1; codec "conv2",
    "conv_splitk"; "sampler_fast" 0|1, "rmsnorm_block" 0|1, "debug_ts" n; batch-1 row-block GEMV
    "rowgemv" / "rowgemv_q4" bits, "row_copies" 0|1 (0: finalize keeps only the row-major weight
    copies those bits select).  They apply to launches
