@@ -52,13 +52,17 @@ __device__ __forceinline__ void fast_attn_head(const FastFusedArgs<T>& a, int r,
     const int hd = a.hd, g = a.nh / a.nkv, kvh = h / g, cpos = a.cpos, half = hd >> 1;
     const float* tab = a.rope + (size_t)cpos * hd;
     const int slot = a.row_slot[r];
+    // FastFusedArgs::noq (codebook 0): one position, the output is 0 + v and the Q rows are not read
+    const bool noq = a.noq && cpos == 0;
     float q0[2], q1[2], k0[2], k1[2], v0[2], v1[2], qw0[2], qw1[2], kw0[2], kw1[2], c_[2], s_[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int p = lane + 64 * u;
         const bool ok = p < half;
         const int pp = ok ? p : 0;
-        raw_pair<T>(a.qkv, a.ldqkv, a.qslab, a.qslab_kp, gridDim.x, a.qbias, r, (size_t)h * hd + 2 * pp, q0[u], q1[u]);
+        q0[u] = q1[u] = 0.f;
+        if (!noq)
+            raw_pair<T>(a.qkv, a.ldqkv, a.qslab, a.qslab_kp, gridDim.x, a.qbias, r, (size_t)h * hd + 2 * pp, q0[u], q1[u]);
         raw_pair<T>(a.qkv, a.ldqkv, a.qslab, a.qslab_kp, gridDim.x, a.qbias, r, (size_t)(a.nh + kvh) * hd + 2 * pp,
                     k0[u], k1[u]);
         raw_pair<T>(a.qkv, a.ldqkv, a.qslab, a.qslab_kp, gridDim.x, a.qbias, r,
@@ -112,7 +116,7 @@ __device__ __forceinline__ void fast_attn_head(const FastFusedArgs<T>& a, int r,
             x1[u] = y1;
         }
     };
-    prep(q0, q1, qw0, qw1, a.qk_norm);
+    if (!noq) prep(q0, q1, qw0, qw1, a.qk_norm);
     prep(k0, k1, kw0, kw1, a.qk_norm);
     if (a.qdbg) {  // per-op test hook only (fm_op_qk_rope)
 #pragma unroll
@@ -136,6 +140,18 @@ __device__ __forceinline__ void fast_attn_head(const FastFusedArgs<T>& a, int r,
                 st(vc + (size_t)cpos * hd, 2 * p + 1, v1[u]);
             }
         }
+    }
+    T* out = a.out + (size_t)r * a.nh * hd + (size_t)h * hd;
+    if (noq) {  // softmax of the one (finite) score is 1: o = 0 + 1 * v, the 0 + turning a -0 into the full form's +0
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int p = lane + 64 * u;
+            if (p < half) {
+                st(out, 2 * p, 0.f + v0[u]);
+                st(out, 2 * p + 1, 0.f + v1[u]);
+            }
+        }
+        return;
     }
     // scores round(round(q.k) * scale), softmax, probabilities rounded (fast SDPA path)
     float sc[FAST_ATTN_MAXJ + 1];
@@ -173,7 +189,6 @@ __device__ __forceinline__ void fast_attn_head(const FastFusedArgs<T>& a, int r,
             o1[u] += p * (j < cpos ? V1[j < FAST_ATTN_MAXJ ? j : 0][u] : v1[u]);
         }
     }
-    T* out = a.out + (size_t)r * a.nh * hd + (size_t)h * hd;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const int p = lane + 64 * u;

@@ -193,6 +193,8 @@ template <typename T> struct FastFusedArgs {
     int qslab_kp = 1;
     const T* qbias = nullptr;
     const int* row_pos = nullptr;  // fattn_wo_kernel: the frame's position (its hand-off tag)
+    int noq = 0;  // fast_attn2_kernel, cpos == 0 (fm_tune rowgemv bit 6): one position, so the output is 0 + v: the
+                  // Q rows of qkv are not read (the projection did not compute them); k / v are cached as ever
 };
 template <typename T> struct GemvArgs {
     const T* W;
@@ -318,13 +320,16 @@ struct FmTuning {
     int fattn_wo = 1;        // 1: batch-1 bf16 fast-model attention + wo as one launch (fm_rowgemv.hip fattn_wo_kernel)
     int row_qkv_rp = 8;      // developer: rows per block of the bf16 row-block wqkv (4, 8 or 16)
     int rowgemv_q4 = 31;     // rowgemv's bits for weight-only int4 models (w1 || w3 too: int4 frame 3.06 -> 3.01 ms; bf16 4.07 -> 4.10, int8 3.11 -> 3.20 with it)
-    int rowgemv = 27;        // batch-1 decode linears on the row-block GEMV (fm_rowgemv.hip): bit 0 wo / w2, bit 1 wqkv, bit 2 w1 || w3,
-                             // bit 3 the codebook head, bit 4 the first layers' wqkv (0: 16-row MFMA tiles; 3 -> 27: 4.066 -> 4.032 ms)
+    int rowgemv = 123;       // batch-1 decode linears on the row-block GEMV (fm_rowgemv.hip): bit 0 wo / w2, bit 1 wqkv, bit 2 w1 || w3,
+                             // bit 3 the codebook head, bit 4 the first layers' wqkv (0: 16-row MFMA tiles; 3 -> 27: 4.066 -> 4.032 ms);
+                             // bit 5: the first fast layer's QKV at codebooks >= 1 read from a table of its codebook_size possible
+                             // rows (no launch); bit 6: at codebook 0 the fast layers compute K / V only (one position: attention = v)
     int row_copies = 1;      // 1: fm_llm_finalize keeps a row-major copy of every linear the row-block GEMV can take, so any
                              // rowgemv bits work later (bf16 S2-Pro: ~3.7 GB beside the packed tiles); 0: only the copies the
                              // rowgemv / rowgemv_q4 bits in force at finalize select (w1 || w3 bf16 / int8: ~3.6 GB saved)
     int prefix_vec = 1;      // voice prefix copy (fm_prefix.hip): 1 16-byte accesses where the runs allow, 0 the scalar path
     unsigned long long* dbg = nullptr;  // device buffer of per-block phase timestamps (debug_ts)
+    unsigned epoch = 0;      // bumped by every fm_tune call but debug_ts: what was derived under older knobs (the QKV table) is rebuilt
 };
 FmTuning& fm_tuning();
 // Voice prefix cache (fm_prefix.hip): rows [0, npos) of every (layer, K | V, kv head) of the listed
@@ -405,6 +410,13 @@ struct FattnWoArgs {
     int cheap;                // 1: poll one word per 32-element group before the full read (fm_tune fw_cheap)
     int prio;                 // 1: attention waves at s_setprio 3 (fm_tune fw_prio)
     unsigned long long* dbg;  // developer records (launcher: fm_tune debug_ts)
+    // fm_tune rowgemv bit 5 (the first fast layer at codebook > 0, bf16): the attention blocks take the raw q|k|v
+    // row from qtab [qrows][at.ldqkv], row qidx[qcol] clamped into it, instead of at.qkv (no QKV launch ran)
+    const bf16_t* qtab;
+    const int32_t* qidx;
+    int qcol, qrows;
+    // fm_tune rowgemv bit 6 (at.cpos == 0, bf16): Q was not computed; the attention output is 0 + v
+    int kv0;
 };
 bool fattn_wo_ok(int nh, int nkv, int hd, int cpos, int N, int K, int qm);
 void launch_fattn_wo(hipStream_t s, const FattnWoArgs& a);

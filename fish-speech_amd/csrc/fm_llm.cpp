@@ -187,6 +187,12 @@ struct fm_llm {
     uint32_t* fxt = nullptr;                // fused fast attention + wo: tagged attention words [nh * hd]
     void* fout_rm = nullptr;                // the codebook head row-major (int8 / int4: codes), row-block GEMV
     int32_t* fiota = nullptr;               // [16]: fiota[c] = c - 1 (the fast KV prefetch's last cached row)
+    // fm_tune rowgemv bit 5: the first fast layer's raw q|k|v row of every code [cb][fast nqkv] (bf16, unquantised
+    // models; ensure_qkv0), valid while qkv0_epoch is the tuning epoch it was built under
+    void* qkv0 = nullptr;
+    int32_t* qkv0_iota = nullptr;           // [cb]: 0, 1, ...: the build's gather index
+    unsigned qkv0_epoch = 0;
+    bool qkv0_built = false;
     // voice prefix cache (fm_llm_prefix_*): id -> a compact snapshot [layer][K|V][kv head][npos][hd] of
     // the slow-stack rows [0, npos) some slot held, one device buffer each (freed at drop / close)
     struct Prefix {
@@ -883,6 +889,90 @@ template <typename T> struct Run {
         };
         return KsbPlan{fin_ksb(d.dim, d.nq()), fin_ksb(d.dim, d.inter)};
     }
+    // a layer's QKV projection (+ attention_norm) of one row on the row-block GEMV.  first: x is the layer's
+    // input row itself (a table row gathered by xidx[xcol] when xidx), else the residual row xb.  a: the tile
+    // form's arguments, whose KV prefetch fields carry over.  kv_rows (fm_tune rowgemv bit 6): rows [nq, nqkv)
+    // only -- the same prologue and the same per-row sums, the Q rows of Y left as they were
+    void qkv_row(const StackDims& d, const LayerW& L, const GemvArgs<T>& a, bool first, const void* x, int ldx,
+                 const int32_t* xidx, int xcol, void* Y, bool kv_rows) {
+        RowGemvArgs r{};
+        if (m->quant == FM_QUANT_INT4) {
+            r.Wq4 = (const uint32_t*)L.wqkv_rm;
+            r.wsz = (const uint32_t*)m->rowsz.at(L.wqkv);
+            r.gs = m->q4_gs;
+        } else {
+            r.W = (const bf16_t*)L.wqkv_rm;
+        }
+        if (first) {
+            r.X = (const bf16_t*)x;
+            r.ldx = ldx;
+            r.xidx = xidx;
+            r.xcol = xcol;
+            r.xrows = xidx ? m->cb : 0;
+        } else {
+            r.X = (const bf16_t*)x;
+        }
+        r.bias = (const bf16_t*)L.bqkv;
+        r.nw = (const bf16_t*)L.an;
+        r.eps = m->c.norm_eps;
+        r.Y = (bf16_t*)Y;
+        r.N = d.nqkv();
+        r.K = d.dim;
+        if (kv_rows) {
+            r.W += (size_t)d.nq() * d.dim;
+            if (r.bias) r.bias += d.nq();
+            r.Y += d.nq();
+            r.N -= d.nq();
+        }
+        r.pf_kc = (const bf16_t*)a.pf_kc;
+        r.pf_vc = (const bf16_t*)a.pf_vc;
+        r.pf_slot = a.pf_slot;
+        r.pf_pos = a.pf_pos;
+        r.pf_slot_stride = a.pf_slot_stride;
+        r.pf_layer_off = a.pf_layer_off;
+        r.pf_S = a.pf_S;
+        r.pf_nkv = a.pf_nkv;
+        r.pf_hd = a.pf_hd;
+        rowgemv(r, ROWGEMV_NORM_STORE);
+    }
+    bool qkv_first_row(int n) const { return row_qkv(n) && (row_bits() & 16); }
+    // the FIRST layer's QKV of one row: the row form (rowgemv bits 1 and 4), else the PRO_NORM tile form.
+    // block_small's launch, and -- one launch per code, xidx an iota array, Y the code's table row -- what
+    // ensure_qkv0 fills the bit-5 table with: the same kernel on the same input row gives the same bytes
+    void qkv_first(const StackDims& d, const LayerW& L, GemvArgs<T> a, int n, const void* x_in, int ldx_in,
+                   const int32_t* xidx, int xcol, void* Y, bool kv_rows) {
+        if (qkv_first_row(n)) {
+            qkv_row(d, L, a, true, x_in, ldx_in, xidx, xcol, Y, kv_rows);
+            return;
+        }
+        a.Y = (T*)Y;
+        a.X = (const T*)x_in;
+        a.ldx = ldx_in;
+        a.xidx = xidx;
+        a.xidx_ld = m->C1;
+        a.xidx_col = xcol;
+        a.xidx_rows = xidx ? m->cb : 0;
+        gemv(a, PRO_NORM, EPI_STORE, 1, "linear");
+    }
+    // the tile form's arguments of a fast layer's QKV at one row, no prefetch (the table build)
+    GemvArgs<T> qkv_args(const StackDims& d, const LayerW& L, int n) {
+        GemvArgs<T> a = ga();
+        a.W = (const T*)L.wqkv;
+        a.bias = (const T*)L.bqkv;
+        a.nw = (const T*)L.an;
+        a.R = n;
+        a.N = d.nqkv();
+        a.K = d.dim;
+        a.Y = (T*)m->qkv;
+        a.ldy = d.nqkv();
+        return a;
+    }
+    // whether block_small may read the first fast layer's QKV from the table (bit 5; bf16, unquantised)
+    bool qkv0_live() const {
+        return sizeof(T) == 2 && !m->quant && (row_bits() & 32) && m->qkv0 && m->qkv0_built &&
+               m->qkv0_epoch == fm_tuning().epoch;
+    }
+
     // one pre-norm block (TransformerBlock.forward, llama.py:838-843) on n rows.  Residual rows
     // are always finalised by the producing GEMV (EPI_SLABFIN: x / h in bf16 plus per-tile sums of
     // squares ssX / ssH), so every RMSNorm consumer is PRO_PRENORM.  x_in: the first layer's input
@@ -922,17 +1012,19 @@ template <typename T> struct Run {
                         fattn_wo_ok(d.nh, d.nkv, d.hd, cpos, d.dim, d.nq(), fq);
         const bool att_wo = is_fast && !kv_only && fm_tuning().attn_wo && !m->quant && n == 1 && cpos < 16 && d.hd % 16 == 0 &&
                             d.hd <= 128 && d.nh % d.nkv == 0 && (d.nq() / kp.wo) % d.hd == 0 && d.nqkv() % 8 == 0;
+        // fm_tune rowgemv bits 5 / 6 (bf16, unquantised, batch 1; inert elsewhere).  tab: the first fast
+        // layer at codebook > 0 inside the fused launch -- its raw q|k|v row comes from the table, no QKV
+        // launch.  kv0: codebook 0 on the row path -- one position, so the attention output is v: the
+        // projection computes rows [nq, nqkv) only and the attention reads no Q (the Q part of m->qkv is stale)
+        const bool row_here = row_qkv(n) && (!first || (row_bits() & 16));
+        const bool bits56 = sizeof(T) == 2 && !m->quant && is_fast && n == 1;
+        const bool tab = bits56 && first && xidx && fw && qkv0_live();
+        const bool kv0 = bits56 && cpos == 0 && (row_bits() & 64) && row_here && !att_wo && d.hd <= 256 &&
+                         (d.nqkv() - d.nq()) % fm_tuning().row_qkv_rp == 0;
+        fa.noq = kv0;
         // QKV (+ attention_norm)
-        {
-            GemvArgs<T> a = ga();
-            a.W = (const T*)L.wqkv;
-            a.bias = (const T*)L.bqkv;
-            a.nw = (const T*)L.an;
-            a.R = n;
-            a.N = d.nqkv();
-            a.K = d.dim;
-            a.Y = (T*)m->qkv;
-            a.ldy = d.nqkv();
+        if (!tab) {
+            GemvArgs<T> a = qkv_args(d, L, n);
             if (!is_fast && n == 1 && fm_tuning().kv_prefetch) {  // the attention's K / V rows into L2
                 a.pf_kc = (const T*)m->kc;
                 a.pf_vc = (const T*)m->vc;
@@ -955,49 +1047,16 @@ template <typename T> struct Run {
                 a.pf_nkv = d.nkv;
                 a.pf_hd = d.hd;
             }
-            const int epi = EPI_STORE;
-            if (row_qkv(n) && (!first || (row_bits() & 16))) {
-                RowGemvArgs r{};
-                row_w(r, L.wqkv_rm, L.wqkv);
-                if (first) {  // the layer's input row itself (a table row gathered by xidx[xcol] at codebook > 0)
-                    r.X = (const bf16_t*)x_in;
-                    r.ldx = ldx_in;
-                    r.xidx = xidx;
-                    r.xcol = xcol;
-                    r.xrows = xidx ? m->cb : 0;
-                } else {
-                    r.X = (const bf16_t*)xb;
-                }
-                r.bias = (const bf16_t*)L.bqkv;
-                r.nw = (const bf16_t*)L.an;
-                r.eps = m->c.norm_eps;
-                r.Y = (bf16_t*)m->qkv;
-                r.N = d.nqkv();
-                r.K = d.dim;
-                r.pf_kc = (const bf16_t*)a.pf_kc;
-                r.pf_vc = (const bf16_t*)a.pf_vc;
-                r.pf_slot = a.pf_slot;
-                r.pf_pos = a.pf_pos;
-                r.pf_slot_stride = a.pf_slot_stride;
-                r.pf_layer_off = a.pf_layer_off;
-                r.pf_S = a.pf_S;
-                r.pf_nkv = a.pf_nkv;
-                r.pf_hd = a.pf_hd;
-                rowgemv(r, ROWGEMV_NORM_STORE);
-            } else if (first) {
-                a.X = (const T*)x_in;
-                a.ldx = ldx_in;
-                a.xidx = xidx;
-                a.xidx_ld = C1;
-                a.xidx_col = xcol;
-                a.xidx_rows = xidx ? m->cb : 0;
-                gemv(a, PRO_NORM, epi, 1, "linear");
+            if (first) {  // the layer's input row itself (a table row gathered by xidx[xcol] at codebook > 0)
+                qkv_first(d, L, a, n, x_in, ldx_in, xidx, xcol, m->qkv, kv0);
+            } else if (row_here) {
+                qkv_row(d, L, a, false, xb, 0, nullptr, 0, m->qkv, kv0);
             } else {
                 a.X = (const T*)xb;
                 a.ldx = d.dim;
                 a.ss_in = m->ssX;
                 a.ss_gran = rf ? 1 : 0;
-                gemv(a, PRO_PRENORM, epi, 1, "linear");
+                gemv(a, PRO_PRENORM, EPI_STORE, 1, "linear");
             }
         }
         if (!is_fast) {
@@ -1057,6 +1116,13 @@ template <typename T> struct Run {
             A.delay = fm_tuning().fw_delay;
             A.cheap = fm_tuning().fw_cheap;
             A.prio = fm_tuning().fw_prio;
+            if (tab) {
+                A.qtab = (const bf16_t*)m->qkv0;
+                A.qidx = xidx;
+                A.qcol = xcol;
+                A.qrows = m->cb;
+            }
+            A.kv0 = kv0;
             chain_flush();
             const int64_t bytes = r.Wq4 ? (int64_t)r.N * r.K / 2 + (int64_t)r.N * (r.K / r.gs) * 4
                                   : (r.Wq ? (int64_t)r.N * r.K + (int64_t)r.N * 2 : (int64_t)r.N * r.K * 2);
@@ -2063,8 +2129,53 @@ static void chain_err_check(fm_llm* m) {
                   "attention + wo; counters reset)"};
 }
 
+// fm_tune rowgemv bit 5: (re)build the table of the first fast layer's raw q|k|v rows, one launch of
+// block_small's own first-layer QKV helper per code (Run::qkv_first: the kernel the frame would run, on
+// the row fast_embeddings[code]), so the table holds the bytes that launch would have written.  Built at
+// load time and again whenever an fm_tune call since could have changed the helper's kernel (the tuning
+// epoch); never inside a capture.  bf16 unquantised models only: bits 5 / 6 are inert for int8 / int4.
+static void ensure_qkv0(fm_llm* m) {
+    FmTuning& t = fm_tuning();
+    if (!m->finalized || m->prec != FM_PREC_BF16 || m->quant || !(t.rowgemv & 32) || !m->fxt || m->C < 2 ||
+        !t.fattn_wo || t.gemv_chain || m->fast.empty())
+        return;
+    if (m->qkv0_built && m->qkv0_epoch == t.epoch) return;
+    const StackDims& d = m->fdm;
+    if (!m->qkv0) {
+        m->qkv0 = m->dalloc((size_t)m->cb * d.nqkv() * sizeof(bf16_t), false);
+        std::vector<int32_t> io((size_t)m->cb);
+        for (size_t i = 0; i < io.size(); ++i) io[i] = (int32_t)i;
+        m->qkv0_iota = (int32_t*)m->dalloc(io.size() * sizeof(int32_t), false);
+        HIPCHK(hipMemcpy(m->qkv0_iota, io.data(), io.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    // the build's launches are neither profiled nor recorded (debug_ts, fm_llm_profile)
+    unsigned long long* dbg = t.dbg;
+    const bool prof_on = m->prof.on;
+    t.dbg = nullptr;
+    m->prof.on = false;
+    try {
+        Run<bf16_t> r(m);
+        const GemvArgs<bf16_t> a = r.qkv_args(d, m->fast[0], 1);
+        for (int code = 0; code < m->cb; ++code)
+            r.qkv_first(d, m->fast[0], a, 1, m->femb, m->c.fast_dim, m->qkv0_iota, code,
+                        (bf16_t*)m->qkv0 + (size_t)code * d.nqkv(), false);
+        r.chain_flush();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(m->stream));
+    } catch (...) {
+        t.dbg = dbg;
+        m->prof.on = prof_on;
+        throw;
+    }
+    t.dbg = dbg;
+    m->prof.on = prof_on;
+    m->qkv0_epoch = t.epoch;
+    m->qkv0_built = true;
+}
+
 // one decode frame for the uploaded rows (graph replay when enabled), async
 static void launch_frame(fm_llm* m, int n) {
+    ensure_qkv0(m);
     if (m->use_graph && !m->prof.on) {
         auto it = m->graphs.find(n);
         if (it == m->graphs.end()) {
@@ -2232,6 +2343,7 @@ int fm_llm_finalize(fm_llm* m) {
         FMCHECK(m, "null handle");
         HIPCHK(hipSetDevice(m->device));
         finalize(m);
+        ensure_qkv0(m);
     });
 }
 
@@ -2247,6 +2359,7 @@ static void do_prefill(fm_llm* m, int slot, const int32_t* tokens, int T, const 
     const int32_t one = slot;
     m->uploaded_slots.clear();
     HIPCHK(hipMemcpyAsync(m->frame_slot, &one, 4, hipMemcpyHostToDevice, m->stream));
+    ensure_qkv0(m);
     with_prec(m, [&](auto& r) {
         const void* last = r.prefill_slow(slot, tokens, T, pos0);
         const void* hid = r.head_small(last, false, 1, 1);
@@ -2287,6 +2400,7 @@ static void do_prefill_batch(fm_llm* m, int n, const int32_t* slots, const int32
     for (int i = 0; i < n; ++i) reset_slot(m, slots[i], sps ? sps + i : nullptr);
     m->uploaded_slots.clear();
     HIPCHK(hipMemcpyAsync(m->frame_slot, slots, (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
+    ensure_qkv0(m);
     with_prec(m, [&](auto& r) {
         r.prefill_multi(n, slots, tk.data(), T, pos0);
         if (n <= GEMV_MAX_ROWS) {
@@ -2598,6 +2712,7 @@ int fm_llm_teacher_step(fm_llm* m, int slot, const int32_t* x, int S, int pos0, 
         HIPCHK(hipMemcpyAsync(m->frame_slot, &one, 4, hipMemcpyHostToDevice, m->stream));
         m->uploaded_slots.clear();
         std::vector<float> lg(m->Nhead);
+        ensure_qkv0(m);
         with_prec(m, [&](auto& r) {
             const void* last = r.prefill_slow(slot, x, S, pos0);
             const void* hid = r.head_small(last, false, 1, 1);
@@ -2690,6 +2805,7 @@ int fm_tune(const char* key, int value) {
         FMCHECK(key, "null key");
         FmTuning& t = fm_tuning();
         const std::string k = key;
+        if (k != "debug_ts") ++t.epoch;  // (arming the timestamps changes no kernel choice)
         if (k == "gemv_nt") {
             t.gemv_nt = value != 0;
         } else if (k == "gemv_u") {
@@ -2858,7 +2974,8 @@ int fm_tune(const char* key, int value) {
         } else if (k == "row_copies") {
             t.row_copies = value != 0;
         } else if (k == "rowgemv") {
-            FMCHECK(value >= 0 && value <= 31, "rowgemv must be 0..31 (bit 0 wo / w2, bit 1 wqkv, bit 2 w1 || w3, bit 3 fast head, bit 4 first-layer wqkv)");
+            FMCHECK(value >= 0 && value <= 127, "rowgemv must be 0..127 (bit 0 wo / w2, bit 1 wqkv, bit 2 w1 || w3, bit 3 fast head, bit 4 first-layer wqkv, "
+                                                "bit 5 first fast layer's QKV from its table, bit 6 K / V only at codebook 0)");
             t.rowgemv = value;
         } else if (k == "rmsnorm_block") {
             t.rmsnorm_block = value != 0;
@@ -2898,6 +3015,7 @@ int fm_llm_kernel_bench(fm_llm* m, const char* cls, int reps, double* avg_us, in
         HIPCHK(hipSetDevice(m->device));
         const int n = (int)m->uploaded_slots.size();
         const bool was_on = m->prof.on;
+        ensure_qkv0(m);
         // record the class's launches of one eager frame (the frame itself runs normally)
         m->prof.on = false;
         m->prof.rec.clear();

@@ -438,9 +438,21 @@ void launch_rowgemv(hipStream_t s, const RowGemvArgs& a0, int kind) {
 constexpr int FW_MAXJ = 15;   // cached rows staged in LDS (cpos < 16)
 constexpr int FW_MAXHD = 128;
 
-template <int U, bool G, int QM>
+//
+// M (bf16 only): 0 the attention reads the raw q|k|v row the QKV launch left in at.qkv.
+// 1 (fm_tune rowgemv bit 5, the first layer at codebook > 0): that row is a pure function of the
+//   sampled code -- round(Wqkv rmsnorm(fast_embeddings[code]) + b) -- so it is read from the table
+//   of all codebook_size rows built at load time (A.qtab) and no QKV launch runs.  The index goes
+//   out first; the cached K / V rows (slot only) are issued before the table-row loads that wait
+//   on it.
+// 2 (bit 6, codebook 0): one position, so softmax = {1} and the output is 0 + 1 * v: no Q loads,
+//   no q prep, no score (the projection computed the K / V rows only).  The 0.f + stays: it is what
+//   turns a -0 of v into the +0 the full form stores.
+template <int U, bool G, int QM, int M>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
 void fattn_wo_kernel(FattnWoArgs A) {
+    static_assert(M == 0 || QM == 0, "table / K-V-only forms: bf16 only");
+    static_assert(2 * FW_MAXJ * FW_MAXHD / 8 <= 512, "cached rows: at most two 16-B chunks per thread");
     __shared__ __attribute__((aligned(16))) bf16_t kvs[2 * FW_MAXJ * FW_MAXHD];
     __shared__ float red[8];
     const FastFusedArgs<bf16_t>& at = A.at;
@@ -455,20 +467,44 @@ void fattn_wo_kernel(FattnWoArgs A) {
         // top issue priority: the wo waves sharing this CU queue their whole weight run at once
         if (A.prio) __builtin_amdgcn_s_setprio(3);
         const int kvh = blockIdx.x, hd = at.hd, g = at.nh / at.nkv, cpos = at.cpos, half = hd >> 1;
+        const bf16_t* qkv = at.qkv;
+        if constexpr (M == 1) {  // the table row of the sampled code (rowgemv_body's xi clamp)
+            const int32_t iv = A.qidx[A.qcol];
+            const int xi = iv < 0 ? 0 : (iv >= A.qrows ? A.qrows - 1 : iv);
+            qkv = A.qtab + (size_t)xi * at.ldqkv;
+        }
         const int slot = at.row_slot[0];
         const bool live = wave < g;
         const int h = kvh * g + (live ? wave : 0);
         const float* tab = at.rope + (size_t)cpos * hd;
+        const size_t base = (size_t)slot * at.slot_stride + at.layer_off + (size_t)kvh * at.S * hd;
+        const int nck = cpos * hd / 8;
+        // the cached rows j < cpos of this kv head -> LDS (K rows, then V rows), 16 B per thread
+        auto kv_src = [&](int i) {  // chunk i of the 2 * nck (past them: chunk 0, loaded and dropped)
+            const bool ok = i < 2 * nck, isv = ok && i >= nck;
+            const int c = ok ? (isv ? i - nck : i) : 0;
+            return reinterpret_cast<const u32x4_t*>((isv ? at.vc : at.kc) + base + (size_t)c * 8);
+        };
+        auto kv_dst = [&](int i) {
+            const bool isv = i >= nck;
+            return reinterpret_cast<u32x4_t*>(kvs + (isv ? FW_MAXJ * FW_MAXHD : 0) + (isv ? i - nck : i) * 8);
+        };
+        u32x4_t kvr[2];
+        if constexpr (M == 1) {  // in registers, ahead of the table-row loads (no branch: nothing drains)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) kvr[q] = *kv_src((int)threadIdx.x + 256 * q);
+        }
         float q0[2], q1[2], k0[2], k1[2], v0[2], v1[2], qw0[2], qw1[2], kw0[2], kw1[2], c_[2], s_[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int p = lane + 64 * u;
             const int pp = p < half ? p : 0;
-            ld_pair_bf(at.qkv + (size_t)h * hd + 2 * pp, q0[u], q1[u]);
-            ld_pair_bf(at.qkv + (size_t)(at.nh + kvh) * hd + 2 * pp, k0[u], k1[u]);
-            ld_pair_bf(at.qkv + (size_t)(at.nh + at.nkv + kvh) * hd + 2 * pp, v0[u], v1[u]);
+            if constexpr (M == 2) q0[u] = q1[u] = 0.f;
+            else ld_pair_bf(qkv + (size_t)h * hd + 2 * pp, q0[u], q1[u]);
+            ld_pair_bf(qkv + (size_t)(at.nh + kvh) * hd + 2 * pp, k0[u], k1[u]);
+            ld_pair_bf(qkv + (size_t)(at.nh + at.nkv + kvh) * hd + 2 * pp, v0[u], v1[u]);
             if (at.qk_norm) {
-                ld_pair_bf(at.qn + 2 * pp, qw0[u], qw1[u]);
+                if constexpr (M != 2) ld_pair_bf(at.qn + 2 * pp, qw0[u], qw1[u]);
                 ld_pair_bf(at.kn + 2 * pp, kw0[u], kw1[u]);
             } else {
                 qw0[u] = qw1[u] = kw0[u] = kw1[u] = 1.f;
@@ -477,14 +513,12 @@ void fattn_wo_kernel(FattnWoArgs A) {
             s_[u] = tab[2 * pp + 1];
             if (p >= half) q0[u] = q1[u] = k0[u] = k1[u] = v0[u] = v1[u] = 0.f;
         }
-        // the cached rows j < cpos of this kv head -> LDS (K rows, then V rows), 16 B per thread
-        const size_t base = (size_t)slot * at.slot_stride + at.layer_off + (size_t)kvh * at.S * hd;
-        const int nck = cpos * hd / 8;
-        for (int i = threadIdx.x; i < 2 * nck; i += 256) {
-            const bool isv = i >= nck;
-            const int c = isv ? i - nck : i;
-            const u32x4_t v = *reinterpret_cast<const u32x4_t*>((isv ? at.vc : at.kc) + base + (size_t)c * 8);
-            *reinterpret_cast<u32x4_t*>(kvs + (isv ? FW_MAXJ * FW_MAXHD : 0) + c * 8) = v;
+        if constexpr (M == 1) {
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+                if ((int)threadIdx.x + 256 * q < 2 * nck) *kv_dst((int)threadIdx.x + 256 * q) = kvr[q];
+        } else if constexpr (M == 0) {
+            for (int i = threadIdx.x; i < 2 * nck; i += 256) *kv_dst(i) = *kv_src(i);
         }
         // qk-norm (fp32 incl. weight, one rounding) + RoPE (bf16 table, rounded): fm_attn_dev.h
         auto prep = [&](float (&x0)[2], float (&x1)[2], const float (&w0)[2], const float (&w1)[2]) {
@@ -508,7 +542,7 @@ void fattn_wo_kernel(FattnWoArgs A) {
                 x1[u] = y1;
             }
         };
-        prep(q0, q1, qw0, qw1);
+        if constexpr (M != 2) prep(q0, q1, qw0, qw1);
         prep(k0, k1, kw0, kw1);
         if (wave == 0) {  // the group's new k / v of cpos into the fast cache
             bf16_t* kd = at.kc + base + (size_t)cpos * hd;
@@ -528,6 +562,14 @@ void fattn_wo_kernel(FattnWoArgs A) {
         const bf16_t* Ks = kvs;
         const bf16_t* Vs = kvs + FW_MAXJ * FW_MAXHD;
         // scores round(round(q.k) * scale), softmax, probabilities rounded (fast SDPA path)
+        float o0[2] = {0.f, 0.f}, o1[2] = {0.f, 0.f};
+        if constexpr (M == 2) {  // the one score's softmax is 1 (finite score): o = 0 + 1 * v
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                o0[u] = 0.f + v0[u];
+                o1[u] = 0.f + v1[u];
+            }
+        } else {
         float sc[FW_MAXJ + 1];
         float mx = -INFINITY;
 #pragma unroll
@@ -557,7 +599,6 @@ void fattn_wo_kernel(FattnWoArgs A) {
             sc[j] = expf(sc[j] - mx);
             den += sc[j];
         }
-        float o0[2] = {0.f, 0.f}, o1[2] = {0.f, 0.f};
 #pragma unroll
         for (int j = 0; j <= FW_MAXJ; ++j) {
             if (j > cpos) break;
@@ -575,6 +616,7 @@ void fattn_wo_kernel(FattnWoArgs A) {
                 o0[u] += pj * b0;
                 o1[u] += pj * b1;
             }
+        }
         }
         // tagged write-through store: word = bf16 << 16 | gen
 #pragma unroll
@@ -615,13 +657,28 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
             "fused fast attention + wo: shapes, tag and buffers");
     const dim3 grid(at.nkv + A.wo.N / 2), block(256);
     const bool G = A.wo.residx != nullptr;
+    // the table form gathers its residual row by the same index; the K / V-only form runs at codebook 0 (no gather)
+    FMCHECK(!A.qtab || (qm == 0 && G && !A.kv0 && A.qidx == A.wo.residx && A.qcol == A.wo.res_col && A.qrows > 0 &&
+                        A.qrows == A.wo.res_rows),
+            "fused fast attention + wo: the QKV table form is bf16, gathered by the residual's index");
+    FMCHECK(!A.kv0 || (qm == 0 && !G && at.cpos == 0), "fused fast attention + wo: the K / V-only form is bf16 at codebook 0");
+    if (A.qtab || A.kv0) {
+        switch (rowgemv_u(A.wo.K, 0)) {
+#define FW(u) \
+    case u: (A.qtab ? fattn_wo_kernel<u, true, 0, 1> : fattn_wo_kernel<u, false, 0, 2>)<<<grid, block, 0, s>>>(A); break;
+            FW(2) FW(3) FW(4) FW(5) FW(6)
+            default: (A.qtab ? fattn_wo_kernel<8, true, 0, 1> : fattn_wo_kernel<8, false, 0, 2>)<<<grid, block, 0, s>>>(A); break;
+#undef FW
+        }
+        return;
+    }
     auto go = [&](auto q) {
         constexpr int Q = decltype(q)::value;
         switch (rowgemv_u(A.wo.K, Q)) {
 #define FW(u) \
-    case u: (G ? fattn_wo_kernel<u, true, Q> : fattn_wo_kernel<u, false, Q>)<<<grid, block, 0, s>>>(A); break;
+    case u: (G ? fattn_wo_kernel<u, true, Q, 0> : fattn_wo_kernel<u, false, Q, 0>)<<<grid, block, 0, s>>>(A); break;
             FW(2) FW(3) FW(4) FW(5) FW(6)
-            default: (G ? fattn_wo_kernel<8, true, Q> : fattn_wo_kernel<8, false, Q>)<<<grid, block, 0, s>>>(A); break;
+            default: (G ? fattn_wo_kernel<8, true, Q, 0> : fattn_wo_kernel<8, false, Q, 0>)<<<grid, block, 0, s>>>(A); break;
 #undef FW
         }
     };

@@ -225,7 +225,15 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    "linear_u32" n, "linear_fill" n; prompt "prefill_attn", "prompt_gemm"; voice prefix copy "prefix_vec" 0|1; codec "conv2",
    "conv_splitk"; "sampler_fast" 0|1, "rmsnorm_block" 0|1, "debug_ts" n; batch-1 row-block GEMV
    "rowgemv" / "rowgemv_q4" bits, "row_copies" 0|1 (0: finalize keeps only the row-major weight
-   copies those bits select).  They apply to launches
+   copies those bits select).  "rowgemv" 0..127, default 123: bits 0-4 put wo / w2, wqkv, w1 || w3,
+   the codebook head and the first layers' wqkv on the row-block GEMV; bit 5 (32): the first fast
+   layer's QKV projection at codebooks >= 1 -- a pure function of the sampled code -- is read from a
+   table of its codebook_size rows (codebook_size x fast nqkv bf16, 50 MB at S2-Pro; built by
+   fm_llm_finalize with the frame's own kernel, one launch per code, and rebuilt before the next
+   frame after any fm_tune call but "debug_ts") instead of being launched; bit 6 (64): at codebook
+   0, where the fast attention has one position and its output is v, the fast layers project K / V
+   only and the attention reads no Q.  Bits 5 and 6 change no output bit (finite scores); they act
+   on bf16 unquantised models, batch 1, and are inert elsewhere.  They apply to launches
    recorded after the call (graphs captured earlier keep theirs). */
 int fm_tune(const char* key, int value);
 /* developer hook ("debug_ts" armed): per-block records of 8 words {tag = N<<32 | blockIdx.y<<16 |

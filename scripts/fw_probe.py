@@ -1,7 +1,9 @@
 """Timeline of the fused fast attention + wo launch (fm_rowgemv.hip fattn_wo_kernel) from its
 debug_ts records: attention waves (0xFFF9: start, K/V staged, stored) and sampled wo blocks
 (0xFFF8: start, weights issued, cheap poll done, full x read, end; aux = polls), per launch,
-relative to the launch's first block start (us)."""
+relative to the launch's first block start (us).  An optional argument sets fm_tune rowgemv first
+(27: the QKV launches of today; 123: first-layer QKV table + K / V only at codebook 0); the first
+fast layer's launches at codebooks >= 1 -- the ones that read the table -- are also listed apart."""
 import os
 import sys
 
@@ -16,6 +18,8 @@ from fishmi.llm import DualARModel  # noqa: E402
 cfg = DualARConfig._from_fish_qwen3_omni(S2_PRO_CONFIG)
 cfg.im_end_id = S2_PRO_IM_END_ID
 cfg.max_seq_len = 1024
+if len(sys.argv) > 1:
+    native.tune("rowgemv", int(sys.argv[1]))
 m = DualARModel.synthetic(cfg, seed=0, log2_half=5, device=0, precision="bf16", max_slots=1)
 p = np.zeros((cfg.num_codebooks + 1, 64), np.int32)
 p[0] = np.random.default_rng(1).integers(16, cfg.semantic_begin_id, 64)
@@ -31,12 +35,13 @@ wo = rec[(rec[:, 0] >> 32) == 0xFFF8]
 # launches: attention records sorted by start, split at gaps > 3 us
 att = att[np.argsort(att[:, 1])]
 cut = np.where(np.diff(att[:, 1]) > 300)[0] + 1
-rows = []
-for g in np.split(att, cut):
+rows, kept = [], []
+for li, g in enumerate(np.split(att, cut)):
     t0 = g[:, 1].min()
     w = wo[(wo[:, 1] >= t0 - 100) & (wo[:, 1] < t0 + 3000)]
     if not len(w):
         continue
+    kept.append(li)
     T = lambda x: (x - t0) / 100.0
     rows.append([T(g[:, 2].max()), T(g[:, 3].max()), T(w[:, 1].max()), T(w[:, 2]).mean(), T(w[:, 3]).mean(),
                  T(w[:, 4]).mean(), T(w[:, 5]).mean(), T(w[:, 5]).max(), np.mean(w[:, 0] & 0xFFFFFFFF)])
@@ -46,3 +51,16 @@ names = ["att staged(max)", "att stored(max)", "wo last start", "wo weights issu
          "wo x read", "wo end(mean)", "wo end(max)", "polls"]
 for n, v in zip(names, r.mean(axis=0)):
     print(f"  {n:18s} {v:7.2f}")
+# a frame's fused launches in order: codebook 0's layers but the last (K / V only, not fused), then every
+# layer of codebooks 1 .. C-1; the first layer's are at n_layer - 1 + n_layer * k
+nl, C = cfg.n_fast_layer, cfg.num_codebooks
+per = nl * C - 1
+kept = np.array(kept)
+if len(cut) + 1 == 2 * per:
+    sel = np.isin(kept % per, [nl - 1 + nl * k for k in range(C - 1)])
+    print(f"first fast layer at codebooks >= 1 ({int(sel.sum())} launches):")
+    for n, v in zip(names, r[sel].mean(axis=0)):
+        print(f"  {n:18s} {v:7.2f}")
+    print(f"the other fused launches ({int((~sel).sum())}):")
+    for n, v in zip(names, r[~sel].mean(axis=0)):
+        print(f"  {n:18s} {v:7.2f}")
