@@ -156,11 +156,19 @@ __device__ __forceinline__ typename Frag<T>::f bs_norm8(typename Frag<T>::f x, f
 // whole run do the waves meet once: every (tile, wave) partial goes to LDS, then the epilogue of
 // all the block's tiles.  kparts is chosen so that tiles * kparts is a whole number of rounds of
 // the grid (no block streams twice as much as another).
-template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO>
+// WQ 1 (weight-only int8, fm_tune bstream_q8): the ring holds the raw 8-byte code words of a.Wq8, the
+// step-granular int8 copy [tile][K/32][64 lanes][8 B] (launch_pack_q8s: the bf16 fragments' index
+// order at half the bytes), and each slot becomes a bf16 fragment (Frag::dq8s, exact) right before
+// its two MFMAs.  A slot is 2 VGPRs, not 4, so the ring is twice as many tiles deep (capped at the
+// NTM the block can own): the bytes in flight per wave stay what they were.  Partition, step order,
+// reduction and epilogues are the bf16 form's, so the results are bit-identical to it.
+template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO, int WQ = 0>
 __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
     using F = Frag<T>;
+    static_assert(!WQ || (sizeof(T) == 2 && PRO == PRO_PLAIN && EPI != EPI_SLABFIN), "bsacc int8 codes: bf16, plain forms");
     extern __shared__ __attribute__((aligned(16))) f32x4_t bred[];  // [NTM][NW][2][64]
-    constexpr int U = SPW * TPI;
+    constexpr int TPR = WQ ? (2 * TPI < NTM ? 2 * TPI : NTM) : TPI;  // ring depth in tiles
+    constexpr int U = SPW * TPR;
     const unsigned long long ts0 = a.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
     unsigned long long ts1 = 0, tsx = 0;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, NW = blockDim.x >> 6;
@@ -173,15 +181,21 @@ __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
     const int wa = s0 + wave * Sp / NW, nst = s0 + (wave + 1) * Sp / NW - wa;  // host: 1 <= nst <= SPW
     const int r = lane & 15, g = lane >> 4;
     const int ra = r < a.R ? r : a.R - 1, rb = 16 + r < a.R ? 16 + r : a.R - 1;
-    // weights (they do not depend on X): ring slot u = (t % TPI) * SPW + j holds (tile t, step j)
+    // weights (they do not depend on X): ring slot u = (t % TPR) * SPW + j holds (tile t, step j)
     const T* wbase = a.W + ((size_t)t0 * S + wa) * 512;
     const int tl = ntl - 1, jl = nst - 1;
-    typename F::f fa[U];
+    typename std::conditional<WQ != 0, u32x2_t, typename F::f>::type fa[U];
     auto issue = [&](int t, int j) {
         const int tt = t < tl ? t : tl, jj = j < jl ? j : jl;
         const bool past = a.dummy_tail && (t > tl || j > jl);  // not this block's: one cached fragment
-        const T* dsrc = a.W + (a.dummy_tail == 2 ? (size_t)((blockIdx.x * 8 + wave) & 255) % ((size_t)T_ * S) * 512 : 0);
-        fa[(t % TPI) * SPW + j] = F::template load_w<true>(past ? dsrc : wbase + ((size_t)tt * S + jj) * 512, lane);
+        if constexpr (WQ) {  // the same (tile, step) indices into 512-byte code fragments
+            const size_t dfrag = a.dummy_tail == 2 ? (size_t)((blockIdx.x * 8 + wave) & 255) % ((size_t)T_ * S) : 0;
+            const size_t frag = past ? dfrag : (size_t)(t0 + tt) * S + wa + jj;
+            fa[(t % TPR) * SPW + j] = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(a.Wq8 + frag * 512) + lane);
+        } else {
+            const T* dsrc = a.W + (a.dummy_tail == 2 ? (size_t)((blockIdx.x * 8 + wave) & 255) % ((size_t)T_ * S) * 512 : 0);
+            fa[(t % TPI) * SPW + j] = F::template load_w<true>(past ? dsrc : wbase + ((size_t)tt * S + jj) * 512, lane);
+        }
     };
     // X operands.  PRO_PRENORM also loads the norm weight and the producer's per-tile sums of squares
     // here, laid out [R][K/16] by bsacc's EPI_SLABFIN (rows w + NW * i of wave w, tiles lane + 64 * jj;
@@ -215,7 +229,7 @@ __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
     };
     if (a.xfirst) load_x();
 #pragma unroll
-    for (int t = 0; t < TPI; ++t)
+    for (int t = 0; t < TPR; ++t)
 #pragma unroll
         for (int j = 0; j < SPW; ++j) issue(t, j);
     if (!a.xfirst) load_x();
@@ -250,10 +264,16 @@ __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
     for (int t = 0; t < NTM; ++t) {
 #pragma unroll
         for (int j = 0; j < SPW; ++j) {
-            const int u = (t % TPI) * SPW + j;
-            acc[t][0] = F::mma(fa[u], xa[j], acc[t][0]);
-            acc[t][1] = F::mma(fa[u], xb[j], acc[t][1]);
-            if (t + TPI < NTM) issue(t + TPI, j);
+            const int u = (t % TPR) * SPW + j;
+            if constexpr (WQ) {
+                const typename F::f w = F::dq8s(fa[u]);
+                acc[t][0] = F::mma(w, xa[j], acc[t][0]);
+                acc[t][1] = F::mma(w, xb[j], acc[t][1]);
+            } else {
+                acc[t][0] = F::mma(fa[u], xa[j], acc[t][0]);
+                acc[t][1] = F::mma(fa[u], xb[j], acc[t][1]);
+            }
+            if (t + TPR < NTM) issue(t + TPR, j);
             __builtin_amdgcn_sched_barrier(0);  // each refill right behind its consumer
             if (t == 0 && j == 0 && a.dbg) ts1 = __builtin_amdgcn_s_memrealtime();
         }
@@ -702,9 +722,9 @@ BstreamPlan bstream_plan(int N, int K, int R, int epi, size_t esz) {
 
 // > 64 KiB of dynamic LDS needs the kernel attribute, which must not be set inside a stream capture
 // (the first batched frame is captured): bsacc_init sets it for every instantiation up front
-template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO>
+template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO, int WQ = 0>
 static void bsacc_attr() {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bsacc_kernel<T, SPW, TPI, NTM, EPI, PRO>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bsacc_kernel<T, SPW, TPI, NTM, EPI, PRO, WQ>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 template <typename T, int SPW, int TPI, int NTM>
@@ -716,11 +736,28 @@ static void bsacc_attr_all() {
     bsacc_attr<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN>();
     bsacc_attr<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN>();
     bsacc_attr<T, SPW, TPI, NTM, EPI_SLABFIN, PRO_PLAIN>();
+    if constexpr (sizeof(T) == 2) {  // the int8-code forms (bsacc_q8_ok)
+        bsacc_attr<T, SPW, TPI, NTM, EPI_STORE, PRO_PLAIN, 1>();
+        bsacc_attr<T, SPW, TPI, NTM, EPI_SWIGLU8, PRO_PLAIN, 1>();
+        bsacc_attr<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN, 1>();
+        bsacc_attr<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN, 1>();
+    }
 }
-template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO>
+template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO, int WQ = 0>
 static void bsacc_launch(hipStream_t s, const BstreamArgs<T>& a, int G, int NW) {
     const size_t lds = (size_t)NTM * NW * 2 * 64 * sizeof(f32x4_t);
-    bsacc_kernel<T, SPW, TPI, NTM, EPI, PRO><<<dim3(G), dim3(NW * 64), lds, s>>>(a);
+    bsacc_kernel<T, SPW, TPI, NTM, EPI, PRO, WQ><<<dim3(G), dim3(NW * 64), lds, s>>>(a);
+}
+// the default batched frame's forms on the int8 codes (a.Wq8 set: launch_bstream checked bsacc_q8_ok)
+template <typename T, int SPW, int TPI, int NTM>
+static void bsacc_go_q8(hipStream_t s, const BstreamArgs<T>& a, int epi, int G, int NW) {
+    switch (epi) {
+        case EPI_STORE: bsacc_launch<T, SPW, TPI, NTM, EPI_STORE, PRO_PLAIN, 1>(s, a, G, NW); break;
+        case EPI_SWIGLU8: bsacc_launch<T, SPW, TPI, NTM, EPI_SWIGLU8, PRO_PLAIN, 1>(s, a, G, NW); break;
+        case EPI_F32: bsacc_launch<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN, 1>(s, a, G, NW); break;
+        case EPI_SLAB: bsacc_launch<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN, 1>(s, a, G, NW); break;
+        default: FMCHECK(false, "bsacc: no int8-code form of this epilogue");
+    }
 }
 template <typename T, int SPW, int TPI, int NTM>
 static void bsacc_go(hipStream_t s, const BstreamArgs<T>& a, int epi, int G, int NW) {
@@ -745,9 +782,15 @@ static void bsacc_go(hipStream_t s, const BstreamArgs<T>& a, int epi, int G, int
     }
 }
 
+bool bsacc_q8_ok(const BstreamPlan& p, int epi, int pro, size_t esz) {
+    return p.ok && p.acc && esz == 2 && pro == PRO_PLAIN &&
+           (epi == EPI_STORE || epi == EPI_SWIGLU8 || epi == EPI_F32 || epi == EPI_SLAB);
+}
+
 template <typename T> bool launch_bstream(hipStream_t s, const BstreamArgs<T>& a0, int epi, const BstreamPlan& p) {
     if (!p.ok) return false;
     BstreamArgs<T> a = a0;
+    if (!bsacc_q8_ok(p, epi, a.pro, sizeof(T))) a.Wq8 = nullptr;  // no int8-code form: the bf16 fragments
     a.kparts = p.kparts;
     a.dummy_tail = fm_tuning().bs_dummy;
     a.xfirst = fm_tuning().bs_xfirst;
@@ -755,10 +798,11 @@ template <typename T> bool launch_bstream(hipStream_t s, const BstreamArgs<T>& a
     if (p.acc) {
         if constexpr (sizeof(T) == 2) {
             FMCHECK(epi != EPI_SWIGLU8 || a.N % 16 == 0, "bsacc: SwiGLU8 needs whole interleaved tiles");
-#define BSA(SPW, TPI, NTM)                                      \
-    if (p.spw == SPW && p.tpi == TPI && p.ntm == NTM) {         \
-        bsacc_go<T, SPW, TPI, NTM>(s, a, epi, p.grid, p.nw);    \
-        return true;                                            \
+#define BSA(SPW, TPI, NTM)                                               \
+    if (p.spw == SPW && p.tpi == TPI && p.ntm == NTM) {                  \
+        if (a.Wq8) bsacc_go_q8<T, SPW, TPI, NTM>(s, a, epi, p.grid, p.nw); \
+        else bsacc_go<T, SPW, TPI, NTM>(s, a, epi, p.grid, p.nw);        \
+        return true;                                                     \
     }
             BSA(2, 4, 2) BSA(2, 4, 3) BSA(2, 4, 5) BSA(2, 4, 6) BSA(5, 2, 2) BSA(5, 2, 3) BSA(5, 2, 5)
             BSA(5, 2, 6) BSA(10, 1, 2) BSA(10, 1, 3) BSA(10, 1, 5) BSA(10, 1, 6)

@@ -12,6 +12,8 @@
 //   mma(a, b, c)            c += a . b over the 32-wide k block
 //   dq8(raw, f0, f1)        16 int8 weights (one int8 unit of a lane: 8 k of k-step 2u, then 8 k
 //                           of k-step 2u + 1) as two exact T fragments (weight-only int8)
+//   dq8s(raw)               8 int8 weights (one k-step of a lane, the step-granular int8 copy of
+//                           the batched stream) as one exact bf16 fragment: dq8's arithmetic
 #pragma once
 #include "fm_common.h"
 
@@ -49,6 +51,15 @@ template <> struct Frag<bf16_t> {
                 o[2 * w + 1] = hi_pair(i8f(v, 2), i8f(v, 3));
             }
         }
+    }
+    static __device__ __forceinline__ f dq8s(u32x2_t raw) {
+        f o;
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            o[2 * w] = hi_pair(i8f(raw[w], 0), i8f(raw[w], 1));
+            o[2 * w + 1] = hi_pair(i8f(raw[w], 2), i8f(raw[w], 3));
+        }
+        return o;
     }
     // 8 int4 codes (nibble e = k e of the lane's 8) -> 8 bf16 values bf16(fma(q - 8, s, z)), RNE
     // (the weight-only int4 dequantisation, launch_quant4 / quantize.py:139-160's affine form)

@@ -23,6 +23,10 @@ template <typename T> void launch_i8_to(hipStream_t s, const int8_t* q, int64_t 
 // int8 row-major [N][K] -> the int8 decode-GEMV layout: [ceil(N/16)][K/64] units of 1 KiB, lane l
 // (row l & 15, k-offset 8 * (l >> 4)) holding 8 bytes of k-step 2u then 8 bytes of k-step 2u + 1
 void launch_pack_q8(hipStream_t s, const int8_t* src, int N, int K, int8_t* dst);
+// int8 row-major [N][K] -> the batched stream's step-granular layout (fm_bstream.hip, 8 < R <= 32):
+// [ceil(N/16)][K/32] fragments of 512 B, lane l (row l & 15, k-offset 8 * (l >> 4)) holding its 8
+// bytes of that k-step -- the packed bf16 fragments' index order at one byte per weight
+void launch_pack_q8s(hipStream_t s, const int8_t* src, int N, int K, int8_t* dst);
 // Weight-only int4, groupwise affine (tools/llama/quantize.py:57-160, WeightOnlyInt4QuantHandler
 // :352-418), bf16 only.  quant4: per (row, group of gs along K) of a row-major bf16 [N][K] w, the
 // reference's group_quantize_tensor in its bf16 arithmetic (every op computed in fp32 and rounded to
@@ -313,6 +317,8 @@ struct FmTuning {
     int q_u = 4;             // int8 / int4 decode GEMV: ring units in flight per wave (2, 4, 8, 16; int8 frame 3.79 -> 3.59 ms at 8 -> 4)
     int fin8 = 1;            // finalize_norm: all eight K parts' slab loads in one round trip (0: two batches of four)
     int fin_split = 0;       // batched finalize_norm: each row over this many blocks (0 / 1: one block per row)
+    int bstream_q8 = 1;      // weight-only int8, 8 < R <= 32: 1 bsacc_kernel streams the int8 codes, 0 their bf16 fragment copy
+                             // (bit-identical; int8 B=32 frame 6.441 -> 5.761 ms, the bf16 model's 6.184; profiles/b32_int8.md)
     int int4_stream = 1;     // weight-only int4: 1 the batch <= 8 GEMVs stream the 4-bit codes, 0 the dequantised bf16 copy
     int fw_delay = 0;        // fattn_wo: FattnWoArgs::delay
     int fw_cheap = 0;        // fattn_wo: FattnWoArgs::cheap
@@ -471,6 +477,9 @@ template <typename T> struct BstreamArgs {
     int dummy_tail = 0;  // bsacc: ring slots past the block's tiles / steps load one cached fragment
     int xfirst = 1;      // bsacc: X (and the PRENORM operands) issued before the weight ring (fm_tune bs_xfirst)
     int vec_epi = 1;     // bsacc: epilogue items of 4 rows (16-byte LDS reads, 8 / 16-byte stores; fm_tune bs_vec_epi)
+    // weight-only int8 (fm_tune bstream_q8): the step-granular code copy of W, [tiles][K/32][64 lanes][8 B]
+    // (launch_pack_q8s).  Set: bsacc_kernel streams it instead of W where bsacc_q8_ok, else W as ever.
+    const unsigned char* Wq8 = nullptr;
 };
 struct BstreamPlan {
     bool ok = false;
@@ -478,6 +487,8 @@ struct BstreamPlan {
     int acc = 0, ntm = 0;  // bsacc_kernel: tiles per block at most (register accumulators)
 };
 BstreamPlan bstream_plan(int N, int K, int R, int epi, size_t esz);
+// whether launch_bstream has an int8-code form (BstreamArgs::Wq8) for this plan, epilogue and prologue
+bool bsacc_q8_ok(const BstreamPlan& p, int epi, int pro, size_t esz);
 void bsacc_init();  // kernel attributes (> 64 KiB LDS) of every bsacc_kernel, outside any capture
 template <typename T> bool launch_bstream(hipStream_t s, const BstreamArgs<T>& a, int epi, const BstreamPlan& p);
 // x_out = round(res + round(sum of kparts slabs + bias)); if nw: xn_out = RMSNorm(x_out) * nw

@@ -176,6 +176,9 @@ struct fm_llm {
         const unsigned char* q8 = nullptr;  // packed int8 (int4: 4-bit codes) decode-GEMV layout
         const void* scale = nullptr;        // int8: [rows padded to 16] in packed row order
         const uint32_t* sz = nullptr;       // int4: packed (scale, zero) per (tile, 128-k unit, row)
+        // int8, bf16, max_slots > 8: the step-granular code copy the batched linears stream
+        // (launch_pack_q8s; its own allocation, whatever row_copies frees)
+        const unsigned char* q8s = nullptr;
     };
     std::map<const void*, QInfo> qmap;
     std::map<const void*, void*> rowmajor;  // packed wo / w2 / wqkv -> row-major bf16 copy (int8 / int4: codes)
@@ -477,7 +480,10 @@ template <typename T> struct Run {
         const BstreamPlan p = bstream_plan(N, K, R, epi, E);
         if (!p.ok || ((epi == EPI_SLABFIN || (ex && ex->pro == PRO_PRENORM)) && !p.acc)) return false;
         BstreamArgs<T> a{(const T*)W, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y, ldy, Yf};
-        if (const auto* q = m->qinfo(W)) a.wscale = (const T*)q->scale;
+        const auto* q = m->qinfo(W);
+        if (q) a.wscale = (const T*)q->scale;
+        // weight-only int8 (fm_tune bstream_q8): the accumulating kernel streams the codes where it has the form
+        if (q && q->q8s && fm_tuning().bstream_q8 && bsacc_q8_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E)) a.Wq8 = q->q8s;
         a.dbg = fm_tuning().dbg;
         if (ex) {
             a.pro = ex->pro;
@@ -491,7 +497,8 @@ template <typename T> struct Run {
             a.ss_out = ex->ss_out;
             a.tickets = m->tickets;
         }
-        const int64_t bytes = (int64_t)N * K * E + (int64_t)R * K * E +
+        const int64_t wbytes = a.Wq8 ? (int64_t)N * K + (int64_t)N * 2 : (int64_t)N * K * E;  // codes + row scales
+        const int64_t bytes = wbytes + (int64_t)R * K * E +
                               (int64_t)R * N * (epi == EPI_SLAB ? 4 * p.kparts : (epi == EPI_F32 ? 4 : E));
         const double flops = 2.0 * R * N * K;
         hipStream_t st = s;
@@ -1600,6 +1607,18 @@ static void* pack_q8_dev(fm_llm* m, const void* q, int rows, int cols) {
     return dst;
 }
 
+// the batched linears' step-granular copy of the same codes: only where bsacc_kernel can take it (int8,
+// bf16, a handle with more than GEMV_MAX_ROWS slots); a max_slots <= 8 handle allocates nothing here
+static const unsigned char* pack_q8s_dev(fm_llm* m, const void* q, int rows, int cols) {
+    if (m->quant != FM_QUANT_INT8 || m->prec != FM_PREC_BF16 || m->max_slots <= GEMV_MAX_ROWS || cols % 32) return nullptr;
+    void* dst = nullptr;
+    HIPCHK(hipMalloc(&dst, (size_t)(rows + 15) / 16 * 16 * cols));
+    launch_pack_q8s(m->stream, (const int8_t*)q, rows, cols, (int8_t*)dst);
+    HIPCHK(hipGetLastError());
+    m->allocs.push_back(dst);
+    return (const unsigned char*)dst;
+}
+
 // int4: codes row-major [rows][cols] + sz [rows][cols / gs] -> the packed GEMV stream and its
 // (scale, zero) table; none (the bf16 dequantised copy serves every kernel) unless the group size
 // and K are whole 128-k units
@@ -1788,7 +1807,8 @@ static void* pack_w13(fm_llm* m, const std::string& p, int inter, int dim) {
         HIPCHK(hipMemcpy2DAsync(s13, 16 * E, t1.s, 8 * E, 8 * E, inter / 8, hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipMemcpy2DAsync((char*)s13 + 8 * E, 16 * E, t3.s, 8 * E, 8 * E, inter / 8, hipMemcpyDeviceToDevice,
                                 m->stream));
-        m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, qt, 2 * inter, dim), s13};
+        m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, qt, 2 * inter, dim), s13, nullptr,
+                                    pack_q8s_dev(m, qt, 2 * inter, dim)};
         HIPCHK(hipStreamSynchronize(m->stream));
         HIPCHK(hipFree(qt));
         HIPCHK(hipFree(t1.q));
@@ -1833,7 +1853,8 @@ static void finalize(fm_llm* m) {
             t.q = nullptr;
             t.s = nullptr;
         } else if (m->quant) {
-            m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, t.q, (int)t.rows, (int)t.cols), t.s};
+            m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, t.q, (int)t.rows, (int)t.cols), t.s, nullptr,
+                                        pack_q8s_dev(m, t.q, (int)t.rows, (int)t.cols)};
             HIPCHK(hipStreamSynchronize(m->stream));
             if (row_keep(m, kv.first, (int)t.rows, (int)t.cols)) {
                 m->rowmajor[pk] = t.q;  // the int8 codes, row-major, for the row-block GEMV
@@ -1957,7 +1978,8 @@ static void finalize(fm_llm* m) {
                               hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipMemcpyAsync((char*)hs + (size_t)m->nsem * m->esz, (const char*)o.s + (size_t)c.im_end_id * m->esz,
                               m->esz, hipMemcpyDeviceToDevice, m->stream));
-        m->qmap[m->head_c] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, hq, m->Nhead, c.dim), hs};
+        m->qmap[m->head_c] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, hq, m->Nhead, c.dim), hs, nullptr,
+                                           pack_q8s_dev(m, hq, m->Nhead, c.dim)};
         HIPCHK(hipStreamSynchronize(m->stream));
         HIPCHK(hipFree(o.q));
         o.q = nullptr;
@@ -2954,6 +2976,8 @@ int fm_tune(const char* key, int value) {
             t.fin_split = value;
         } else if (k == "int4_stream") {
             t.int4_stream = value != 0;
+        } else if (k == "bstream_q8") {
+            t.bstream_q8 = value != 0;
         } else if (k == "fw_delay") {
             FMCHECK(value >= 0 && value <= 1000, "fw_delay must be 0..1000 (10-ns ticks)");
             t.fw_delay = value;

@@ -246,6 +246,24 @@ void launch_pack_q8(hipStream_t s, const int8_t* src, int N, int K, int8_t* dst)
     const int64_t n = (int64_t)((N + 15) / 16) * (K / 64) * 64;
     pack_q8_kernel<<<(int)std::min<int64_t>(FM_CEIL(n, 256), 16384), 256, 0, s>>>(src, N, K, dst);
 }
+// one thread per (fragment, lane): 8 bytes = one k-step of row (l & 15), k-offset 8 * (l >> 4)
+__global__ void pack_q8s_kernel(const int8_t* __restrict__ src, int N, int K, int8_t* __restrict__ dst) {
+    const int S = K >> 5;
+    const int64_t n = (int64_t)((N + 15) / 16) * S * 64;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t frag = i >> 6;
+        const int l = (int)(i & 63);
+        const int t = (int)(frag / S), sidx = (int)(frag - (int64_t)t * S);
+        const int row = 16 * t + (l & 15);
+        int8_t* d = dst + i * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d[j] = row < N ? src[(size_t)row * K + 32 * sidx + 8 * (l >> 4) + j] : (int8_t)0;
+    }
+}
+void launch_pack_q8s(hipStream_t s, const int8_t* src, int N, int K, int8_t* dst) {
+    const int64_t n = (int64_t)((N + 15) / 16) * (K / 32) * 64;
+    pack_q8s_kernel<<<(int)std::min<int64_t>(FM_CEIL(n, 256), 16384), 256, 0, s>>>(src, N, K, dst);
+}
 // ---- weight-only int4 (tools/llama/quantize.py:57-160) --------------------------------------
 // one thread per (row, group): get_group_qparams + group_quantize_tensor_from_qparams in torch's bf16
 // arithmetic (fp32 op, bf16 rounding after every op), then the dequantised bf16 weight in place

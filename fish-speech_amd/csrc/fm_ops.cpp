@@ -13,6 +13,8 @@
 //   fm_op_prompt_attn  the prompt-chunk causal attention (llama.py:883-946) over a cache prefix,
 //                   on the split kernel or the flash-form attn_prefill_kernel
 //   fm_op_embed     the Dual-AR input embedding (llama.py:399-420)
+//   fm_op_batched_linear_q8  the batched decode linear (bsacc_kernel) on weight-only int8 codes and on
+//                   their bf16 fragment copy (fm_tune bstream_q8)
 //   fm_rope_table   the host-built bf16 cos/sin table (no device needed)
 // Operands are fp32 host arrays, converted to the precision's storage type (bf16 rounding is the
 // caller's business: pass bf16-valued floats for bit-level comparisons).
@@ -468,6 +470,60 @@ int fm_op_quant4(int device, const float* w, int N, int K, int gs, uint8_t* q, f
             HIPCHK(hipMemcpyAsync(y_q4, dy, (size_t)R * N * 4, hipMemcpyDeviceToHost, g.s));
             HIPCHK(hipStreamSynchronize(g.s));
         }
+    });
+}
+
+// weight-only int8 on the batched decode linear: the device quantizer (launch_quant_rows), then the
+// same bstream plan / launch on the bf16 fragment copy of the codes and on the step-granular int8
+// copy (BstreamArgs::Wq8).  Outputs as fp32: [R][N] (EPI_STORE / EPI_F32), [R][N / 2] (EPI_SWIGLU8),
+// raw slabs [kparts][R][N] (EPI_SLAB).
+int fm_op_batched_linear_q8(int device, const float* w, int N, int K, const float* x, int R, int epi,
+                            float* y_q8, float* y_bf16, int* kparts, int8_t* q_out, float* scale_out) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y_q8 && y_bf16 && N >= 1 && K >= 32 && K % 32 == 0 && R > 8 && R <= 32, "bad arguments");
+        FMCHECK(epi == EPI_STORE || epi == EPI_F32 || epi == EPI_SLAB || (epi == EPI_SWIGLU8 && N % 16 == 0),
+                "epi must be 0 (store), 3 (fp32), 4 (slabs) or 7 (SwiGLU, whole 16-row tiles)");
+        StreamGuard g(device);
+        DevBufs b(g.s);
+        bsacc_init();
+        const BstreamPlan p = bstream_plan(N, K, R, epi, 2);
+        FMCHECK(bsacc_q8_ok(p, epi, PRO_PLAIN, 2), "no int8-code batched kernel for this shape");
+        const int Np = (N + 15) / 16 * 16;
+        bf16_t* dw = (bf16_t*)b.alloc((size_t)Np * K * 2);
+        {
+            bf16_t* t = b.upload<bf16_t>(w, (size_t)N * K);
+            HIPCHK(hipMemcpyAsync(dw, t, (size_t)N * K * 2, hipMemcpyDeviceToDevice, g.s));
+        }
+        int8_t* dq = (int8_t*)b.alloc((size_t)Np * K);
+        bf16_t* ds = (bf16_t*)b.alloc((size_t)Np * 2);
+        launch_quant_rows<bf16_t>(g.s, dw, N, K, dq, ds);  // dw <- bf16(q)
+        bf16_t* pk = (bf16_t*)b.alloc((size_t)Np * K * 2);
+        launch_pack<bf16_t>(g.s, dw, N, K, pk);
+        int8_t* pq = (int8_t*)b.alloc((size_t)Np * K);
+        launch_pack_q8s(g.s, dq, N, K, pq);
+        HIPCHK(hipGetLastError());
+        if (q_out) HIPCHK(hipMemcpyAsync(q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, g.s));
+        if (scale_out) download<bf16_t>(ds, (size_t)N, scale_out, g.s);
+        bf16_t* dx = b.upload<bf16_t>(x, (size_t)R * K);
+        const int No = epi == EPI_SWIGLU8 ? N / 2 : N;
+        const bool f32 = epi == EPI_F32 || epi == EPI_SLAB;
+        const size_t ny = (size_t)(epi == EPI_SLAB ? p.kparts : 1) * R * No;
+        for (int form = 0; form < 2; ++form) {
+            void* dy = b.alloc(ny * (f32 ? 4 : 2));
+            BstreamArgs<bf16_t> a{pk, nullptr, dx, K, R, N, K, f32 ? nullptr : (bf16_t*)dy, No, f32 ? (float*)dy : nullptr};
+            a.wscale = ds;
+            if (form) a.Wq8 = (const unsigned char*)pq;
+            FMCHECK(launch_bstream<bf16_t>(g.s, a, epi, p), "bstream: no kernel for the plan");
+            HIPCHK(hipGetLastError());
+            float* out = form ? y_q8 : y_bf16;
+            if (f32) {
+                HIPCHK(hipMemcpyAsync(out, dy, ny * 4, hipMemcpyDeviceToHost, g.s));
+                HIPCHK(hipStreamSynchronize(g.s));
+            } else {
+                download<bf16_t>((const bf16_t*)dy, ny, out, g.s);
+            }
+        }
+        if (kparts) *kparts = p.kparts;
     });
 }
 

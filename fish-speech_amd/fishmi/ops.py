@@ -142,3 +142,32 @@ def quant4(w, gs, x=None, device=0):
                                            native.f32p(zr), native.f32p(wd), native.f32p(x), R,
                                            native.f32p(y4) if y4 is not None else None, native.f32p(yb)))
     return q, sc, zr, wd, yb, y4
+
+
+EPI_STORE, EPI_F32, EPI_SLAB, EPI_SWIGLU8 = 0, 3, 4, 7
+
+
+def batched_linear_q8(w, x, epi, device=0):
+    """fm_op_batched_linear_q8: the batched decode linear (8 < R <= 32 rows of x, bf16) on the device-
+    quantised int8 form of w [N][K], once streaming the int8 codes and once their bf16 fragment copy.
+    Returns (y_q8, y_bf16, kparts, q [N][K] int8, scale [N]); the outputs are [R][N] (EPI_STORE /
+    EPI_F32), [R][N/2] (EPI_SWIGLU8) or the raw split-K slabs [kparts][R][N] (EPI_SLAB)."""
+    w = np.ascontiguousarray(w, np.float32)
+    N, K = w.shape
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+    R = x.shape[0]
+    No = N // 2 if epi == EPI_SWIGLU8 else N
+    cap = 8 if epi == EPI_SLAB else 1  # K parts at most (bsacc_plan)
+    yq = np.zeros((cap, R, No), np.float32)
+    yb = np.zeros((cap, R, No), np.float32)
+    kp = np.zeros(1, np.int32)
+    q = np.zeros((N, K), np.int8)
+    sc = np.zeros(N, np.float32)
+    native.check(native.lib().fm_op_batched_linear_q8(device, native.f32p(w), N, K, native.f32p(x), R, int(epi),
+                                                      native.f32p(yq), native.f32p(yb), native.i32p(kp),
+                                                      q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+                                                      native.f32p(sc)))
+    k = int(kp[0])
+    if epi == EPI_SLAB:
+        return yq.reshape(-1)[:k * R * No].reshape(k, R, No), yb.reshape(-1)[:k * R * No].reshape(k, R, No), k, q, sc
+    return yq[0], yb[0], k, q, sc

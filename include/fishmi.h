@@ -221,7 +221,9 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    "attn_cap" n, "attn_cap_batched" n, "fd_min" n, "fd_min_batched" n, "fd_nw" 4|8|16, "fd_min16" n,
    "fd_nw_batched" 4|8|16, "attn_wo" 0|1,
    "batched_fused_attn" 0|1; batched linears "bstream" 0|1, "bstream_acc" 0|1, "bstream_chain" 0|1, "bstream_kparts" n, "bstream_nw" n, "bs_dummy" 0|1|2, "bs_qkv_slab" 0|1,
-   "bs_xfirst" 0|1, "bs_vec_epi" 0|1,
+   "bs_xfirst" 0|1, "bs_vec_epi" 0|1, "bstream_q8" 0|1 (weight-only int8 bf16 models opened with more than
+   8 slots: 1, the default, the batched decode linears stream the int8 codes -- bit-identical
+   outputs, half the weight bytes -- 0 the bf16 copy of the codes; inert for every other model),
    "linear_u32" n, "linear_fill" n; prompt "prefill_attn", "prompt_gemm"; voice prefix copy "prefix_vec" 0|1; codec "conv2",
    "conv_splitk"; "sampler_fast" 0|1, "rmsnorm_block" 0|1, "debug_ts" n; batch-1 row-block GEMV
    "rowgemv" / "rowgemv_q4" bits, "row_copies" 0|1 (0: finalize keeps only the row-major weight
@@ -286,6 +288,15 @@ int fm_op_embed(int device, int precision, const int32_t* tok, int R, const floa
    and, when gs and K are multiples of 128 and y_q4 is given, on the streamed 4-bit codes (y_q4). */
 int fm_op_quant4(int device, const float* w, int N, int K, int gs, uint8_t* q, float* scale, float* zero,
                  float* w_deq, const float* x, int R, float* y_q4, float* y_bf16);
+/* Weight-only int8 on the batched decode linear (8 < R <= 32, bf16; fm_tune "bstream_q8"): quantises
+   the bf16-valued w [N][K] on the device with the int8 rule (quantize.py:22-52), packs the codes
+   both ways and runs the batched linear's plan once per form: y_q8 from the streamed int8 codes,
+   y_bf16 from their bf16 fragment copy.  x [R][K] bf16-valued.  epi 0 (store) / 3 (fp32): [R][N]
+   outputs round(round(acc) * scale); epi 7 (SwiGLU over w's 16-row tiles of 8 gate + 8 up rows):
+   [R][N/2]; epi 4 (split-K slabs): the raw fp32 slabs [kparts][R][N], no scale.  kparts: the plan's
+   K parts.  q_out [N][K] / scale_out [N] (optional): the codes and bf16 row scales it used. */
+int fm_op_batched_linear_q8(int device, const float* w, int N, int K, const float* x, int R, int epi,
+                            float* y_q8, float* y_bf16, int* kparts, int8_t* q_out, float* scale_out);
 /* the RoPE cos/sin table the library builds on the host (precompute_freqs_cis, llama.py:1003-1022):
    out [seq_len][head_dim/2][2], bf16-valued floats.  No device needed. */
 int fm_rope_table(int seq_len, int head_dim, float base, float* out);
