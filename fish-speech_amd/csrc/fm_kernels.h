@@ -324,6 +324,9 @@ struct FmTuning {
     int fw_cheap = 0;        // fattn_wo: FattnWoArgs::cheap
     int fw_prio = 0;         // fattn_wo: FattnWoArgs::prio
     int fattn_wo = 1;        // 1: batch-1 bf16 fast-model attention + wo as one launch (fm_rowgemv.hip fattn_wo_kernel)
+    int fattn_ilp = 1;       // 1: fattn_wo_kernel's attention chain without serial blocks: q / k prep chains side by side, score /
+                             // softmax / PV over a compile-time position count, the softmax one position per lane (bit-identical
+                             // to 0, the early-exit loops)
     int row_qkv_rp = 8;      // developer: rows per block of the bf16 row-block wqkv (4, 8 or 16)
     int rowgemv_q4 = 31;     // rowgemv's bits for weight-only int4 models (w1 || w3 too: int4 frame 3.06 -> 3.01 ms; bf16 4.07 -> 4.10, int8 3.11 -> 3.20 with it)
     int rowgemv = 123;       // batch-1 decode linears on the row-block GEMV (fm_rowgemv.hip): bit 0 wo / w2, bit 1 wqkv, bit 2 w1 || w3,
@@ -415,6 +418,7 @@ struct FattnWoArgs {
     int delay;                // wo blocks wait this many 10-ns ticks before their weight loads (fm_tune fw_delay)
     int cheap;                // 1: poll one word per 32-element group before the full read (fm_tune fw_cheap)
     int prio;                 // 1: attention waves at s_setprio 3 (fm_tune fw_prio)
+    int ilp;                  // 1: the attention chain without serial per-position blocks (fm_tune fattn_ilp)
     unsigned long long* dbg;  // developer records (launcher: fm_tune debug_ts)
     // fm_tune rowgemv bit 5 (the first fast layer at codebook > 0, bf16): the attention blocks take the raw q|k|v
     // row from qtab [qrows][at.ldqkv], row qidx[qcol] clamped into it, instead of at.qkv (no QKV launch ran)

@@ -1123,6 +1123,7 @@ template <typename T> struct Run {
             A.delay = fm_tuning().fw_delay;
             A.cheap = fm_tuning().fw_cheap;
             A.prio = fm_tuning().fw_prio;
+            A.ilp = fm_tuning().fattn_ilp;
             if (tab) {
                 A.qtab = (const bf16_t*)m->qkv0;
                 A.qidx = xidx;
@@ -2987,6 +2988,8 @@ int fm_tune(const char* key, int value) {
             t.fw_cheap = value != 0;
         } else if (k == "fattn_wo") {
             t.fattn_wo = value != 0;
+        } else if (k == "fattn_ilp") {
+            t.fattn_ilp = value != 0;
         } else if (k == "sampler_kth") {
             t.sampler_kth = value != 0;
         } else if (k == "row_qkv_rp") {

@@ -172,11 +172,15 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         }
     }
     asm volatile("" ::: "memory");
+    unsigned long long tsw = 0, tsx = 0;  // TX developer stamps: weights issued, x words current
+    unsigned polls = 0;
     if constexpr (TX) {
+        if (a.dbg) tsw = __builtin_amdgcn_s_memrealtime();
         // EPL tagged words per lane per chunk (sc1 loads, 16 B each), re-read until all are current
         const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xt, (short)0, a.K * 4, 0x00020000);
         u32x4_t xw[U][EPL / 4];
         for (unsigned it = 0;; ++it) {
+            polls = it + 1;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int jc = u < last ? u : last;
@@ -198,6 +202,7 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
             }
             __builtin_amdgcn_s_sleep(1);
         }
+        if (a.dbg) tsx = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -342,8 +347,13 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         }
     }
     if (a.dbg && threadIdx.x == 0) {
-        const unsigned long long t[7] = {ts0, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0};
-        dbg_record(a.dbg, TX ? 0xFFF8u : 0xFFFAu, (unsigned)blk, t);
+        if constexpr (TX) {  // (wave 0) start, weights issued, x words current, dot products done, end; aux = reads of x
+            const unsigned long long t[7] = {ts0, tsw, tsx, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0};
+            dbg_record(a.dbg, 0xFFF8u, polls, t);
+        } else {
+            const unsigned long long t[7] = {ts0, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0};
+            dbg_record(a.dbg, 0xFFFAu, (unsigned)blk, t);
+        }
     }
 }
 
@@ -438,13 +448,76 @@ void launch_rowgemv(hipStream_t s, const RowGemvArgs& a0, int kind) {
 constexpr int FW_MAXJ = 15;   // cached rows staged in LDS (cpos < 16)
 constexpr int FW_MAXHD = 128;
 
+// score -> softmax -> PV of one q head over positions 0 .. cpos, cpos < NJ <= FW_MAXJ + 1 (fm_tune
+// fattn_ilp).  NJ is a compile-time count, so the whole body is one basic block: every LDS read of a
+// phase is issued before its first use, and the NJ wave_sum chains are independent instructions the
+// scheduler interleaves.  Per position the arithmetic is that of the early-exit loops
+// in fattn_wo_kernel, in the same order (max, then den and the PV sums in ascending j); a position
+// j > cpos (NJ rounded up) has score -inf, weight exactly 0 and a zeroed V row, and adding its +0
+// changes neither den (> 0) nor an accumulator (never -0: it starts from +0), so the bits are the same.
+// Rows j >= cpos of the staged K / V hold no data; they are read (inside the array) and selected away.
+// Only the lane's first RoPE pair (x0, x1 = element [0] of the loops' pairs) takes part: hd <= FW_MAXHD
+// = 128, so the second pair (lane + 64 >= hd / 2) is masked to zero in every operand, its products
+// add +-0 to a partial sum that is never -0, and its output is not stored.
+template <int NJ>
+__device__ __forceinline__ void fw_attend(const bf16_t* Ks, const bf16_t* Vs, const int hd, const int half, const int cpos,
+                                          const int lane, const float scale, const float q0, const float q1, const float k0,
+                                          const float k1, const float v0, const float v1, float& o0, float& o1) {
+    static_assert(NJ >= 1 && NJ <= FW_MAXJ + 1 && FW_MAXHD <= 128, "positions 0 .. FW_MAXJ, one pair per lane");
+    constexpr int NC = NJ < FW_MAXJ ? NJ : FW_MAXJ;  // staged rows that can be live (j < cpos <= NJ - 1)
+    const bool in = lane < half;
+    const int pp = in ? lane : 0;
+    uint32_t kw[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) kw[j] = *reinterpret_cast<const uint32_t*>(Ks + j * hd + 2 * pp);
+    float sc[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const uint32_t w = kw[j < NC ? j : 0];
+        const bool cached = j < NC && j < cpos;  // (else the new k: position cpos, or a masked one)
+        const float a0 = cached ? (in ? lo16(w) : 0.f) : k0;
+        const float a1 = cached ? (in ? hi16(w) : 0.f) : k1;
+        float d = 0.f;
+        d += q0 * a0 + q1 * a1;
+        sc[j] = d;
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) sc[j] = wave_sum(sc[j]);
+    uint32_t vw[NC];
+#pragma unroll
+    for (int j = 0; j < NC; ++j) vw[j] = *reinterpret_cast<const uint32_t*>(Vs + j * hd + 2 * pp);
+    // The NJ sums are wave-uniform: lane j takes position j's, so the two roundings of the score, expf and the
+    // division run once for all positions (one per lane, lanes 0 .. NJ - 1 of the first 16-lane row) instead of
+    // once per position in every lane; den is still summed in ascending j, from the lanes' values
+    float s = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) s = lane == j ? sc[j] : s;
+    s = lane <= cpos ? bfround(bfround(s) * scale) : -INFINITY;
+    const float mx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(row_max16(s)), 0));  // (max: any order)
+    const float e = lane <= cpos ? expf(s - mx) : 0.f;
+    float den = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) den += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), j));
+    const float p = bfround(e / den);  // lane j: position j's probability (0 past cpos)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const float pj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), j));
+        const uint32_t w = vw[j < NC ? j : 0];
+        const bool cached = j < NC && j < cpos;
+        o0 += pj * (cached ? lo16(w) : (j == cpos ? v0 : 0.f));
+        o1 += pj * (cached ? hi16(w) : (j == cpos ? v1 : 0.f));
+    }
+}
+
 //
 // M (bf16 only): 0 the attention reads the raw q|k|v row the QKV launch left in at.qkv.
 // 1 (fm_tune rowgemv bit 5, the first layer at codebook > 0): that row is a pure function of the
 //   sampled code -- round(Wqkv rmsnorm(fast_embeddings[code]) + b) -- so it is read from the table
 //   of all codebook_size rows built at load time (A.qtab) and no QKV launch runs.  The index goes
-//   out first; the cached K / V rows (slot only) are issued before the table-row loads that wait
-//   on it.
+//   out first; the table-row loads wait on it.
+// In forms 0 and 1 the cached K / V rows go out ahead of the q|k|v row loads, two 16-B chunks per
+// thread into registers, unconditionally (a load under a branch drains vmcnt; a copy loop with a
+// runtime trip count, and a knob that selects one behind a branch, both measured slower).
 // 2 (bit 6, codebook 0): one position, so softmax = {1} and the output is 0 + 1 * v: no Q loads,
 //   no q prep, no score (the projection computed the K / V rows only).  The 0.f + stays: it is what
 //   turns a -0 of v into the +0 the full form stores.
@@ -490,7 +563,7 @@ void fattn_wo_kernel(FattnWoArgs A) {
             return reinterpret_cast<u32x4_t*>(kvs + (isv ? FW_MAXJ * FW_MAXHD : 0) + (isv ? i - nck : i) * 8);
         };
         u32x4_t kvr[2];
-        if constexpr (M == 1) {  // in registers, ahead of the table-row loads (no branch: nothing drains)
+        if constexpr (M != 2) {  // in registers, ahead of the q|k|v row loads (no branch: nothing drains)
 #pragma unroll
             for (int q = 0; q < 2; ++q) kvr[q] = *kv_src((int)threadIdx.x + 256 * q);
         }
@@ -513,12 +586,10 @@ void fattn_wo_kernel(FattnWoArgs A) {
             s_[u] = tab[2 * pp + 1];
             if (p >= half) q0[u] = q1[u] = k0[u] = k1[u] = v0[u] = v1[u] = 0.f;
         }
-        if constexpr (M == 1) {
+        if constexpr (M != 2) {
 #pragma unroll
             for (int q = 0; q < 2; ++q)
                 if ((int)threadIdx.x + 256 * q < 2 * nck) *kv_dst((int)threadIdx.x + 256 * q) = kvr[q];
-        } else if constexpr (M == 0) {
-            for (int i = threadIdx.x; i < 2 * nck; i += 256) *kv_dst(i) = *kv_src(i);
         }
         // qk-norm (fp32 incl. weight, one rounding) + RoPE (bf16 table, rounded): fm_attn_dev.h
         auto prep = [&](float (&x0)[2], float (&x1)[2], const float (&w0)[2], const float (&w1)[2]) {
@@ -542,8 +613,40 @@ void fattn_wo_kernel(FattnWoArgs A) {
                 x1[u] = y1;
             }
         };
-        if constexpr (M != 2) prep(q0, q1, qw0, qw1);
-        prep(k0, k1, kw0, kw1);
+        if (M != 2 && A.ilp) {
+            // the q and k chains are independent: both in one basic block (the same operations per chain as prep),
+            // so their wave_sum, rsqrt and rounding sequences interleave
+            if (at.qk_norm) {
+                float sq = 0.f, sk = 0.f;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    sq += q0[u] * q0[u] + q1[u] * q1[u];
+                    sk += k0[u] * k0[u] + k1[u] * k1[u];
+                }
+                sq = wave_sum(sq);
+                sk = wave_sum(sk);
+                const float rq = 1.0f / sqrtf(sq / (float)hd + at.eps), rk = 1.0f / sqrtf(sk / (float)hd + at.eps);
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    q0[u] = bfround((q0[u] * rq) * qw0[u]);
+                    q1[u] = bfround((q1[u] * rq) * qw1[u]);
+                    k0[u] = bfround((k0[u] * rk) * kw0[u]);
+                    k1[u] = bfround((k1[u] * rk) * kw1[u]);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const float a0 = bfround(q0[u] * c_[u] - q1[u] * s_[u]), a1 = bfround(q1[u] * c_[u] + q0[u] * s_[u]);
+                const float b0 = bfround(k0[u] * c_[u] - k1[u] * s_[u]), b1 = bfround(k1[u] * c_[u] + k0[u] * s_[u]);
+                q0[u] = a0;
+                q1[u] = a1;
+                k0[u] = b0;
+                k1[u] = b1;
+            }
+        } else {
+            if constexpr (M != 2) prep(q0, q1, qw0, qw1);
+            prep(k0, k1, kw0, kw1);
+        }
         if (wave == 0) {  // the group's new k / v of cpos into the fast cache
             bf16_t* kd = at.kc + base + (size_t)cpos * hd;
             bf16_t* vd = at.vc + base + (size_t)cpos * hd;
@@ -569,6 +672,23 @@ void fattn_wo_kernel(FattnWoArgs A) {
                 o0[u] = 0.f + v0[u];
                 o1[u] = 0.f + v1[u];
             }
+        } else if (A.ilp) {  // one basic block per position count (fw_attend); counts past 10 rounded up to 12 / 16
+#define FWA(n) fw_attend<n>(Ks, Vs, hd, half, cpos, lane, at.scale, q0[0], q1[0], k0[0], k1[0], v0[0], v1[0], o0[0], o1[0])
+            switch (cpos) {
+                case 0: FWA(1); break;
+                case 1: FWA(2); break;
+                case 2: FWA(3); break;
+                case 3: FWA(4); break;
+                case 4: FWA(5); break;
+                case 5: FWA(6); break;
+                case 6: FWA(7); break;
+                case 7: FWA(8); break;
+                case 8: FWA(9); break;
+                case 9: FWA(10); break;
+                case 10: case 11: FWA(12); break;
+                default: FWA(16); break;
+            }
+#undef FWA
         } else {
         float sc[FW_MAXJ + 1];
         float mx = -INFINITY;

@@ -236,7 +236,9 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    0, where the fast attention has one position and its output is v, the fast layers project K / V
    only and the attention reads no Q.  Bits 5 and 6 change no output bit (finite scores); they act
    on bf16 unquantised models, batch 1, and are inert elsewhere.  They apply to launches
-   recorded after the call (graphs captured earlier keep theirs). */
+   recorded after the call (graphs captured earlier keep theirs).  "fattn_ilp" 0|1 (default 1: the
+   fused fast attention + wo launch runs its q / k preparation and score / softmax / PV over a
+   compile-time position count in one basic block) changes no output bit either. */
 int fm_tune(const char* key, int value);
 /* developer hook ("debug_ts" armed): per-block records of 8 words {tag = N<<32 | blockIdx.y<<16 |
    blockIdx.x, start, staged, streamed, end, 3 kernel-specific} of the decode GEMVs,

@@ -1,9 +1,10 @@
 """Timeline of the fused fast attention + wo launch (fm_rowgemv.hip fattn_wo_kernel) from its
-debug_ts records: attention waves (0xFFF9: start, K/V staged, stored) and sampled wo blocks
-(0xFFF8: start, weights issued, cheap poll done, full x read, end; aux = polls), per launch,
-relative to the launch's first block start (us).  An optional argument sets fm_tune rowgemv first
-(27: the QKV launches of today; 123: first-layer QKV table + K / V only at codebook 0); the first
-fast layer's launches at codebooks >= 1 -- the ones that read the table -- are also listed apart."""
+debug_ts records: attention waves (0xFFF9: start, K/V staged, stored) and the wo blocks' first waves
+(0xFFF8: start, weights issued, x words current, dot products done, end; aux = reads of x), per
+launch, relative to the launch's first block start (us).  Optional arguments: fm_tune rowgemv (27:
+a QKV launch per layer; 123: first-layer QKV table + K / V only at codebook 0), then fm_tune
+fattn_ilp (0 | 1); the first fast layer's launches at codebooks >= 1 -- the ones
+that read the table -- are also listed apart."""
 import os
 import sys
 
@@ -18,8 +19,9 @@ from fishmi.llm import DualARModel  # noqa: E402
 cfg = DualARConfig._from_fish_qwen3_omni(S2_PRO_CONFIG)
 cfg.im_end_id = S2_PRO_IM_END_ID
 cfg.max_seq_len = 1024
-if len(sys.argv) > 1:
-    native.tune("rowgemv", int(sys.argv[1]))
+for knob, arg in zip(("rowgemv", "fattn_ilp"), sys.argv[1:]):
+    native.tune(knob, int(arg))
+    print(f"fm_tune {knob} {int(arg)}")
 m = DualARModel.synthetic(cfg, seed=0, log2_half=5, device=0, precision="bf16", max_slots=1)
 p = np.zeros((cfg.num_codebooks + 1, 64), np.int32)
 p[0] = np.random.default_rng(1).integers(16, cfg.semantic_begin_id, 64)
@@ -44,11 +46,12 @@ for li, g in enumerate(np.split(att, cut)):
     kept.append(li)
     T = lambda x: (x - t0) / 100.0
     rows.append([T(g[:, 2].max()), T(g[:, 3].max()), T(w[:, 1].max()), T(w[:, 2]).mean(), T(w[:, 3]).mean(),
-                 T(w[:, 4]).mean(), T(w[:, 5]).mean(), T(w[:, 5]).max(), np.mean(w[:, 0] & 0xFFFFFFFF)])
+                 T(w[:, 3]).max(), T(w[:, 4]).mean(), T(w[:, 5]).mean(), T(w[:, 5]).max(),
+                 np.mean(w[:, 0] & 0xFFFFFFFF)])
 r = np.array(rows)
 print(f"{len(r)} launches; means (us from the launch's first block start):")
-names = ["att staged(max)", "att stored(max)", "wo last start", "wo weights issued", "wo poll ok",
-         "wo x read", "wo end(mean)", "wo end(max)", "polls"]
+names = ["att staged(max)", "att stored(max)", "wo last start", "wo weights issued", "wo x current",
+         "wo x current(max)", "wo dots done", "wo end(mean)", "wo end(max)", "wo reads of x"]
 for n, v in zip(names, r.mean(axis=0)):
     print(f"  {n:18s} {v:7.2f}")
 # a frame's fused launches in order: codebook 0's layers but the last (K / V only, not fused), then every
