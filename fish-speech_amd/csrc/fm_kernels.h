@@ -2,6 +2,7 @@
 #pragma once
 #include <algorithm>
 #include "fm_common.h"
+#include "fm_tune_table.h"
 
 enum { EPI_STORE = 0, EPI_RESID = 1, EPI_SWIGLU = 2, EPI_F32 = 3 };
 
@@ -171,7 +172,7 @@ enum { PRO_PLAIN = 0, PRO_NORM = 1, PRO_PRENORM = 3, PRO_FATT = 4 };
 // the Wo GEMV needs no separate attention launch; blockIdx.x == 0 writes the new k / v of cpos.
 enum { EPI_SLAB = 4, EPI_SLABFIN = 5, EPI_SWIGLU8 = 7 };
 // EPI_SWIGLU8: W is the row-interleaved W1||W3 (each 16-row tile = 8 gate rows then the same 8 up
-// rows, see pack_w13 in fm_llm.cpp); a tile yields 8 SwiGLU outputs, N = 2 * intermediate.
+// rows, see pack_w13 in fm_llm_weights.cpp); a tile yields 8 SwiGLU outputs, N = 2 * intermediate.
 
 template <typename T> struct FastFusedArgs {
     const T* qkv;
@@ -249,94 +250,11 @@ template <typename T> struct GemvArgs {
     int pf_S, pf_nkv, pf_hd;
     int dummy_tail;  // ring slots past the wave's run load one fixed fragment (else the run's last)
 };
-// developer knobs for the decode GEMV (fm_tune): weight load policy and split-K policy
+// developer knobs (fm_tune): one int field per entry of fm_tune_table.h, in its order
 struct FmTuning {
-    int gemv_nt = 1;         // 1: non-temporal weight loads (each weight byte is read once a frame)
-    int gemv_u = 8;          // weight fragments in flight per wave (2, 4 or 8)
-    int gemv_wpb = 4;        // waves per block (4 or 8) sharing one 16-row tile
-    int sampler_kth = 1;     // sample_fast_kernel: the K-th lane maximum as the wave threshold when its candidates fit (else the radix search)
-    int sampler_fast = 1;    // 1: two-stage register top-K sampler, 0: LDS radix-select sampler
-    int attn_cap = 32;       // slow decode attention rows per block cap (0: the LDS-budget maximum)
-    int attn_wo = 0;         // 1: fast-model attention recomputed in the Wo GEMV's prologue (PRO_FATT, R == 1; measured 0.37 ms/frame slower)
-    int ksb_blocks = 512;    // split K until the grid has at least this many blocks
-    int batched_fused_attn = 1;  // batched decode (one row per slot): fused QK-norm/RoPE/KV-write attention kernels
-    int attn_cap_batched = 128;  // rows per block of the batched decode attention (one row per slot)
-    int linear_u32 = 4;      // linear_kernel weight fragments in flight per wave at 16 < R <= 32 (4 or 8)
-    int linear_fill = 0;     // batched linear_kernel: split K until this many blocks (0: never; measured slower)
-    int attn3 = 1;           // 1: slow decode attention on attn_dec3_kernel, 0: attn_decode2_kernel
-    int attn_fd = 1;         // 1: slow decode attention on attn_fd_kernel (flash-decode splits) where eligible
-    int fd_min = 32;         // attn_fd: minimum positions per split at R <= 8
-    int fd_min_batched = 512;  // attn_fd: minimum positions per split at R > 8 (B=32: one split below 512)
-    int fd_nw = 8;           // attn_fd at R <= 8: waves per block (4, 8 or 16) ...
-    int fin_ksb = 0;         // batch-1 wo / w2 (EPI_SLABFIN) split-K factor (0: whole K whenever the x slice fits LDS)
-    int fd_nw_batched = 4;   // attn_fd at R > 8: waves per block (4, 8 or 16)
-    int fd_min16 = 256;      // ... and splits of at least this many positions (8 or 16 waves; below it
-                             // one block per kv head, no cross-block combine)
-    int prefill_attn = 1;    // 1: prompt-chunk attention on attn_prefill_kernel (bf16, head_dim 128, flash form)
-    int prompt_gemm = 1;     // 1: prompt-chunk linears (R > 32) on the codec's LDS-tiled GEMM kernels
-    int prompt_skinny = 1;      // prompt linears at 32 < R <= 64 rows (bf16) on prompt_skinny_kernel ...
-    int prompt_skinny_blocks = 256;  // ... with K sliced until its 64-row blocks number >= this
-    int prompt_unroll = 1;      // skinny prompt GEMM: the fully unrolled form (5 / 10 / 20-chunk slices)
-    int prompt_qkv_slab = 1;    // skinny QKV: slabs summed by qk_rope_cache_kernel (no epilogue launch)
-    int prompt_fin = 1;         // skinny wo / w2: slabs finished by finalize_norm with the next RMSNorm
-    int prompt_swiglu = 1;      // skinny w1 || w3: the SwiGLU in its split-K epilogue (no separate launch)
-    int prompt_ks_tiles = 384;  // prompt GEMM: split K until ceil(R/128) ceil(N/128) ks reaches this ...
-    int prompt_ks_max = 8;      // ... or ks this (fp32 slabs + the conv split-K epilogue)
-    int conv2 = 1;           // 1: codec GEMMs on the LDS-staged conv_gemm2_kernel, 0: conv_gemm_kernel
-    int conv_splitk = 1;     // 1: small-grid codec GEMMs split K into fp32 slabs + a reduce/epilogue kernel
-    int resunit_cfg = 1;     // resunit_kernel tile at 192 / 96 channels: 0 (BM 128 / 256, 8 time tiles per wave), 1 (BM 64 / 128, 4 tiles), 2 (128 / 128)
-    int resunit_enc = 1;     // 1: the encoder's units (64 / 128 / 256 / 512 channels) fused as well
-    int resunit_384 = 1;     // 1: the 384-channel stage's units fused too (BM 64, 8 waves)
-    int codec_norm = 1;      // 1: the codec transformer's RMSNorms in the wo / w2 split-K epilogues (no rmsnorm launch)
-    int codec_rope = 1;      // 1: the codec transformer's RoPE in the wqkv split-K epilogue (no rope_qk launch)
-    int codec_swiglu = 1;    // 1: codec FeedForward W1 | W3 as one split-K GEMM with the SwiGLU epilogue
-    int codec_fuse = 1;      // 1: decoder ResidualUnits at 96 / 192 / 384 channels as one resunit_kernel launch (k7 + k1)
-    int bstream = 1;         // 1: batched decode linears (8 < R <= 32) on bstream_kernel (fm_bstream.hip)
-    int bstream_kparts = 0;  // bstream EPI_SLAB K parts (0: by K)
-    int bstream_nw = 0;      // bstream waves per block (0: 16 whole-K, 8 split-K)
-    // ring slots past a wave's run (tail of the decode GEMV ring, bsacc tiles / steps a block does
-    // not own): 0 re-load the run's last fragment, 1 one fixed fragment, 2 a fixed fragment per
-    // (block, wave) over 256 of them.  B=1 frame 4.447 / 4.47 / 4.398 ms, B=32 6.51 / 6.44 / 6.42 ms
-    int bs_dummy = 2;
-    int gemv_dummy = 2;
-    int bs_qkv_slab = 1;     // batched frames: QKV as K-part slabs summed by the attention (balanced
-                             // grid: 384 tiles x 2 K parts over 256 CUs; B=32 frame 6.48 -> 6.33 ms)
-    int fast_tail = 1;       // 1: codebook 0's fast pass stops its last layer after the K / V cache write (its output is discarded)
-    int fkv_prefetch = 0;    // 1: the batch-1 fast-model QKV GEMV pulls the fast attention's cached rows into L2 too
-    int kv_prefetch = 1;     // 1: the batch-1 QKV GEMV pulls the next attention's K / V rows into L2
-    int bstream_chain = 0;   // 1: bsacc SLABFIN / PRENORM chain instead of finalize_norm launches (measured 6.31 -> 6.75 ms per B=32 frame)
-    int bstream_acc = 1;     // 1: bsacc_kernel (per-tile register accumulators, one reduction at the end, balanced K parts); 0: bstream_kernel
-    int rmsnorm_block = 0;   // 1: block-per-row RMSNorm (the pre-vectorisation kernel), 0: wave-per-row when shapes allow
-    int ksb_balance = 0;     // 1: prefer grids that are whole multiples of 256 blocks (one per CU)
-    int chain_max = 4;       // gemv_chain: GEMVs per launch at most (2..4)
-    int chain_sleep = 4;     // gemv_chain: s_sleep argument between a waiting block's polls (1, 4 or 16)
-    int gemv_chain = 0;      // 1: batch-1 decode runs wo -> w1||w3 -> w2 -> next qkv as one launch (gemv_chain_kernel)
-    int bs_xfirst = 1;       // bsacc: X operands before the weight ring (B=32 frame 6.48 -> 6.36 ms)
-    int bs_vec_epi = 1;      // bsacc: 4-row epilogue items (bit-identical to the scalar epilogue; B=32 frame 6.31 -> 6.18 ms)
-    int bsacc_kparts = 0;    // developer: force the K parts of the batched split-K (slab) linears (0: bsacc_plan's pick)
-    int q_u = 4;             // int8 / int4 decode GEMV: ring units in flight per wave (2, 4, 8, 16; int8 frame 3.79 -> 3.59 ms at 8 -> 4)
-    int fin8 = 1;            // finalize_norm: all eight K parts' slab loads in one round trip (0: two batches of four)
-    int fin_split = 0;       // batched finalize_norm: each row over this many blocks (0 / 1: one block per row)
-    int bstream_q8 = 1;      // weight-only int8, 8 < R <= 32: 1 bsacc_kernel streams the int8 codes, 0 their bf16 fragment copy
-                             // (bit-identical; int8 B=32 frame 6.441 -> 5.761 ms, the bf16 model's 6.184; profiles/b32_int8.md)
-    int int4_stream = 1;     // weight-only int4: 1 the batch <= 8 GEMVs stream the 4-bit codes, 0 the dequantised bf16 copy
-    int fw_delay = 0;        // fattn_wo: FattnWoArgs::delay
-    int fw_cheap = 0;        // fattn_wo: FattnWoArgs::cheap
-    int fw_prio = 0;         // fattn_wo: FattnWoArgs::prio
-    int fattn_wo = 1;        // 1: batch-1 bf16 fast-model attention + wo as one launch (fm_rowgemv.hip fattn_wo_kernel)
-    int fattn_ilp = 1;       // 1: fattn_wo_kernel's attention chain without serial blocks: q / k prep chains side by side, score /
-                             // softmax / PV over a compile-time position count, the softmax one position per lane (bit-identical
-                             // to 0, the early-exit loops)
-    int row_qkv_rp = 8;      // developer: rows per block of the bf16 row-block wqkv (4, 8 or 16)
-    int rowgemv_q4 = 31;     // rowgemv's bits for weight-only int4 models (w1 || w3 too: int4 frame 3.06 -> 3.01 ms; bf16 4.07 -> 4.10, int8 3.11 -> 3.20 with it)
-    int rowgemv = 123;       // batch-1 decode linears on the row-block GEMV (fm_rowgemv.hip): bit 0 wo / w2, bit 1 wqkv, bit 2 w1 || w3,
-                             // bit 3 the codebook head, bit 4 the first layers' wqkv (0: 16-row MFMA tiles; 3 -> 27: 4.066 -> 4.032 ms);
-                             // bit 5: the first fast layer's QKV at codebooks >= 1 read from a table of its codebook_size possible
-                             // rows (no launch); bit 6: at codebook 0 the fast layers compute K / V only (one position: attention = v)
-    int row_copies = 1;      // 1: fm_llm_finalize keeps a row-major copy of every linear the row-block GEMV can take, so any
-                             // rowgemv bits work later (bf16 S2-Pro: ~3.7 GB beside the packed tiles); 0: only the copies the
-                             // rowgemv / rowgemv_q4 bits in force at finalize select (w1 || w3 bf16 / int8: ~3.6 GB saved)
-    int prefix_vec = 1;      // voice prefix copy (fm_prefix.hip): 1 16-byte accesses where the runs allow, 0 the scalar path
+#define FM_KNOB(name, def, ...) int name = def;
+#include "fm_tune_table.h"
+#undef FM_KNOB
     unsigned long long* dbg = nullptr;  // device buffer of per-block phase timestamps (debug_ts)
     unsigned epoch = 0;      // bumped by every fm_tune call but debug_ts: what was derived under older knobs (the QKV table) is rebuilt
 };

@@ -1,0 +1,1462 @@
+// fm_llm_frame.cpp -- the launches of the Dual-AR forward: Run<T> (instantiated here only) and the
+// non-template entry points the C API reaches it through.
+#include <math.h>
+
+#include <algorithm>
+#include <array>
+
+#include "fm_codec.h"
+#include "fm_llm_model.h"
+
+// ------------------------------------------------------------------------------------------
+// kernels on a stack (slow or fast), templated on storage T
+// ------------------------------------------------------------------------------------------
+template <typename T> struct Run {
+    typedef T type_t;
+    fm_llm* m;
+    hipStream_t s;
+    int64_t E;  // element size
+    // ---- the mutable state of a pass (everything else a launch needs comes from its arguments and m) ----
+    // rows_distinct_slots: the rows of slow_layers are one per slot (a batched decode frame), not one prompt's
+    // bs_frame: inside a batched decode frame or first frame: 8 < R <= 32 linears may run on bsacc / bstream
+    // x_ss: bstream_chain only: the stack's x rows are final and m->ssX holds their tile sums
+    // pend: a w2 whose fp32 K-part slabs are not yet summed into the residual rows; the next block's
+    //       attention_norm launch (bs_norm_in) or flush() finalises it
+    // segs: (first row, rows) of each prompt inside the current batched-prefill chunk (attention per prompt)
+    bool rows_distinct_slots = false, bs_frame = false, x_ss = false;
+    struct BsPending {
+        bool on = false;
+        const float* slab = nullptr;
+        int kparts = 0, d = 0, R = 0;
+        void* res = nullptr;  // residual rows (h) ...
+        void* out = nullptr;  // ... + round(sum of slabs) -> out (x)
+        const void* sc = nullptr;  // weight-only int8 row scales of w2
+    } pend;
+    std::vector<std::array<int, 2>> segs;
+    void set_pending(const float* slab, int kparts, int d, int R, void* res, void* out, const void* sc) {
+        pend = BsPending{true, slab, kparts, d, R, res, out, sc};
+    }
+    explicit Run(fm_llm* mm) : m(mm), s(mm->stream), E(sizeof(T)) {}
+
+    // Prompt chunks (R > 32 rows): a linear is a GEMM, not a weight stream, so it runs on the codec's
+    // LDS-tiled implicit-GEMM kernels as a one-tap conv (conv_gemm2_kernel: 128-row x 96-128-column
+    // tiles, or the 64 x 64 register tiles with split-K when the grid would not fill the chip).
+    // The packed weight layout is the same; epilogues: round(acc + bias) and round(res + round(acc)).
+    bool prompt_gemm(const void* W, const void* W2, const void* bias, const void* X, int ldx, int R, int N, int K,
+                     void* Y, int ldy, const void* res, int ldr, int epi, const char* cls) {
+        if (R <= 32 || W2 || m->qinfo(W) || !fm_tuning().prompt_gemm ||
+            (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU8) || N % 16 || K % 32 || N < 96 ||
+            (epi == EPI_SWIGLU8 && (bias || N % 16)))
+            return false;
+        ConvArgs<T> c{};
+        c.x = (const T*)X;
+        c.ldx = ldx;
+        c.Ci = K;
+        c.Lq = R;
+        c.Lx = R;
+        c.w = (const T*)W;
+        c.Co = N;
+        c.ntaps = 1;
+        c.stride = 1;
+        c.nphase = 1;
+        c.bias = (const T*)bias;
+        c.res = epi == EPI_RESID ? (const T*)res : nullptr;
+        c.ldr = ldr;
+        c.out = Y;
+        c.ldo = ldy;
+        c.flags = CE_STORE | (bias ? CE_BIAS : 0) | (epi == EPI_RESID ? CE_RES : 0) |
+                  (epi == EPI_SWIGLU8 ? CE_SWIGLU8 : 0);  // SWIGLU8: Y = act [R][N/2], ldy = N/2
+        hipStream_t st = s;
+        const int64_t bytes = (int64_t)N * K * E + (int64_t)R * K * E + (int64_t)R * N * E;
+        const double flops = 2.0 * R * N * K;
+        if constexpr (sizeof(T) == 2) {
+            // R <= 64: one weight pass for all rows (fm_prompt.hip), K slices finished by the conv
+            // split-K epilogue (the same roundings as below)
+            auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+            const int ks = prompt_skinny_ks(N, K, fm_tuning().prompt_skinny_blocks);
+            if (fm_tuning().prompt_skinny && ks > 0 && R <= 64 && ldx % 8 == 0 && al16(X) && al16(Y) && ldy % 8 == 0 &&
+                (!c.res || (al16(c.res) && ldr % 8 == 0)) && (long long)ks * R * N <= m->skpart_cap) {
+                c.ksplit = ks;
+                c.slab = m->skpart;
+                c.slab_cap = (size_t)m->skpart_cap;
+                PromptSkinnyArgs p{(const bf16_t*)W, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+                const bool direct = ks == 1 && epi == EPI_SWIGLU8;  // the kernel stores act itself
+                if (direct) {
+                    p.act = (bf16_t*)Y;
+                    p.lda = ldy;
+                }
+                auto go = [st, c, p, ks, direct] {
+                    launch_prompt_skinny(st, p, ks);
+                    if (!direct) launch_conv_epi<T>(st, c);
+                };
+                launch(cls, bytes, flops, go);
+                return true;
+            }
+        }
+        if (epi == EPI_SWIGLU8) return false;  // the conv GEMMs' own epilogues have no interleaved SwiGLU
+        // split K (fp32 slabs + the conv split-K epilogue) until the 128 x 128 tiles number >=
+        // prompt_ks_tiles (default 384)
+        const long long t128 = (long long)FM_CEIL(R, 128) * FM_CEIL(N, 128);
+        int ks = 1;
+        while (t128 * ks < fm_tuning().prompt_ks_tiles && ks < fm_tuning().prompt_ks_max && K / 32 >= 8 * ks * 2)
+            ks *= 2;
+        c.ksplit = ks;
+        c.slab = m->skpart;
+        c.slab_cap = (size_t)m->skpart_cap;
+        auto go = [st, c] { launch_conv_gemm<T>(st, c); };
+        launch(cls, bytes, flops, go);
+        return true;
+    }
+    // A prompt chunk's wo / w2 (32 < R <= 64, bf16) as raw K-slice partials in m->skpart ([ks][R][N], the
+    // finalize_norm slab layout): the residual add, the bias and the next RMSNorm then run in one
+    // finalize_norm launch instead of the split-K epilogue + an RMSNorm launch.  false: not eligible.
+    bool prompt_slab(const void* W, const void* X, int ldx, int R, int N, int K, int* ks_out) {
+        if constexpr (sizeof(T) != 2) {
+            return false;
+        } else {
+            if (!fm_tuning().prompt_fin || !fm_tuning().prompt_skinny || !fm_tuning().prompt_gemm || R <= 32 ||
+                R > 64 || m->qinfo(W) || N % 16 || K % 32 || ldx % 8 || ((uintptr_t)X & 15))
+                return false;
+            const int ks = prompt_skinny_ks(N, K, fm_tuning().prompt_skinny_blocks);
+            if (ks <= 0 || (long long)ks * R * N > m->skpart_cap) return false;
+            const PromptSkinnyArgs p{(const bf16_t*)W, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+            hipStream_t st = s;
+            auto go = [st, p, ks] { launch_prompt_skinny(st, p, ks); };
+            const int64_t bytes = (int64_t)N * K * E + (int64_t)R * K * E + (int64_t)ks * R * N * 4;
+            launch("linear", bytes, 2.0 * R * N * K, go);
+            *ks_out = ks;
+            return true;
+        }
+    }
+    void linear(const void* W, const void* W2, const void* bias, const void* X, int ldx, int R, int N,
+                int K, void* Y, int ldy, const void* res, int ldr, float* Yf, int epi, const char* cls) {
+        if (bs_use(R, false) && !W2 && !res && (epi == EPI_F32 || epi == EPI_STORE) &&
+            bs_linear(W, bias, X, ldx, R, N, K, Y, ldy, Yf, epi))
+            return;  // heads / fast_project_in of a batched frame
+        if (prompt_gemm(W, W2, bias, X, ldx, R, N, K, Y, ldy, res, ldr, epi, cls)) return;
+        LinearArgs<T> a{(const T*)W, (const T*)W2, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y,
+                        ldy, (const T*)res, ldr, Yf};
+        if (const auto* q = m->qinfo(W)) a.wscale = (const T*)q->scale;
+        if (R > GEMV_MAX_ROWS && R <= 64) {  // batched decode: split-K over the idle CUs
+            FMCHECK(m->skpart_cap >= (long long)LINEAR_PART_CAP, "split-K partial buffer too small");
+            a.part = m->skpart;
+            a.tickets = m->tickets;
+        }
+        const int64_t wbytes = (int64_t)N * K * E * (epi == EPI_SWIGLU ? 2 : 1);
+        const int64_t bytes = wbytes + (int64_t)R * K * E + (int64_t)R * N * (epi == EPI_F32 ? 4 : E);
+        const double flops = 2.0 * R * N * K * (epi == EPI_SWIGLU ? 2 : 1);
+        hipStream_t st = s;
+        auto go = [st, a, epi] { launch_linear<T>(st, a, epi); };
+        launch(cls, bytes, flops, go);
+    }
+
+    // TransformerBlock.forward (llama.py:838-843) on R rows; x is updated in place.
+    // ---- batched decode (8 < R <= 32 rows, one per slot) on bstream_kernel (fm_bstream.hip) ----
+    // Wo and W2 leave fp32 K-part slabs; finalize_norm_kernel sums them into the residual row and
+    // applies the next RMSNorm, so W2's finalise is deferred to the next block's start (or flush()).
+    // slow-model decode attention: attn_dec3 (registers, 64 positions per block) for the batched
+    // frame (B=32: 35.7 vs 38.1 us per layer), attn_decode2 (LDS tiles, 32-row blocks) at B <= 8,
+    // where it is the faster of the two (B=1 frame 4.28 vs 4.52 ms)
+    void attn_slow(const AttnDecArgs<T>& aa, int R) { attn_slow_on(s, aa, R); }
+    static void attn_slow_on(hipStream_t s, const AttnDecArgs<T>& aa, int R) {
+        if (fm_tuning().attn_fd && attn_fd_ok(aa.hd, aa.nh / aa.nkv)) {
+            AttnDecArgs<T> b = aa;
+            b.cap = std::max(16, R > GEMV_MAX_ROWS ? fm_tuning().fd_min_batched : fm_tuning().fd_min);
+            if (R <= GEMV_MAX_ROWS && fm_tuning().fd_nw > 4) {
+                b.nwb = fm_tuning().fd_nw;
+                b.cap = std::max(16, fm_tuning().fd_min16);
+            } else if (R > GEMV_MAX_ROWS && fm_tuning().fd_nw_batched > 4) {
+                b.nwb = fm_tuning().fd_nw_batched;
+            }
+            launch_attn_fd<T>(s, b, R);
+        } else if (fm_tuning().attn3 && R > GEMV_MAX_ROWS && aa.hd % 32 == 0 && aa.hd <= 128 && aa.nh / aa.nkv <= 6)
+            launch_attn_decode3<T>(s, aa, R);
+        else
+            launch_attn_decode2<T>(s, aa, R);
+    }
+    bool bs_use(int R, bool) const {
+        return fm_tuning().bstream && bs_frame && R > GEMV_MAX_ROWS && R <= 32 && m->bsA;
+    }
+    // one bstream linear; returns false (nothing launched) when the shape is not eligible
+    // bsacc_kernel's fused prologue / epilogue operands (the batched SLABFIN / PRENORM chain)
+    struct BsExtra {
+        int pro = PRO_PLAIN;
+        const float* ss_in = nullptr;
+        const void* nw = nullptr;
+        const void* res = nullptr;
+        void* res_out = nullptr;
+        float* ss_out = nullptr;
+    };
+    bool bs_linear(const void* W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
+                   float* Yf, int epi, int* kparts_out = nullptr, const BsExtra* ex = nullptr) {
+        const BstreamPlan p = bstream_plan(N, K, R, epi, E);
+        if (!p.ok || ((epi == EPI_SLABFIN || (ex && ex->pro == PRO_PRENORM)) && !p.acc)) return false;
+        BstreamArgs<T> a{(const T*)W, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y, ldy, Yf};
+        const auto* q = m->qinfo(W);
+        if (q) a.wscale = (const T*)q->scale;
+        // weight-only int8 (fm_tune bstream_q8): the accumulating kernel streams the codes where it has the form
+        if (q && q->q8s && fm_tuning().bstream_q8 && bsacc_q8_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E)) a.Wq8 = q->q8s;
+        a.dbg = fm_tuning().dbg;
+        if (ex) {
+            a.pro = ex->pro;
+            a.ss_in = ex->ss_in;
+            a.nw = (const T*)ex->nw;
+            a.eps = m->c.norm_eps;
+            a.res = (const T*)ex->res;
+            a.ldr = N;
+            a.res_out = (T*)ex->res_out;
+            a.ldro = N;
+            a.ss_out = ex->ss_out;
+            a.tickets = m->tickets;
+        }
+        const int64_t wbytes = a.Wq8 ? (int64_t)N * K + (int64_t)N * 2 : (int64_t)N * K * E;  // codes + row scales
+        const int64_t bytes = wbytes + (int64_t)R * K * E +
+                              (int64_t)R * N * (epi == EPI_SLAB ? 4 * p.kparts : (epi == EPI_F32 ? 4 : E));
+        const double flops = 2.0 * R * N * K;
+        hipStream_t st = s;
+        auto go = [st, a, epi, p] { FMCHECK(launch_bstream<T>(st, a, epi, p), "bstream: no kernel for the plan"); };
+        launch("linear", bytes, flops, go);
+        if (kparts_out) *kparts_out = p.kparts;
+        return true;
+    }
+    const void* wscale(const void* W) const {
+        const auto* q = m->qinfo(W);
+        return q ? q->scale : nullptr;
+    }
+    // The batched bf16 chain on bsacc_kernel (fm_tune bstream_chain): Wo and W2 finalise the residual
+    // rows and their tile sums of squares (EPI_SLABFIN), QKV and W13 normalise in their prologue
+    // (PRO_PRENORM) -- no finalize_norm launches.  Measured slower (B=32 frame 6.31 -> 6.75 ms): the
+    // prologue's X rows and tile sums arrive ~7 us into the launch (scripts/b32_ts.py "xready"),
+    // 3-4 us later than a plain prologue's, and the last K part's finalise adds 3-5 us to Wo / W2.
+    bool bs_chain(const StackDims& d, int R) const {
+        if (!fm_tuning().bstream_chain || E != 2 || R > 32) return false;
+        auto ok = [&](int N, int K, int epi) { return bstream_plan(N, K, R, epi, E).acc; };
+        return ok(d.nqkv(), d.dim, EPI_STORE) && ok(d.dim, d.nq(), EPI_SLABFIN) && ok(2 * d.inter, d.dim, EPI_SWIGLU8) &&
+               ok(d.dim, d.inter, EPI_SLABFIN);
+    }
+    void finalize_norm(const float* slab, int kparts, const void* bias, const void* res, void* out, const void* nw,
+                       void* xn, int d, int R, const void* sc) {
+        FinalizeArgs<T> f{slab, kparts, d, (const T*)bias, (const T*)res, d, (T*)out, d, (const T*)nw,
+                          m->c.norm_eps, (T*)xn, d, d, R, (const T*)sc};
+        if (fm_tuning().fin_split > 1 && m->fin_cnt) {
+            f.ch = fm_tuning().fin_split;
+            f.cnt = m->fin_cnt;
+            f.ss_part = m->fin_ss;
+            f.err = m->chain_err;
+        }
+        run_("norm", 0, 0, [&] { launch_finalize_norm<T>(s, f); });
+    }
+    // finalise a W2 left pending by the last block of a stack (no norm)
+    void flush() {
+        if (!pend.on) return;
+        pend.on = false;
+        finalize_norm(pend.slab, pend.kparts, nullptr, pend.res, pend.out, nullptr, nullptr, pend.d, pend.R, pend.sc);
+    }
+    // the stack's input rows x are final unless a previous block left W2 pending on them
+    void bs_norm_in(const StackDims& d, const LayerW& L, int R, void* xb, void* xnb) {
+        if (pend.on) {
+            FMCHECK(pend.out == xb && pend.R == R && pend.d == d.dim, "bstream: pending residual mismatch");
+            pend.on = false;
+            finalize_norm(pend.slab, pend.kparts, nullptr, pend.res, xb, L.an, xnb, d.dim, R, pend.sc);
+        } else {
+            run_("norm", 0, 0, [&] {
+                launch_rmsnorm<T>(s, (const T*)xb, d.dim, (const T*)L.an, d.dim, m->c.norm_eps, (T*)xnb, d.dim, R);
+            });
+        }
+    }
+
+    // One layer of block(): its arguments and its regime.  bs: a batched frame's rows on the bsacc / bstream
+    // linears (chain: their SLABFIN / PRENORM variant, fm_tune bstream_chain); else a prompt chunk (the skinny
+    // GEMM's slabs where eligible) or the plain linear() fallback -- each stage tries them in that order.
+    struct Blk {
+        const StackDims& d;
+        const LayerW& L;
+        int R;
+        const int *rslot, *rpos;
+        int fixed_pos;
+        bool is_fast;
+        void *kc, *vc;
+        size_t sstride, loff;
+        int Sc;
+        const float* rope;
+        void *xb, *hb, *xnb;
+        bool bs, chain;
+        const float* qslab = nullptr;  // the QKV projection's K-part slabs (bs_qkv_slab, prompt_qkv_slab) instead of m->qkv
+        int qslab_kp = 1;
+    };
+    // QKV (+ attention_norm, + the finalise of a w2 the previous block left pending)
+    void blk_qkv(Blk& b) {
+        const StackDims& d = b.d;
+        const LayerW& L = b.L;
+        const int R = b.R;
+        if (b.chain && x_ss) {  // QKV normalises x itself (attention_norm from the tile sums)
+            BsExtra e;
+            e.pro = PRO_PRENORM;
+            e.ss_in = m->ssX;
+            e.nw = L.an;
+            FMCHECK(bs_linear(L.wqkv, L.bqkv, b.xb, d.dim, R, d.nqkv(), d.dim, m->qkv, d.nqkv(), nullptr, EPI_STORE,
+                              nullptr, &e),
+                    "bsacc: no PRENORM QKV plan");
+            return;
+        }
+        bs_norm_in(d, L, R, b.xb, b.xnb);  // (a prompt chunk's pending w2 (prompt_slab) is finalised with this norm too)
+        int kp = 0;
+        if (b.bs) {
+            // fm_tune bs_qkv_slab: K-part slabs (a grid of whole rounds: 384 QKV tiles x 2 parts over
+            // 256 CUs) summed + biased + rounded by the fused attention that reads them
+            // (bsQ holds BS_KPARTS x 32 rows of either stack's width; the plan never exceeds those)
+            // (only where the attention below is one of the fused kernels that read the slabs)
+            const bool fused_fast = b.is_fast && b.fixed_pos >= 0 && b.fixed_pos < 16 && d.hd <= 256;
+            const bool fused_slow = !b.is_fast && rows_distinct_slots && fm_tuning().attn_fd &&
+                                    attn_fd_ok(d.hd, d.nh / d.nkv);
+            // (weight-only int8 keeps the STORE epilogue: its row scales apply before the rounding)
+            const bool slab_ok = fm_tuning().bs_qkv_slab && fm_tuning().batched_fused_attn && m->bsQ && R <= 32 &&
+                                 (fused_fast || fused_slow) && !m->qinfo(L.wqkv);
+            if (slab_ok && bs_linear(L.wqkv, nullptr, b.xnb, d.dim, R, d.nqkv(), d.dim, nullptr, d.nqkv(), m->bsQ,
+                                     EPI_SLAB, &kp)) {
+                b.qslab = m->bsQ;
+                b.qslab_kp = kp;
+                return;
+            }
+            if (bs_linear(L.wqkv, L.bqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, m->qkv, d.nqkv(), nullptr, EPI_STORE)) return;
+        } else if (!b.is_fast && !rows_distinct_slots && fm_tuning().prompt_qkv_slab &&
+                   prompt_slab(L.wqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, &kp)) {
+            // a prompt chunk's QKV as K-slice slabs, summed by qk_rope_cache_kernel itself (no epilogue launch)
+            b.qslab = m->skpart;
+            b.qslab_kp = kp;
+            return;
+        }
+        linear(L.wqkv, nullptr, L.bqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, m->qkv, d.nqkv(), nullptr, 0, nullptr,
+               EPI_STORE, "linear");
+    }
+    // One row per slot (batched decode frames, every fast pass): the fused decode attention
+    // kernels of the small-batch path do QK-norm, RoPE and the KV write themselves.  Prompt
+    // chunks (rows of one slot, causal among themselves) keep the separate write + attention.
+    void blk_attn(const Blk& b) {
+        const StackDims& d = b.d;
+        const LayerW& L = b.L;
+        const int R = b.R;
+        const float eps = m->c.norm_eps, scale = 1.0f / sqrtf((float)d.hd);
+        const bool rows_are_slots = b.is_fast || rows_distinct_slots;
+        hipStream_t st = s;
+        if (rows_are_slots && !b.is_fast && fm_tuning().batched_fused_attn) {
+            AttnDecArgs<T> aa{(const T*)m->qkv, d.nqkv(), b.rslot, b.rpos, d.nh, d.nkv, d.hd, d.qk_norm, eps,
+                              (const T*)L.qn, (const T*)L.kn, b.rope, (T*)b.kc, (T*)b.vc, b.sstride, b.loff, b.Sc,
+                              m->maxsplit, scale, m->part};
+            aa.cap = attn2_cap(d.hd, d.nh / d.nkv, E);
+            if (fm_tuning().attn_cap_batched) aa.cap = std::min(aa.cap, fm_tuning().attn_cap_batched);
+            aa.maxsplit = FM_CEIL(b.Sc, aa.cap);
+            aa.cnt = m->attn_cnt;
+            aa.dbg = fm_tuning().dbg;
+            aa.out = (T*)m->att;
+            aa.qslab = b.qslab;
+            aa.qslab_kp = b.qslab_kp;
+            aa.qbias = (const T*)L.bqkv;
+            FMCHECK(!b.qslab || (fm_tuning().attn_fd && attn_fd_ok(d.hd, d.nh / d.nkv)), "bs_qkv_slab needs attn_fd");
+            auto go = [st, aa, R] { attn_slow_on(st, aa, R); };
+            m->prof.record("attn_slow", 0, go);  // the slow model's launches alone (fm_llm_kernel_bench)
+            launch("attn", 0, 0, go);
+        } else if (b.is_fast && fm_tuning().batched_fused_attn && b.fixed_pos >= 0 && b.fixed_pos < 16 && d.hd <= 256) {
+            FastFusedArgs<T> fa{(const T*)m->qkv, d.nqkv(), b.rslot, d.nh, d.nkv, d.hd, d.qk_norm, eps,
+                                (const T*)L.qn, (const T*)L.kn, b.rope, (T*)b.kc, (T*)b.vc, b.sstride, b.loff, b.Sc,
+                                b.fixed_pos, scale, (T*)m->att};
+            fa.dbg = fm_tuning().dbg;
+            fa.qslab = b.qslab;
+            fa.qslab_kp = b.qslab_kp;
+            fa.qbias = (const T*)L.bqkv;
+            launch("attn", 0, 0, [st, fa, R] { launch_fast_attn2<T>(st, fa, R); });
+        } else {
+            QkArgs<T> qa{(const T*)m->qkv, d.nqkv(), b.rslot, b.rpos, b.fixed_pos, d.nh, d.nkv, d.hd, d.qk_norm,
+                         eps, (const T*)L.qn, (const T*)L.kn, b.rope, (T*)m->q, (T*)b.kc, (T*)b.vc, b.sstride, b.loff, b.Sc};
+            qa.qslab = b.qslab;
+            qa.qslab_kp = b.qslab_kp;
+            qa.qbias = (const T*)L.bqkv;
+            run_("rope", 0, 0, [&] { launch_qk_rope_cache<T>(s, qa, R); });
+            if (b.is_fast) {
+                FastAttnArgs<T> fa{(const T*)m->q, b.rslot, (const T*)b.kc, (const T*)b.vc, b.sstride, b.loff, b.Sc,
+                                   d.nh, d.nkv, d.hd, b.fixed_pos, scale, (T*)m->att};
+                run_("attn", 0, 0, [&] { launch_fast_attn<T>(s, fa, R); });
+                return;
+            }
+            // rows [r0, r0 + len) in pieces of <= ATTN_PIECE rows (rows are independent given the cache)
+            auto attn_rows = [&](int r0, int len, bool one_slot) {
+                for (int p0 = r0; p0 < r0 + len; p0 += ATTN_PIECE) {
+                    const int pn = std::min(ATTN_PIECE, r0 + len - p0);
+                    const size_t o = (size_t)p0 * d.nh * d.hd;
+                    AttnArgs<T> aa{(const T*)m->q + o, b.rslot + p0, b.rpos + p0, (const T*)b.kc, (const T*)b.vc, b.sstride,
+                                   b.loff, b.Sc, d.nh, d.nkv, d.hd, ATTN_SPLIT, m->maxsplit, scale, m->part};
+                    run_("attn", 0, 0, [&] { launch_attn<T>(s, aa, pn, m->maxsplit, (T*)m->att + o, one_slot); });
+                }
+            };
+            if (!segs.empty())  // a batched prefill chunk: attention per prompt segment
+                for (const auto& sg : segs) attn_rows(sg[0], sg[1], true);
+            else
+                attn_rows(0, R, !rows_are_slots);
+        }
+    }
+    // h = x + wo(att), and xn = ffn_norm(h) where the next stage does not normalise itself
+    void blk_wo(const Blk& b) {
+        const StackDims& d = b.d;
+        const LayerW& L = b.L;
+        const int R = b.R;
+        int kp = 0;
+        if (b.chain) {
+            BsExtra eo;  // finalised with its tile sums by the last K part
+            eo.res = b.xb;
+            eo.res_out = b.hb;
+            eo.ss_out = m->ssH;
+            FMCHECK(bs_linear(L.wo, L.bo, m->att, d.nq(), R, d.dim, d.nq(), nullptr, d.dim, m->bsA, EPI_SLABFIN, &kp, &eo),
+                    "bsacc: no SLABFIN wo plan");
+        } else if (b.bs && bs_linear(L.wo, nullptr, m->att, d.nq(), R, d.dim, d.nq(), nullptr, d.dim, m->bsA, EPI_SLAB, &kp)) {
+            finalize_norm(m->bsA, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, wscale(L.wo));
+        } else if (!b.bs && prompt_slab(L.wo, m->att, d.nq(), R, d.dim, d.nq(), &kp)) {
+            finalize_norm(m->skpart, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, nullptr);
+        } else {
+            linear(L.wo, nullptr, L.bo, m->att, d.nq(), R, d.dim, d.nq(), b.hb, d.dim, b.xb, d.dim, nullptr,
+                   EPI_RESID, "linear");
+            run_("norm", 0, 0, [&] {
+                launch_rmsnorm<T>(s, (const T*)b.hb, d.dim, (const T*)L.fn, d.dim, m->c.norm_eps, (T*)b.xnb, d.dim, R);
+            });
+        }
+    }
+    // act = SwiGLU(w1 xn, w3 xn) on the row-interleaved W1 || W3
+    void blk_w13(const Blk& b) {
+        const StackDims& d = b.d;
+        const LayerW& L = b.L;
+        const int R = b.R;
+        if (b.chain) {
+            BsExtra e13;  // ffn_norm(h) in W1||W3's prologue
+            e13.pro = PRO_PRENORM;
+            e13.ss_in = m->ssH;
+            e13.nw = L.fn;
+            FMCHECK(bs_linear(L.w13, nullptr, b.hb, d.dim, R, 2 * d.inter, d.dim, m->act, d.inter, nullptr, EPI_SWIGLU8,
+                              nullptr, &e13),
+                    "bsacc: no PRENORM w13 plan");
+            return;
+        }
+        if (b.bs && bs_linear(L.w13, nullptr, b.xnb, d.dim, R, 2 * d.inter, d.dim, m->act, d.inter, nullptr, EPI_SWIGLU8))
+            return;
+        // a prompt chunk's w1 || w3 with the SwiGLU in its split-K epilogue (skinny path), else the
+        // stored output and the SwiGLU launch
+        if (fm_tuning().prompt_swiglu && prompt_gemm(L.w13, nullptr, nullptr, b.xnb, d.dim, R, 2 * d.inter, d.dim, m->act,
+                                                     d.inter, nullptr, 0, EPI_SWIGLU8, "linear"))
+            return;
+        linear(L.w13, nullptr, nullptr, b.xnb, d.dim, R, 2 * d.inter, d.dim, m->act2, 2 * d.inter, nullptr, 0, nullptr,
+               EPI_STORE, "linear");
+        run_("other", 0, 0,
+             [&] { launch_swiglu_i8<T>(s, (const T*)m->act2, 2 * d.inter, (T*)m->act, d.inter, d.inter, R); });
+    }
+    // x = h + w2(act): as slabs it stays pending for the next block's norm launch (or flush())
+    void blk_w2(const Blk& b) {
+        const StackDims& d = b.d;
+        const LayerW& L = b.L;
+        const int R = b.R;
+        int kp = 0;
+        if (b.chain) {
+            BsExtra e2;  // finalised with its tile sums
+            e2.res = b.hb;
+            e2.res_out = b.xb;
+            e2.ss_out = m->ssX;
+            FMCHECK(bs_linear(L.w2, nullptr, m->act, d.inter, R, d.dim, d.inter, nullptr, d.dim, m->bsB, EPI_SLABFIN, &kp,
+                              &e2),
+                    "bsacc: no SLABFIN w2 plan");
+            x_ss = true;
+        } else if (b.bs && bs_linear(L.w2, nullptr, m->act, d.inter, R, d.dim, d.inter, nullptr, d.dim, m->bsB, EPI_SLAB, &kp)) {
+            set_pending(m->bsB, kp, d.dim, R, b.hb, b.xb, wscale(L.w2));
+        } else if (!b.bs && prompt_slab(L.w2, m->act, d.inter, R, d.dim, d.inter, &kp)) {
+            set_pending(m->skpart, kp, d.dim, R, b.hb, b.xb, nullptr);
+        } else {
+            linear(L.w2, nullptr, nullptr, m->act, d.inter, R, d.dim, d.inter, b.xb, d.dim, b.hb, d.dim, nullptr,
+                   EPI_RESID, "linear");
+        }
+    }
+    // TransformerBlock.forward (llama.py:838-843) on R rows (a batched decode frame's, or a prompt chunk's);
+    // x is updated in place
+    void block(const StackDims& d, const LayerW& L, int R, const int* rslot, const int* rpos,
+               int fixed_pos, bool is_fast, void* kc, void* vc, size_t sstride, size_t loff, int Sc,
+               const float* rope, void* xb, void* hb, void* xnb) {
+        const bool bs = bs_use(R, is_fast);
+        Blk b{d, L, R, rslot, rpos, fixed_pos, is_fast, kc, vc, sstride, loff, Sc, rope, xb, hb, xnb, bs, bs && bs_chain(d, R)};
+        blk_qkv(b);
+        blk_attn(b);
+        blk_wo(b);
+        blk_w13(b);
+        blk_w2(b);
+    }
+
+    // ---------------- small-batch (<= 8 streams) fused path --------------------------------
+    GemvArgs<T> ga() {
+        GemvArgs<T> a{};
+        a.eps = m->c.norm_eps;
+        a.dummy_tail = fm_tuning().gemv_dummy;
+        return a;
+    }
+    // ---- batch-1 GEMV chain: consecutive GEMVs of one row are deferred and launched together
+    // (gemv_chain_kernel), up to GEMV_CHAIN_MAX per launch; any other launch flushes them first
+    struct ChainSt {
+        GemvArgs<T> a;
+        int kind;
+        int64_t bytes;
+        double flops;
+    };
+    std::vector<ChainSt> chain;
+    int chain_kind(const GemvArgs<T>& a, int pro, int epi, int ksb) const {
+        const FmTuning& t = fm_tuning();
+        if (!t.gemv_chain || m->prof.on || ksb != 1 || a.R != 1 || a.Wq || m->qinfo(a.W) || !t.gemv_nt ||
+            t.gemv_u != 8 || t.gemv_wpb != 4 || a.N % 16 || a.xidx)
+            return -1;
+        if (pro == PRO_PLAIN && epi == EPI_SLABFIN) return GEMV_CHAIN_WO_W2;
+        if (a.xn_out || a.K > 4096 || pro != PRO_PRENORM) return a.xn_out && pro == PRO_PRENORM && epi == EPI_F32 &&
+                                                                    a.K <= 4096 ? GEMV_CHAIN_HEAD : -1;
+        if (epi == EPI_SWIGLU8) return GEMV_CHAIN_W13;
+        if (epi == EPI_STORE) return GEMV_CHAIN_QKV;
+        if (epi == EPI_F32) return GEMV_CHAIN_HEAD;
+        return -1;
+    }
+    void chain_flush() {
+        if (chain.empty()) return;
+        std::vector<ChainSt> c;
+        c.swap(chain);
+        if (c.size() == 1) {
+            static const int pro_of[4] = {PRO_PLAIN, PRO_PRENORM, PRO_PRENORM, PRO_PRENORM};
+            static const int epi_of[4] = {EPI_SLABFIN, EPI_SWIGLU8, EPI_STORE, EPI_F32};
+            gemv_now(c[0].a, pro_of[c[0].kind], epi_of[c[0].kind], 1, "linear");
+            return;
+        }
+        GemvChainArgs<T> g{};
+        int64_t bytes = 0;
+        double flops = 0;
+        g.n = (int)c.size();
+        for (int i = 0; i < g.n; ++i) {
+            g.st[i] = c[i].a;
+            if (!g.st[i].tickets) g.st[i].tickets = m->tickets;
+            g.kind[i] = c[i].kind;
+            bytes += c[i].bytes;
+            flops += c[i].flops;
+        }
+        g.cnt = m->chain_cnt;
+        g.err = m->chain_err;
+        g.sleep = fm_tuning().chain_sleep;
+        hipStream_t st = s;
+        auto go = [st, g] { launch_gemv_chain<T>(st, g); };
+        launch("linear", bytes, flops, go);
+    }
+    void gemv(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls) {
+        const int kind = chain_kind(a, pro, epi, ksb);
+        if (kind < 0) {
+            chain_flush();
+            gemv_now(a, pro, epi, ksb, cls);
+            return;
+        }
+        const size_t E = sizeof(T);
+        const int64_t bytes = (int64_t)a.N * a.K * E + (int64_t)a.K * E;
+        chain.push_back(ChainSt{a, kind, bytes, 2.0 * a.N * a.K});
+        if ((int)chain.size() >= std::min(GEMV_CHAIN_MAX, fm_tuning().chain_max) || kind == GEMV_CHAIN_HEAD)
+            chain_flush();
+    }
+    void gemv_now(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls) {
+        int64_t wbytes = (int64_t)a.N * a.K * E * (epi == EPI_SWIGLU ? 2 : 1);
+        const auto* q = m->qinfo(a.W);
+        if (q && q->sz && !fm_tuning().int4_stream) q = nullptr;  // int4 model on its dequantised bf16 weights
+        if (q) {
+            a.Wq = q->q8;
+            if (q->sz) {  // weight-only int4: 4-bit codes + group (scale, zero), whole 128-k units per slice
+                a.wsz = q->sz;
+                a.wscale = nullptr;
+                while (ksb > 1 && (a.K / ksb) % 128) ksb /= 2;
+                wbytes = (int64_t)a.N * a.K / 2 + (int64_t)(a.N + 15) / 16 * 16 * (a.K / 128) * 4;
+            } else {  // weight-only int8: the int8 stream, whole 64-k units per slice
+                a.wscale = (const T*)q->scale;
+                while (ksb > 1 && (a.K / ksb) % 64) ksb /= 2;
+                wbytes = (int64_t)a.N * a.K;
+            }
+        }
+        const int64_t bytes = wbytes + (int64_t)a.R * a.K * E;
+        const double flops = 2.0 * a.R * a.N * a.K * (epi == EPI_SWIGLU ? 2 : 1);
+        hipStream_t st = s;
+        if (!a.tickets) a.tickets = m->tickets;
+        auto go = [st, a, pro, epi, ksb] { launch_gemv<T>(st, a, pro, epi, ksb); };
+        launch(cls, bytes, flops, go);
+    }
+    // batch-1 bf16 wo / w2 on the row-block GEMV (fm_rowgemv.hip: one block per pair of rows, every
+    // CU busy); their RMSNorm consumers then take the statistic from the row they stage (ss_gran 1)
+    // the row-block GEMV's enabled linears (fm_tune rowgemv; int4 models: rowgemv_q4)
+    int row_bits() const {
+        const FmTuning& t = fm_tuning();
+        return m->quant == FM_QUANT_INT4 ? t.rowgemv_q4 : t.rowgemv;
+    }
+    bool row_fin(int n) const {
+        const FmTuning& t = fm_tuning();
+        return sizeof(T) == 2 && n == 1 && m->row_ok && (row_bits() & 1) && !t.gemv_chain && !t.attn_wo &&
+               (m->quant != FM_QUANT_INT4 || t.int4_stream);
+    }
+    // ... and wqkv (norm prologue, 8 rows per block)
+    bool row_qkv(int n) const {
+        const FmTuning& t = fm_tuning();
+        // (int8: the tile kernel's wqkv measured as fast, 3.12 vs 3.14 ms per frame)
+        return sizeof(T) == 2 && n == 1 && m->row_qkv_ok && m->quant != FM_QUANT_INT8 && (row_bits() & 2) &&
+               !t.gemv_chain && (m->quant != FM_QUANT_INT4 || t.int4_stream);
+    }
+    // ... and w1 || w3 (norm prologue, SwiGLU epilogue, 4 + 4 rows per block)
+    bool row_w13(int n) const {
+        const FmTuning& t = fm_tuning();
+        return sizeof(T) == 2 && n == 1 && m->row_w13_ok && (row_bits() & 4) && !t.gemv_chain &&
+               (m->quant != FM_QUANT_INT4 || t.int4_stream);
+    }
+    // the row-block GEMV's weight: bf16 row-major, or the int8 codes + row scales, or the int4 code words + group
+    // (scale, zero) rows.  rowscale holds only w1 || w3's row-block interleaved scales (pack_w13 is its one
+    // writer), so for every other linear -- the codebook head included -- the lookup misses and the packed
+    // weight's own row scales apply.
+    void row_weight(RowGemvArgs& r, const void* rm, const void* packed) {
+        if (m->quant == FM_QUANT_INT4) {
+            r.Wq4 = (const uint32_t*)rm;
+            r.wsz = (const uint32_t*)m->rowsz.at(packed);
+            r.gs = m->q4_gs;
+        } else if (m->quant) {
+            r.Wq = (const int8_t*)rm;
+            auto it = m->rowscale.find(packed);
+            r.wscale = (const bf16_t*)(it != m->rowscale.end() ? it->second : m->qinfo(packed)->scale);
+        } else {
+            r.W = (const bf16_t*)rm;
+        }
+    }
+    // weight bytes a row-block GEMV streams (int4: codes + group words; int8: codes + row scales)
+    static int64_t rowgemv_wbytes(const RowGemvArgs& a) {
+        return a.Wq4 ? (int64_t)a.N * a.K / 2 + (int64_t)a.N * (a.K / a.gs) * 4
+                     : (a.Wq ? (int64_t)a.N * a.K + (int64_t)a.N * 2 : (int64_t)a.N * a.K * 2);
+    }
+    // the residual a wo GEMV adds: the layer's input row itself for a stack's first layer (a table row gathered
+    // by xidx[xcol] at codebook > 0), else the residual row xb
+    void row_residual(RowGemvArgs& r, bool first, const void* x_in, int ldx_in, const int32_t* xidx, int xcol,
+                      const void* xb, int dim) {
+        r.res = (const bf16_t*)(first ? x_in : xb);
+        r.ldr = first ? ldx_in : dim;
+        if (first) {
+            r.residx = xidx;
+            r.res_col = xcol;
+            r.res_rows = xidx ? m->cb : 0;
+        }
+    }
+    // KV prefetch operands of a QKV GEMV (GemvArgs / RowGemvArgs pf_*): the cached rows 0 .. *pos of *slot
+    template <typename A, typename P>
+    static void kv_prefetch(A& a, const P* kc, const P* vc, const int32_t* slot, const int32_t* pos, size_t slot_stride,
+                            size_t layer_off, int S, int nkv, int hd) {
+        a.pf_kc = kc;
+        a.pf_vc = vc;
+        a.pf_slot = slot;
+        a.pf_pos = pos;
+        a.pf_slot_stride = slot_stride;
+        a.pf_layer_off = layer_off;
+        a.pf_S = S;
+        a.pf_nkv = nkv;
+        a.pf_hd = hd;
+    }
+    void rowgemv(const RowGemvArgs& a, int kind) {
+        hipStream_t st = s;
+        auto go = [st, a, kind] { launch_rowgemv(st, a, kind); };
+        launch("linear", rowgemv_wbytes(a) + (int64_t)a.K * 2, 2.0 * a.N * a.K, go);
+    }
+    template <typename F> void run_(const char* cls, int64_t bytes, double flops, F&& f) {
+        chain_flush();
+        m->prof.run(s, cls, bytes, flops, std::forward<F>(f));
+    }
+    // run one launch and record it for fm_llm_kernel_bench (under rec where that class differs from the
+    // profiler's): `go` must capture by value (it is replayed later).  Pending chain GEMVs go first.
+    template <typename F> void launch(const char* cls, int64_t bytes, double flops, const F& go, const char* rec = nullptr) {
+        chain_flush();
+        m->prof.record(rec ? rec : cls, bytes, go);
+        m->prof.run(s, cls, bytes, flops, go);
+    }
+    struct KsbPlan {
+        int wo, w2;
+    };
+    // wo / w2 finalise the residual rows (EPI_SLABFIN): whole K per block (local finalise, no
+    // cross-block hand-off) whenever the x slice fits the LDS budget, else split K
+    KsbPlan plan(const StackDims& d, int n) {
+        auto fin_ksb = [&](int N, int K) {
+            const int fk = fm_tuning().fin_ksb;  // developer override (split-K factor)
+            if (fk > 0 && K % (32 * fk) == 0) return fk;
+            // (splitting K further to fill more CUs measured slower at B = 1: 4.37 -> 4.74 ms per
+            // frame at 320 blocks, the split-K hand-off costs more than the idle CUs)
+            return gemv_lds_bytes(n, K, E) <= 120 * 1024 ? 1 : pick_ksb(N, K, n, E);
+        };
+        return KsbPlan{fin_ksb(d.dim, d.nq()), fin_ksb(d.dim, d.inter)};
+    }
+    // a layer's QKV projection (+ attention_norm) of one row on the row-block GEMV.  first: x is the layer's
+    // input row itself (a table row gathered by xidx[xcol] when xidx), else the residual row xb.  a: the tile
+    // form's arguments, whose KV prefetch fields carry over.  kv_rows (fm_tune rowgemv bit 6): rows [nq, nqkv)
+    // only -- the same prologue and the same per-row sums, the Q rows of Y left as they were
+    void qkv_row(const StackDims& d, const LayerW& L, const GemvArgs<T>& a, bool first, const void* x, int ldx,
+                 const int32_t* xidx, int xcol, void* Y, bool kv_rows) {
+        RowGemvArgs r{};
+        row_weight(r, L.wqkv_rm, L.wqkv);  // (bf16 or int4: row_qkv excludes int8 models)
+        r.X = (const bf16_t*)x;
+        if (first) {
+            r.ldx = ldx;
+            r.xidx = xidx;
+            r.xcol = xcol;
+            r.xrows = xidx ? m->cb : 0;
+        }
+        r.bias = (const bf16_t*)L.bqkv;
+        r.nw = (const bf16_t*)L.an;
+        r.eps = m->c.norm_eps;
+        r.Y = (bf16_t*)Y;
+        r.N = d.nqkv();
+        r.K = d.dim;
+        if (kv_rows) {
+            r.W += (size_t)d.nq() * d.dim;
+            if (r.bias) r.bias += d.nq();
+            r.Y += d.nq();
+            r.N -= d.nq();
+        }
+        kv_prefetch(r, (const bf16_t*)a.pf_kc, (const bf16_t*)a.pf_vc, a.pf_slot, a.pf_pos, a.pf_slot_stride, a.pf_layer_off,
+                    a.pf_S, a.pf_nkv, a.pf_hd);
+        rowgemv(r, ROWGEMV_NORM_STORE);
+    }
+    bool qkv_first_row(int n) const { return row_qkv(n) && (row_bits() & 16); }
+    // the FIRST layer's QKV of one row: the row form (rowgemv bits 1 and 4), else the PRO_NORM tile form.
+    // block_small's launch, and -- one launch per code, xidx an iota array, Y the code's table row -- what
+    // ensure_qkv0 fills the bit-5 table with: the same kernel on the same input row gives the same bytes
+    void qkv_first(const StackDims& d, const LayerW& L, GemvArgs<T> a, int n, const void* x_in, int ldx_in,
+                   const int32_t* xidx, int xcol, void* Y, bool kv_rows) {
+        if (qkv_first_row(n)) {
+            qkv_row(d, L, a, true, x_in, ldx_in, xidx, xcol, Y, kv_rows);
+            return;
+        }
+        a.Y = (T*)Y;
+        a.X = (const T*)x_in;
+        a.ldx = ldx_in;
+        a.xidx = xidx;
+        a.xidx_ld = m->C1;
+        a.xidx_col = xcol;
+        a.xidx_rows = xidx ? m->cb : 0;
+        gemv(a, PRO_NORM, EPI_STORE, 1, "linear");
+    }
+    // the tile form's arguments of a fast layer's QKV at one row, no prefetch (the table build)
+    GemvArgs<T> qkv_args(const StackDims& d, const LayerW& L, int n) {
+        GemvArgs<T> a = ga();
+        a.W = (const T*)L.wqkv;
+        a.bias = (const T*)L.bqkv;
+        a.nw = (const T*)L.an;
+        a.R = n;
+        a.N = d.nqkv();
+        a.K = d.dim;
+        a.Y = (T*)m->qkv;
+        a.ldy = d.nqkv();
+        return a;
+    }
+    // whether block_small may read the first fast layer's QKV from the table (bit 5; bf16, unquantised)
+    bool qkv0_live() const {
+        return sizeof(T) == 2 && !m->quant && (row_bits() & 32) && m->qkv0 && m->qkv0_built &&
+               m->qkv0_epoch == fm_tuning().epoch;
+    }
+
+    // One layer of block_small: its arguments ...
+    // x_in: the first layer's input (plain rows, or an embedding table + xidx gather), whose norm is computed in
+    // place.  xo: where W2 writes the block's output row (xb itself unless the chain alternates buffers)
+    struct Small {
+        const StackDims& d;
+        const LayerW& L;
+        int n;
+        bool first;
+        const void* x_in;
+        int ldx_in;
+        const int32_t* xidx;
+        int xcol;
+        void *xb, *hb;
+        bool is_fast;
+        int cpos, layer;
+        KsbPlan kp;
+        void* xo;
+    };
+    // ... and the kernel path of each of its stages, chosen once (small_path)
+    struct SmallPath {
+        bool rf;        // wo / w2 on the row-block GEMV; their RMSNorm consumers take the statistic from the row they stage
+        bool fw;        // fast model: attention + wo as one launch (fattn_wo_kernel), no attention launch
+        bool att_wo;    // fast model: attention recomputed in the wo tile GEMV's prologue (PRO_FATT), no attention launch
+        bool row_here;  // this layer's QKV on the row-block GEMV (a stack's first layer: only with rowgemv bit 4)
+        bool tab;       // rowgemv bit 5: the first fast layer at codebook > 0 inside fw: its q|k|v row comes from the table, no QKV launch
+        bool kv0;       // rowgemv bit 6: codebook 0 on the row path: only K / V are projected and the attention reads no Q (one position: output = v)
+        bool kv_only;   // the layer ends after its K / V cache write (fm_tune fast_tail: its output would be discarded)
+    };
+    SmallPath small_path(const Small& c, bool kv_only) const {
+        const StackDims& d = c.d;
+        SmallPath p{};
+        p.kv_only = kv_only;
+        p.rf = row_fin(c.n);
+        const int fq = m->quant == FM_QUANT_INT8 ? 1 : (m->quant == FM_QUANT_INT4 ? 2 : 0);
+        p.fw = c.is_fast && !kv_only && p.rf && fm_tuning().fattn_wo && m->fxt && m->fdm.n_layer * m->C >= 2 &&
+               m->fdm.n_layer * m->C <= 40 && fattn_wo_ok(d.nh, d.nkv, d.hd, c.cpos, d.dim, d.nq(), fq);
+        // (fm_tune attn_wo; measured slower, kept under test)
+        p.att_wo = c.is_fast && !kv_only && fm_tuning().attn_wo && !m->quant && c.n == 1 && c.cpos < 16 && d.hd % 16 == 0 &&
+                   d.hd <= 128 && d.nh % d.nkv == 0 && (d.nq() / c.kp.wo) % d.hd == 0 && d.nqkv() % 8 == 0;
+        p.row_here = row_qkv(c.n) && (!c.first || (row_bits() & 16));
+        // bits 5 / 6: bf16, unquantised, batch 1; inert elsewhere (with kv0 the Q part of m->qkv is stale)
+        const bool bits56 = sizeof(T) == 2 && !m->quant && c.is_fast && c.n == 1;
+        p.tab = bits56 && c.first && c.xidx && p.fw && qkv0_live();
+        p.kv0 = bits56 && c.cpos == 0 && (row_bits() & 64) && p.row_here && !p.att_wo && d.hd <= 256 &&
+                (d.nqkv() - d.nq()) % fm_tuning().row_qkv_rp == 0;
+        return p;
+    }
+    // the fast model's attention operands at this layer (the attention launch, fattn_wo, PRO_FATT)
+    FastFusedArgs<T> small_fast_args(const Small& c, const SmallPath& p) const {
+        const StackDims& d = c.d;
+        FastFusedArgs<T> fa{(const T*)m->qkv, d.nqkv(), m->frame_slot, d.nh, d.nkv, d.hd, d.qk_norm,
+                            m->c.norm_eps, (const T*)c.L.qn, (const T*)c.L.kn, m->frope, (T*)m->fkc,
+                            (T*)m->fvc, m->fslot_stride, (size_t)c.layer * m->flayer_stride, m->C, c.cpos,
+                            1.0f / sqrtf((float)d.hd), (T*)m->att};
+        fa.dbg = fm_tuning().dbg;
+        fa.noq = p.kv0;
+        return fa;
+    }
+    // QKV (+ attention_norm)
+    void small_qkv(const Small& c, const SmallPath& p) {
+        if (p.tab) return;
+        const StackDims& d = c.d;
+        GemvArgs<T> a = qkv_args(d, c.L, c.n);
+        if (!c.is_fast && c.n == 1 && fm_tuning().kv_prefetch)  // the attention's K / V rows into L2
+            kv_prefetch(a, (const T*)m->kc, (const T*)m->vc, m->frame_slot, m->frame_pos, m->slot_stride,
+                        (size_t)c.layer * m->layer_stride, m->S, d.nkv, d.hd);
+        else if (c.is_fast && c.n == 1 && fm_tuning().fkv_prefetch && m->fiota && c.cpos < 16)
+            // the fast attention's cached rows 0 .. cpos - 1 (fiota[cpos] = cpos - 1)
+            kv_prefetch(a, (const T*)m->fkc, (const T*)m->fvc, m->frame_slot, m->fiota + c.cpos, m->fslot_stride,
+                        (size_t)c.layer * m->flayer_stride, m->C, d.nkv, d.hd);
+        if (c.first) {  // the layer's input row itself (a table row gathered by xidx[xcol] at codebook > 0)
+            qkv_first(d, c.L, a, c.n, c.x_in, c.ldx_in, c.xidx, c.xcol, m->qkv, p.kv0);
+        } else if (p.row_here) {
+            qkv_row(d, c.L, a, false, c.xb, 0, nullptr, 0, m->qkv, p.kv0);
+        } else {
+            a.X = (const T*)c.xb;
+            a.ldx = d.dim;
+            a.ss_in = m->ssX;
+            a.ss_gran = p.rf ? 1 : 0;
+            gemv(a, PRO_PRENORM, EPI_STORE, 1, "linear");
+        }
+    }
+    // attention launch (none where wo does it: fw, att_wo)
+    void small_attn(const Small& c, const SmallPath& p) {
+        const StackDims& d = c.d;
+        const int n = c.n;
+        hipStream_t st = s;
+        if (!c.is_fast) {
+            AttnDecArgs<T> aa{(const T*)m->qkv, d.nqkv(), m->frame_slot, m->frame_pos, d.nh, d.nkv, d.hd,
+                              d.qk_norm, m->c.norm_eps, (const T*)c.L.qn, (const T*)c.L.kn, m->rope, (T*)m->kc,
+                              (T*)m->vc, m->slot_stride, (size_t)c.layer * m->layer_stride, m->S,
+                              m->maxsplit, 1.0f / sqrtf((float)d.hd), m->part};
+            aa.cap = attn2_cap(d.hd, d.nh / d.nkv, E);
+            if (fm_tuning().attn_cap) aa.cap = std::min(aa.cap, fm_tuning().attn_cap);
+            aa.maxsplit = FM_CEIL(m->S, aa.cap);
+            aa.cnt = m->attn_cnt;
+            aa.dbg = fm_tuning().dbg;
+            aa.out = (T*)m->att;
+            auto go = [st, aa, n] { attn_slow_on(st, aa, n); };
+            m->prof.record("attn_slow", 0, go);  // the slow model's launches alone (fm_llm_kernel_bench)
+            launch("attn", 0, 0, go);
+        } else if (!p.att_wo && !p.fw) {
+            const FastFusedArgs<T> fa = small_fast_args(c, p);
+            const bool f2 = c.cpos < 16 && d.hd <= 256;
+            launch("attn", 0, 0, [st, fa, n, f2] {
+                if (f2)
+                    launch_fast_attn2<T>(st, fa, n);
+                else
+                    launch_fast_attn_fused<T>(st, fa, n);
+            });
+        }
+    }
+    // wo: h = x + wo(att) (tile form: split-K, the last block of each tile finalises h and its sums of squares)
+    void small_wo(const Small& c, const SmallPath& p) {
+        const StackDims& d = c.d;
+        const LayerW& L = c.L;
+        if (p.fw || p.rf) {
+            FattnWoArgs A{};
+            RowGemvArgs& r = A.wo;
+            row_weight(r, L.wo_rm, L.wo);
+            r.X = (const bf16_t*)m->att;  // (fw: unused, x comes from the tagged words)
+            r.bias = (const bf16_t*)L.bo;
+            row_residual(r, c.first, c.x_in, c.ldx_in, c.xidx, c.xcol, c.xb, d.dim);
+            r.res_out = (bf16_t*)c.hb;
+            r.N = d.dim;
+            r.K = d.nq();
+            if (!p.fw) {
+                rowgemv(r, ROWGEMV_FIN);
+                return;
+            }
+            const FastFusedArgs<T> fa = small_fast_args(c, p);
+            A.at = *reinterpret_cast<const FastFusedArgs<bf16_t>*>(&fa);
+            A.at.dbg = nullptr;
+            A.at.row_pos = m->frame_pos;
+            A.xt = m->fxt;
+            A.gen = 1 + c.layer + m->fdm.n_layer * c.cpos;  // <= 40 (fattn_wo_ok: cpos < 16, n_layer * C checked)
+            A.err = m->chain_err;
+            A.delay = fm_tuning().fw_delay;
+            A.cheap = fm_tuning().fw_cheap;
+            A.prio = fm_tuning().fw_prio;
+            A.ilp = fm_tuning().fattn_ilp;
+            if (p.tab) {
+                A.qtab = (const bf16_t*)m->qkv0;
+                A.qidx = c.xidx;
+                A.qcol = c.xcol;
+                A.qrows = m->cb;
+            }
+            A.kv0 = p.kv0;
+            hipStream_t st = s;
+            auto go = [st, A] { launch_fattn_wo(st, A); };
+            // (recorded as "attn_wo", not "linear": attention + GEMV, reported apart)
+            launch("attn", rowgemv_wbytes(r), 2.0 * r.N * r.K, go, "attn_wo");
+            return;
+        }
+        GemvArgs<T> a = ga();
+        a.W = (const T*)L.wo;
+        a.bias = (const T*)L.bo;
+        a.X = (const T*)m->att;
+        a.ldx = d.nq();
+        a.R = c.n;
+        a.N = d.dim;
+        a.K = d.nq();
+        a.Yf = m->slabA;
+        a.ldy = d.dim;
+        if (c.first) {
+            a.res = (const T*)c.x_in;
+            a.ldr = c.ldx_in;
+            a.residx = c.xidx;
+            a.xidx_ld = m->C1;
+            a.xidx_col = c.xcol;
+            a.xidx_rows = c.xidx ? m->cb : 0;
+        } else {
+            a.res = (const T*)c.xb;
+            a.ldr = d.dim;
+        }
+        a.res_out = (T*)c.hb;
+        a.ldro = d.dim;
+        a.ss_out = m->ssH;
+        a.tickets = m->tickets;
+        if (p.att_wo) a.att = small_fast_args(c, p);
+        gemv(a, p.att_wo ? PRO_FATT : PRO_PLAIN, EPI_SLABFIN, c.kp.wo, "linear");
+    }
+    // W1 || W3 (+ ffn_norm) -> SwiGLU act
+    void small_w13(const Small& c, const SmallPath& p) {
+        const StackDims& d = c.d;
+        if (row_w13(c.n)) {
+            RowGemvArgs r{};
+            row_weight(r, c.L.w13_rm, c.L.w13);
+            r.X = (const bf16_t*)c.hb;
+            r.nw = (const bf16_t*)c.L.fn;
+            r.eps = m->c.norm_eps;
+            r.Y = (bf16_t*)m->act;
+            r.N = 2 * d.inter;
+            r.K = d.dim;
+            rowgemv(r, ROWGEMV_NORM_SWIGLU);
+            return;
+        }
+        GemvArgs<T> a = ga();
+        a.W = (const T*)c.L.w13;
+        a.nw = (const T*)c.L.fn;
+        a.R = c.n;
+        a.N = 2 * d.inter;
+        a.K = d.dim;
+        a.X = (const T*)c.hb;
+        a.ldx = d.dim;
+        a.ss_in = m->ssH;
+        a.ss_gran = p.rf ? 1 : 0;
+        a.Y = (T*)m->act;
+        a.ldy = d.inter;
+        gemv(a, PRO_PRENORM, EPI_SWIGLU8, 1, "linear");
+    }
+    // W2: the block output x = h + w2(act) into xo (tile form: split-K, finalised with its sums of squares)
+    void small_w2(const Small& c, const SmallPath& p) {
+        const StackDims& d = c.d;
+        if (p.rf) {
+            RowGemvArgs r{};
+            row_weight(r, c.L.w2_rm, c.L.w2);
+            r.X = (const bf16_t*)m->act;
+            r.res = (const bf16_t*)c.hb;
+            r.ldr = d.dim;
+            r.res_out = (bf16_t*)c.xo;
+            r.N = d.dim;
+            r.K = d.inter;
+            rowgemv(r, ROWGEMV_FIN);
+            return;
+        }
+        GemvArgs<T> a = ga();
+        a.W = (const T*)c.L.w2;
+        a.X = (const T*)m->act;
+        a.ldx = d.inter;
+        a.R = c.n;
+        a.N = d.dim;
+        a.K = d.inter;
+        a.Yf = m->slabB;
+        a.ldy = d.dim;
+        a.res = (const T*)c.hb;
+        a.ldr = d.dim;
+        a.res_out = (T*)c.xo;
+        a.ldro = d.dim;
+        a.ss_out = m->ssX;
+        a.tickets = m->tickets;
+        gemv(a, PRO_PLAIN, EPI_SLABFIN, c.kp.w2, "linear");
+    }
+    // one pre-norm block (TransformerBlock.forward, llama.py:838-843) on n <= 8 rows.  Residual rows
+    // are always finalised by the producing GEMV (EPI_SLABFIN: x / h in bf16 plus per-tile sums of
+    // squares ssX / ssH), so every RMSNorm consumer is PRO_PRENORM.
+    void block_small(const StackDims& d, const LayerW& L, int n, bool first, const void* x_in, int ldx_in,
+                     const int32_t* xidx, int xcol, void* xb, void* hb, bool is_fast, int cpos, int layer,
+                     const KsbPlan& kp, void* xo, bool kv_only = false) {
+        const Small c{d, L, n, first, x_in, ldx_in, xidx, xcol, xb, hb, is_fast, cpos, layer, kp, xo};
+        const SmallPath p = small_path(c, kv_only);
+        small_qkv(c, p);
+        small_attn(c, p);
+        if (p.kv_only) return;  // the attention wrote the K / V rows at cpos, all a later launch reads
+        small_wo(c, p);
+        small_w13(c, p);
+        small_w2(c, p);
+    }
+
+    // the residual row of layer l: x (in place) or, in chain mode, x / x2 alternating
+    void* xbuf(void* x0, void* x1, int l) const { return (fm_tuning().gemv_chain && (l & 1)) ? x1 : x0; }
+    void* xfin = nullptr;  // the slow stack's output row (head_small's input when pending)
+    void slow_small(int n) {
+        const KsbPlan kp = plan(m->sd, n);
+        for (int l = 0; l < m->sd.n_layer; ++l)
+            block_small(m->sd, m->slow[l], n, l == 0, m->x, m->c.dim, nullptr, 0, xbuf(m->x, m->x2, l), m->h, false, 0,
+                        l, kp, xbuf(m->x, m->x2, l + 1));
+        xfin = xbuf(m->x, m->x2, m->sd.n_layer);
+    }
+
+    // final norm (+ pending residual) -> constrained head logits and the fast-model hidden
+    const void* head_small(const void* xlast, bool pending, int n, int ksb_prev) {
+        const fm_model_config& c = m->c;
+        GemvArgs<T> a = ga();
+        a.W = (const T*)m->head_c;
+        a.nw = (const T*)m->norm;
+        a.R = n;
+        a.N = m->Nhead;
+        a.K = c.dim;
+        a.Yf = m->logits;
+        a.ldy = m->Nhead;
+        a.xn_out = (T*)m->xnl;
+        a.ldxo = c.dim;
+        const void* xs = xfin ? xfin : m->x;
+        if (pending) {  // the last slow layer's W2 finalised x (xs) and its sums of squares
+            a.X = (const T*)xs;
+            a.ldx = c.dim;
+            a.ss_in = m->ssX;
+            a.ss_gran = row_fin(n) ? 1 : 0;
+            gemv(a, PRO_PRENORM, EPI_F32, 1, "linear");
+        } else {
+            a.X = (const T*)xlast;
+            a.ldx = c.dim;
+            gemv(a, PRO_NORM, EPI_F32, 1, "linear");
+        }
+        const void* hid = c.norm_fastlayer_input ? m->xnl : (pending ? xs : xlast);
+        if (m->fproj_w) {
+            GemvArgs<T> p = ga();
+            p.W = (const T*)m->fproj_w;
+            p.bias = (const T*)m->fproj_b;
+            p.X = (const T*)hid;
+            p.ldx = c.dim;
+            p.R = n;
+            p.N = c.fast_dim;
+            p.K = c.dim;
+            p.Y = (T*)m->xl;
+            p.ldy = c.fast_dim;
+            gemv(p, PRO_PLAIN, EPI_STORE, 1, "linear");
+            return m->xl;
+        }
+        return hid;
+    }
+
+    void fast_small(int n, int cc, bool with_head, const void* hidden) {
+        const fm_model_config& c = m->c;
+        const KsbPlan kp = plan(m->fdm, n);
+        for (int l = 0; l < m->fdm.n_layer; ++l) {
+            const bool first = l == 0;
+            const void* xin = cc == 0 ? hidden : m->femb;
+            const int32_t* xidx = cc == 0 ? nullptr : m->cols;
+            // codebook 0's pass (no head: inference.py:148-149 discards its output) only fills the fast
+            // KV cache, so its last layer stops once its K / V rows are cached (fm_tune fast_tail)
+            const bool kv_only = !with_head && l == m->fdm.n_layer - 1 && fm_tuning().fast_tail;
+            block_small(m->fdm, m->fast[l], n, first, xin, c.fast_dim, xidx, cc, xbuf(m->fx, m->fx2, l), m->fh, true,
+                        cc, l, kp, xbuf(m->fx, m->fx2, l + 1), kv_only);
+        }
+        if (with_head && sizeof(T) == 2 && n == 1 && m->fout_rm && (row_bits() & 8) && !fm_tuning().gemv_chain &&
+            (m->quant != FM_QUANT_INT4 || fm_tuning().int4_stream)) {
+            RowGemvArgs r{};  // the codebook head on the row-block GEMV (norm prologue, fp32 logits)
+            row_weight(r, m->fout_rm, m->fout);
+            r.X = (const bf16_t*)xbuf(m->fx, m->fx2, m->fdm.n_layer);
+            r.nw = (const bf16_t*)m->fnorm;
+            r.eps = c.norm_eps;
+            r.Yf = m->flogits;
+            r.N = m->cb;
+            r.K = c.fast_dim;
+            rowgemv(r, ROWGEMV_NORM_F32);
+        } else if (with_head) {
+            GemvArgs<T> a = ga();
+            a.W = (const T*)m->fout;
+            a.nw = (const T*)m->fnorm;
+            a.R = n;
+            a.N = m->cb;
+            a.K = c.fast_dim;
+            a.Yf = m->flogits;
+            a.ldy = m->cb;
+            a.X = (const T*)xbuf(m->fx, m->fx2, m->fdm.n_layer);
+            a.ldx = c.fast_dim;
+            a.ss_in = m->ssX;
+            a.ss_gran = row_fin(n) ? 1 : 0;
+            gemv(a, PRO_PRENORM, EPI_F32, 1, "linear");
+        }
+    }
+
+    void frame_tail_small(int n, bool ras_enable, bool sample, const void* hidden) {
+        if (sample) {
+            SampleArgs a = sargs(true, ras_enable, 0);
+            run_("sample", 0, 0, [&] { launch_sample_radix<T>(s, a, n); });
+        }
+        fast_small(n, 0, false, hidden);  // position 0 fills the fast KV cache; logits discarded
+        for (int cc = 1; cc < m->C; ++cc) {
+            fast_small(n, cc, true, hidden);
+            if (sample) {
+                SampleArgs a = sargs(false, 0, cc);
+                run_("sample", 0, 0, [&] { launch_sample_radix<T>(s, a, n); });
+            }
+        }
+    }
+
+    void decode_frame_small(int n) {
+        run_("other", 0, 0, [&] {
+            launch_embed<T>(s, m->tok_in, n, (const T*)m->emb, (const T*)m->cbemb, m->c.dim, m->C, m->cb,
+                            m->c.semantic_begin_id, m->c.semantic_end_id, m->c.scale_codebook_embeddings,
+                            (T*)m->x, m->frame_slot);
+        });
+        slow_small(n);
+        const KsbPlan kp = plan(m->sd, n);
+        const void* hid = head_small(nullptr, true, n, kp.w2);
+        frame_tail_small(n, true, true, hid);
+        chain_flush();
+        launch_finish(s, n, m->frame_slot, m->frame_pos, m->cols, m->C1, m->tok_in, m->ras, m->C1 * 10, m->C1,
+                      1, m->sp);
+    }
+
+    void slow_layers(int R, const int* rslot, const int* rpos) {
+        x_ss = false;
+        for (int l = 0; l < m->sd.n_layer; ++l)
+            block(m->sd, m->slow[l], R, rslot, rpos, -1, false, m->kc, m->vc, m->slot_stride,
+                  (size_t)l * m->layer_stride, m->S, m->rope, m->x, m->h, m->xn);
+        flush();
+    }
+
+    // final norm -> constrained head logits; hidden for the fast model (llama.py:447-466, 826)
+    void head_and_hidden(const void* xlast, int n) {
+        const fm_model_config& c = m->c;
+        chain_flush();
+        run_("norm", 0, 0, [&] {
+            launch_rmsnorm<T>(s, (const T*)xlast, c.dim, (const T*)m->norm, c.dim, c.norm_eps, (T*)m->xnl,
+                              c.dim, n);
+        });
+        linear(m->head_c, nullptr, nullptr, m->xnl, c.dim, n, m->Nhead, c.dim, nullptr, m->Nhead,
+               nullptr, 0, m->logits, EPI_F32, "linear");
+        const void* src = c.norm_fastlayer_input ? m->xnl : xlast;
+        if (m->fproj_w)
+            linear(m->fproj_w, nullptr, m->fproj_b, src, c.dim, n, c.fast_dim, c.dim, m->fx, c.fast_dim,
+                   nullptr, 0, nullptr, EPI_STORE, "linear");
+        else
+            HIPCHK(hipMemcpyAsync(m->fx, src, (size_t)n * c.dim * E, hipMemcpyDeviceToDevice, s));
+    }
+
+    void fast_pass(int n, int cpos, bool with_head) {
+        const fm_model_config& c = m->c;
+        x_ss = false;
+        for (int l = 0; l < m->fdm.n_layer; ++l)
+            block(m->fdm, m->fast[l], n, m->frame_slot, nullptr, cpos, true, m->fkc, m->fvc,
+                  m->fslot_stride, (size_t)l * m->flayer_stride, m->C, m->frope, m->fx, m->fh, m->fxn);
+        flush();
+        if (with_head) {
+            run_("norm", 0, 0, [&] {
+                launch_rmsnorm<T>(s, (const T*)m->fx, c.fast_dim, (const T*)m->fnorm, c.fast_dim,
+                                  c.norm_eps, (T*)m->fxn, c.fast_dim, n);
+            });
+            linear(m->fout, nullptr, nullptr, m->fxn, c.fast_dim, n, m->cb, c.fast_dim, nullptr, m->cb,
+                   nullptr, 0, m->flogits, EPI_F32, "linear");
+        }
+    }
+
+    SampleArgs sargs(bool slow, int ras_enable, int c) {
+        const fm_model_config& cc = m->c;
+        SampleArgs a{};
+        a.logits = slow ? m->logits : m->flogits;
+        a.ldl = slow ? m->Nhead : m->cb;
+        a.Nl = a.ldl;
+        a.row_slot = m->frame_slot;
+        a.sp = m->sp;
+        a.ras = m->ras;
+        a.ras_stride = m->C1 * 10;
+        a.ras_enable = ras_enable;
+        a.slow = slow;
+        a.sb = cc.semantic_begin_id;
+        a.se = cc.semantic_end_id;
+        a.im_end = cc.im_end_id;
+        a.cb = m->cb;
+        a.draw = 1 + c;
+        a.col_idx = c + 1;
+        a.cols = m->cols;
+        a.ldc = m->C1;
+        a.dbg = fm_tuning().dbg;
+        a.force_cols = m->force_cols;
+        a.tap = slow ? m->tap_slow : m->tap_fast + (size_t)(c - 1) * m->cb;
+        a.tap_ld = slow ? m->Nhead : (m->C - 1) * m->cb;
+        return a;
+    }
+
+    // tail of decode_one_token_ar after the slow forward: sample, fast AR over codebooks
+    void frame_tail(int n, bool ras_enable, bool sample) {
+        if (sample) {
+            SampleArgs a = sargs(true, ras_enable, 0);
+            run_("sample", 0, 0, [&] { launch_sample_radix<T>(s, a, n); });
+        }
+        fast_pass(n, 0, false);  // position 0: fills the fast KV cache, logits discarded
+        for (int cc = 1; cc < m->C; ++cc) {
+            run_("other", 0, 0, [&] {
+                launch_gather_rows<T>(s, m->cols, m->C1, cc, (const T*)m->femb, m->c.fast_dim, m->cb, n, (T*)m->fx);
+            });
+            fast_pass(n, cc, true);
+            if (sample) {
+                SampleArgs a = sargs(false, 0, cc);
+                run_("sample", 0, 0, [&] { launch_sample_radix<T>(s, a, n); });
+            }
+        }
+    }
+
+    void decode_frame(int n) {
+        if (n <= GEMV_MAX_ROWS) {
+            decode_frame_small(n);
+            return;
+        }
+        run_("other", 0, 0, [&] {
+            launch_embed<T>(s, m->tok_in, n, (const T*)m->emb, (const T*)m->cbemb, m->c.dim, m->C, m->cb,
+                            m->c.semantic_begin_id, m->c.semantic_end_id, m->c.scale_codebook_embeddings,
+                            (T*)m->x, m->frame_slot);
+        });
+        rows_distinct_slots = true;
+        bs_frame = true;
+        slow_layers(n, m->frame_slot, m->frame_pos);
+        rows_distinct_slots = false;
+        head_and_hidden(m->x, n);
+        frame_tail(n, true, true);
+        bs_frame = false;
+        chain_flush();
+        launch_finish(s, n, m->frame_slot, m->frame_pos, m->cols, m->C1, m->tok_in, m->ras, m->C1 * 10,
+                      m->C1, 1, m->sp);
+    }
+
+    // runs the prompt through the slow model (chunks), leaves the last row in m->x[row]
+    const void* prefill_slow(int slot, const int32_t* tokens, int Tn, int pos0) {
+        const int C1 = m->C1;
+        std::vector<int32_t> rows((size_t)PREFILL_CHUNK * C1);
+        std::vector<int> rs(PREFILL_CHUNK, slot), rp(PREFILL_CHUNK);
+        int last = 0;
+        for (int t0 = 0; t0 < Tn; t0 += PREFILL_CHUNK) {
+            const int R = std::min(PREFILL_CHUNK, Tn - t0);
+            for (int r = 0; r < R; ++r) {
+                for (int q = 0; q < C1; ++q) rows[(size_t)r * C1 + q] = tokens[(size_t)q * Tn + t0 + r];
+                rp[r] = pos0 + t0 + r;
+            }
+            chain_flush();
+            HIPCHK(hipMemcpyAsync(m->ptok, rows.data(), (size_t)R * C1 * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(m->prow_slot, rs.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(m->prow_pos, rp.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+            launch_embed<T>(s, m->ptok, R, (const T*)m->emb, (const T*)m->cbemb, m->c.dim, m->C, m->cb,
+                            m->c.semantic_begin_id, m->c.semantic_end_id, m->c.scale_codebook_embeddings,
+                            (T*)m->x, nullptr);
+            slow_layers(R, m->prow_slot, m->prow_pos);
+            last = R - 1;
+            HIPCHK(hipStreamSynchronize(s));  // host vectors reused by the next chunk
+        }
+        return (const char*)m->x + (size_t)last * m->c.dim * E;
+    }
+
+    // Several prompts (one slot each, positions from pos0[i], or from 0) through the slow stack together: their rows
+    // packed into PREFILL_CHUNK-row chunks, so every linear is one GEMM over all of them (a prompt
+    // may span chunks: its earlier rows are in the KV cache by then); the attention runs per prompt
+    // segment (segs); the last row of prompt i is copied to plast row i.
+    void prefill_multi(int n, const int32_t* slots, const int32_t* const* toks, const int* Ts, const int* pos0) {
+        const int C1 = m->C1, dim = m->c.dim;
+        std::vector<int32_t> rows((size_t)PREFILL_CHUNK * C1);
+        std::vector<int> rs(PREFILL_CHUNK), rp(PREFILL_CHUNK);
+        int i = 0, t = 0;  // next (prompt, position) to place
+        while (i < n) {
+            int R = 0;
+            segs.clear();
+            std::vector<std::array<int, 2>> lasts;  // (prompt, row) of prompts ending in this chunk
+            while (R < PREFILL_CHUNK && i < n) {
+                const int take = std::min(PREFILL_CHUNK - R, Ts[i] - t);
+                segs.push_back({R, take});
+                for (int r = 0; r < take; ++r) {
+                    for (int q = 0; q < C1; ++q) rows[(size_t)(R + r) * C1 + q] = toks[i][(size_t)q * Ts[i] + t + r];
+                    rs[R + r] = slots[i];
+                    rp[R + r] = (pos0 ? pos0[i] : 0) + t + r;
+                }
+                R += take;
+                t += take;
+                if (t == Ts[i]) {
+                    lasts.push_back({i, R - 1});
+                    ++i;
+                    t = 0;
+                }
+            }
+            chain_flush();
+            HIPCHK(hipMemcpyAsync(m->ptok, rows.data(), (size_t)R * C1 * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(m->prow_slot, rs.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(m->prow_pos, rp.data(), (size_t)R * 4, hipMemcpyHostToDevice, s));
+            launch_embed<T>(s, m->ptok, R, (const T*)m->emb, (const T*)m->cbemb, dim, m->C, m->cb,
+                            m->c.semantic_begin_id, m->c.semantic_end_id, m->c.scale_codebook_embeddings,
+                            (T*)m->x, nullptr);
+            slow_layers(R, m->prow_slot, m->prow_pos);
+            chain_flush();
+            for (const auto& l : lasts)
+                HIPCHK(hipMemcpyAsync((char*)m->plast + (size_t)l[0] * dim * E, (const char*)m->x + (size_t)l[1] * dim * E,
+                                      (size_t)dim * E, hipMemcpyDeviceToDevice, s));
+            segs.clear();
+            HIPCHK(hipStreamSynchronize(s));  // host vectors reused by the next chunk
+        }
+    }
+};
+
+template <typename F> static int with_prec(fm_llm* m, F&& f) {
+    if (m->prec == FM_PREC_BF16) {
+        Run<bf16_t> r(m);
+        f(r);
+        r.chain_flush();
+    } else {
+        Run<float> r(m);
+        f(r);
+        r.chain_flush();
+    }
+    return 0;
+}
+
+// fm_tune rowgemv bit 5: (re)build the table of the first fast layer's raw q|k|v rows, one launch of
+// block_small's own first-layer QKV helper per code (Run::qkv_first: the kernel the frame would run, on
+// the row fast_embeddings[code]), so the table holds the bytes that launch would have written.  Built at
+// load time and again whenever an fm_tune call since could have changed the helper's kernel (the tuning
+// epoch); never inside a capture.  bf16 unquantised models only: bits 5 / 6 are inert for int8 / int4.
+void ensure_qkv0(fm_llm* m) {
+    FmTuning& t = fm_tuning();
+    if (!m->finalized || m->prec != FM_PREC_BF16 || m->quant || !(t.rowgemv & 32) || !m->fxt || m->C < 2 ||
+        !t.fattn_wo || t.gemv_chain || m->fast.empty())
+        return;
+    if (m->qkv0_built && m->qkv0_epoch == t.epoch) return;
+    const StackDims& d = m->fdm;
+    if (!m->qkv0) {
+        m->qkv0 = m->dalloc((size_t)m->cb * d.nqkv() * sizeof(bf16_t), false);
+        std::vector<int32_t> io((size_t)m->cb);
+        for (size_t i = 0; i < io.size(); ++i) io[i] = (int32_t)i;
+        m->qkv0_iota = (int32_t*)m->dalloc(io.size() * sizeof(int32_t), false);
+        HIPCHK(hipMemcpy(m->qkv0_iota, io.data(), io.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    // the build's launches are neither profiled nor recorded (debug_ts, fm_llm_profile)
+    unsigned long long* dbg = t.dbg;
+    const bool prof_on = m->prof.on;
+    t.dbg = nullptr;
+    m->prof.on = false;
+    try {
+        Run<bf16_t> r(m);
+        const GemvArgs<bf16_t> a = r.qkv_args(d, m->fast[0], 1);
+        for (int code = 0; code < m->cb; ++code)
+            r.qkv_first(d, m->fast[0], a, 1, m->femb, m->c.fast_dim, m->qkv0_iota, code,
+                        (bf16_t*)m->qkv0 + (size_t)code * d.nqkv(), false);
+        r.chain_flush();
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(m->stream));
+    } catch (...) {
+        t.dbg = dbg;
+        m->prof.on = prof_on;
+        throw;
+    }
+    t.dbg = dbg;
+    m->prof.on = prof_on;
+    m->qkv0_epoch = t.epoch;
+    m->qkv0_built = true;
+}
+
+// one decode frame for the uploaded rows (graph replay when enabled), async
+void launch_frame(fm_llm* m, int n) {
+    ensure_qkv0(m);
+    if (m->use_graph && !m->prof.on) {
+        auto it = m->graphs.find(n);
+        if (it == m->graphs.end()) {
+            hipGraph_t g;
+            HIPCHK(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal));
+            with_prec(m, [&](auto& r) { r.decode_frame(n); });
+            HIPCHK(hipStreamEndCapture(m->stream, &g));
+            hipGraphExec_t ge;
+            HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+            HIPCHK(hipGraphDestroy(g));
+            it = m->graphs.emplace(n, ge).first;
+        }
+        HIPCHK(hipGraphLaunch(it->second, m->stream));
+    } else {
+        with_prec(m, [&](auto& r) { r.decode_frame(n); });
+    }
+}
+
+void decode_frame_eager(fm_llm* m, int n) {
+    with_prec(m, [&](auto& r) { r.decode_frame(n); });
+}
+
+void prefill_frame(fm_llm* m, int slot, const int32_t* tokens, int T, int pos0) {
+    ensure_qkv0(m);
+    with_prec(m, [&](auto& r) {
+        const void* last = r.prefill_slow(slot, tokens, T, pos0);
+        const void* hid = r.head_small(last, false, 1, 1);
+        r.frame_tail_small(1, false, true, hid);
+    });
+}
+
+void prefill_batch_frame(fm_llm* m, int n, const int32_t* slots, const int32_t* const* toks, const int32_t* T,
+                         const int32_t* pos0) {
+    ensure_qkv0(m);
+    with_prec(m, [&](auto& r) {
+        r.prefill_multi(n, slots, toks, T, pos0);
+        if (n <= GEMV_MAX_ROWS) {
+            const void* hid = r.head_small(m->plast, false, n, 1);
+            r.frame_tail_small(n, false, true, hid);
+        } else {
+            r.bs_frame = true;
+            r.head_and_hidden(m->plast, n);
+            r.frame_tail(n, false, true);
+            r.bs_frame = false;
+        }
+    });
+}
+
+void teacher_frame(fm_llm* m, int slot, const int32_t* x, int S, int pos0, const int32_t* next_col, float* lg,
+                   float* hidden, float* fast_logits) {
+    const fm_model_config& c = m->c;
+    ensure_qkv0(m);
+    with_prec(m, [&](auto& r) {
+        const void* last = r.prefill_slow(slot, x, S, pos0);
+        const void* hid = r.head_small(last, false, 1, 1);
+        HIPCHK(hipMemcpyAsync(lg, m->logits, (size_t)m->Nhead * 4, hipMemcpyDeviceToHost, m->stream));
+        if (hidden) {
+            std::vector<uint8_t> hb((size_t)c.fast_dim * m->esz);
+            HIPCHK(hipMemcpyAsync(hb.data(), hid, hb.size(), hipMemcpyDeviceToHost, m->stream));
+            HIPCHK(hipStreamSynchronize(m->stream));
+            for (int i = 0; i < c.fast_dim; ++i) {
+                if (m->esz == 2) {
+                    uint32_t u = ((uint32_t)((uint16_t*)hb.data())[i]) << 16;
+                    memcpy(&hidden[i], &u, 4);
+                } else {
+                    hidden[i] = ((float*)hb.data())[i];
+                }
+            }
+        }
+        if (next_col) {
+            HIPCHK(hipMemcpyAsync(m->cols, next_col, (size_t)m->C1 * 4, hipMemcpyHostToDevice, m->stream));
+            r.fast_small(1, 0, false, hid);
+            for (int cc = 1; cc < m->C; ++cc) {
+                r.fast_small(1, cc, true, hid);
+                if (fast_logits)
+                    HIPCHK(hipMemcpyAsync(fast_logits + (size_t)(cc - 1) * m->cb, m->flogits, (size_t)m->cb * 4,
+                                          hipMemcpyDeviceToHost, m->stream));
+            }
+        }
+    });
+}

@@ -1,0 +1,107 @@
+// fm_tune_table.h -- the one list of the fm_tune developer knobs: FM_KNOB(name, default, accepted values)
+// and the knob's comment.  Everything else is generated from it: the FmTuning fields (fm_kernels.h; in
+// this order, all int), and fm_tune / fm_tune_get (fm_llm_dev.cpp: look the key up, validate, store).
+// Included twice: plainly for the rule vocabulary below, and with FM_KNOB defined for the list.
+// ("debug_ts" is no entry: it allocates FmTuning::dbg and leaves FmTuning::epoch alone.)
+#ifndef FM_TUNE_RULES
+#define FM_TUNE_RULES
+enum { FM_RULE_BOOL, FM_RULE_ANY, FM_RULE_SET, FM_RULE_RANGE, FM_RULE_MULT16 };
+template <typename... V> constexpr int fm_knob_set(V... v) { return (0 | ... | (1 << v)); }
+// accepted values of a knob, as (rule, a, b)
+#define FM_BOOL FM_RULE_BOOL, 0, 0                      /* any value, stored as value != 0 */
+#define FM_ANY FM_RULE_ANY, 0, 0                        /* any value, stored as given */
+#define FM_SET(...) FM_RULE_SET, fm_knob_set(__VA_ARGS__), 0 /* one of the listed values (each 0..30) */
+#define FM_RANGE(lo, hi) FM_RULE_RANGE, lo, hi          /* lo <= value <= hi */
+#define FM_MIN(lo) FM_RULE_RANGE, lo, 0x7fffffff        /* value >= lo */
+#define FM_MULT16 FM_RULE_MULT16, 0, 0                  /* a multiple of 16, >= 16 */
+#define FM_ZERO_OR_MULT16 FM_RULE_MULT16, 1, 0          /* 0, or a multiple of 16 */
+#endif
+
+#ifdef FM_KNOB
+FM_KNOB(gemv_nt, 1, FM_BOOL)               // 1: non-temporal weight loads (each weight byte is read once a frame)
+FM_KNOB(gemv_u, 8, FM_SET(2, 4, 8))        // weight fragments in flight per wave (2, 4 or 8)
+FM_KNOB(gemv_wpb, 4, FM_SET(4, 8))         // waves per block (4 or 8) sharing one 16-row tile
+FM_KNOB(sampler_kth, 1, FM_BOOL)           // sample_fast_kernel: the K-th lane maximum as the wave threshold when its candidates fit (else the radix search)
+FM_KNOB(sampler_fast, 1, FM_BOOL)          // 1: two-stage register top-K sampler, 0: LDS radix-select sampler
+FM_KNOB(attn_cap, 32, FM_ZERO_OR_MULT16)   // slow decode attention rows per block cap (0: the LDS-budget maximum)
+FM_KNOB(attn_wo, 0, FM_BOOL)               // 1: fast-model attention recomputed in the Wo GEMV's prologue (PRO_FATT, R == 1; measured 0.37 ms/frame slower)
+FM_KNOB(ksb_blocks, 512, FM_MIN(1))        // split K until the grid has at least this many blocks
+FM_KNOB(batched_fused_attn, 1, FM_BOOL)    // batched decode (one row per slot): fused QK-norm/RoPE/KV-write attention kernels
+FM_KNOB(attn_cap_batched, 128, FM_ZERO_OR_MULT16)  // rows per block of the batched decode attention (one row per slot)
+FM_KNOB(linear_u32, 4, FM_SET(4, 8))       // linear_kernel weight fragments in flight per wave at 16 < R <= 32 (4 or 8)
+FM_KNOB(linear_fill, 0, FM_MIN(0))         // batched linear_kernel: split K until this many blocks (0: never; measured slower)
+FM_KNOB(attn3, 1, FM_BOOL)                 // 1: slow decode attention on attn_dec3_kernel, 0: attn_decode2_kernel
+FM_KNOB(attn_fd, 1, FM_BOOL)               // 1: slow decode attention on attn_fd_kernel (flash-decode splits) where eligible
+FM_KNOB(fd_min, 32, FM_MULT16)             // attn_fd: minimum positions per split at R <= 8
+FM_KNOB(fd_min_batched, 512, FM_MULT16)    // attn_fd: minimum positions per split at R > 8 (B=32: one split below 512)
+FM_KNOB(fd_nw, 8, FM_SET(4, 8, 16))        // attn_fd at R <= 8: waves per block (4, 8 or 16) ...
+FM_KNOB(fin_ksb, 0, FM_RANGE(0, 8))        // batch-1 wo / w2 (EPI_SLABFIN) split-K factor (0: whole K whenever the x slice fits LDS; at most KSB_MAX)
+FM_KNOB(fd_nw_batched, 4, FM_SET(4, 8, 16))  // attn_fd at R > 8: waves per block (4, 8 or 16)
+FM_KNOB(fd_min16, 256, FM_MULT16)          // ... and splits of at least this many positions (8 or 16 waves; below it
+                                           // one block per kv head, no cross-block combine)
+FM_KNOB(prefill_attn, 1, FM_BOOL)          // 1: prompt-chunk attention on attn_prefill_kernel (bf16, head_dim 128, flash form)
+FM_KNOB(prompt_gemm, 1, FM_BOOL)           // 1: prompt-chunk linears (R > 32) on the codec's LDS-tiled GEMM kernels
+FM_KNOB(prompt_skinny, 1, FM_BOOL)         // prompt linears at 32 < R <= 64 rows (bf16) on prompt_skinny_kernel ...
+FM_KNOB(prompt_skinny_blocks, 256, FM_MIN(1))  // ... with K sliced until its 64-row blocks number >= this
+FM_KNOB(prompt_unroll, 1, FM_BOOL)         // skinny prompt GEMM: the fully unrolled form (5 / 10 / 20-chunk slices)
+FM_KNOB(prompt_qkv_slab, 1, FM_BOOL)       // skinny QKV: slabs summed by qk_rope_cache_kernel (no epilogue launch)
+FM_KNOB(prompt_fin, 1, FM_BOOL)            // skinny wo / w2: slabs finished by finalize_norm with the next RMSNorm
+FM_KNOB(prompt_swiglu, 1, FM_BOOL)         // skinny w1 || w3: the SwiGLU in its split-K epilogue (no separate launch)
+FM_KNOB(prompt_ks_tiles, 384, FM_MIN(1))   // prompt GEMM: split K until ceil(R/128) ceil(N/128) ks reaches this ...
+FM_KNOB(prompt_ks_max, 8, FM_SET(1, 2, 4, 8))  // ... or ks this (fp32 slabs + the conv split-K epilogue)
+FM_KNOB(conv2, 1, FM_BOOL)                 // 1: codec GEMMs on the LDS-staged conv_gemm2_kernel, 0: conv_gemm_kernel
+FM_KNOB(conv_splitk, 1, FM_BOOL)           // 1: small-grid codec GEMMs split K into fp32 slabs + a reduce/epilogue kernel
+FM_KNOB(resunit_cfg, 1, FM_RANGE(0, 2))    // resunit_kernel tile at 192 / 96 channels: 0 (BM 128 / 256, 8 time tiles per wave), 1 (BM 64 / 128, 4 tiles), 2 (128 / 128)
+FM_KNOB(resunit_enc, 1, FM_BOOL)           // 1: the encoder's units (64 / 128 / 256 / 512 channels) fused as well
+FM_KNOB(resunit_384, 1, FM_BOOL)           // 1: the 384-channel stage's units fused too (BM 64, 8 waves)
+FM_KNOB(codec_norm, 1, FM_BOOL)            // 1: the codec transformer's RMSNorms in the wo / w2 split-K epilogues (no rmsnorm launch)
+FM_KNOB(codec_rope, 1, FM_BOOL)            // 1: the codec transformer's RoPE in the wqkv split-K epilogue (no rope_qk launch)
+FM_KNOB(codec_swiglu, 1, FM_BOOL)          // 1: codec FeedForward W1 | W3 as one split-K GEMM with the SwiGLU epilogue
+FM_KNOB(codec_fuse, 1, FM_BOOL)            // 1: decoder ResidualUnits at 96 / 192 / 384 channels as one resunit_kernel launch (k7 + k1)
+FM_KNOB(bstream, 1, FM_BOOL)               // 1: batched decode linears (8 < R <= 32) on bstream_kernel (fm_bstream.hip)
+FM_KNOB(bstream_kparts, 0, FM_SET(0, 1, 2, 4, 8))  // bstream EPI_SLAB K parts (0: by K)
+FM_KNOB(bstream_nw, 0, FM_RANGE(0, 16))    // bstream waves per block (0: 16 whole-K, 8 split-K)
+// ring slots past a wave's run (tail of the decode GEMV ring, bsacc tiles / steps a block does
+// not own): 0 re-load the run's last fragment, 1 one fixed fragment, 2 a fixed fragment per
+// (block, wave) over 256 of them.  B=1 frame 4.447 / 4.47 / 4.398 ms, B=32 6.51 / 6.44 / 6.42 ms
+FM_KNOB(bs_dummy, 2, FM_RANGE(0, 2))
+FM_KNOB(gemv_dummy, 2, FM_RANGE(0, 2))
+FM_KNOB(bs_qkv_slab, 1, FM_BOOL)           // batched frames: QKV as K-part slabs summed by the attention (balanced
+                                           // grid: 384 tiles x 2 K parts over 256 CUs; B=32 frame 6.48 -> 6.33 ms)
+FM_KNOB(fast_tail, 1, FM_BOOL)             // 1: codebook 0's fast pass stops its last layer after the K / V cache write (its output is discarded)
+FM_KNOB(fkv_prefetch, 0, FM_BOOL)          // 1: the batch-1 fast-model QKV GEMV pulls the fast attention's cached rows into L2 too
+FM_KNOB(kv_prefetch, 1, FM_BOOL)           // 1: the batch-1 QKV GEMV pulls the next attention's K / V rows into L2
+FM_KNOB(bstream_chain, 0, FM_ANY)          // 1: bsacc SLABFIN / PRENORM chain instead of finalize_norm launches (measured 6.31 -> 6.75 ms per B=32 frame)
+FM_KNOB(bstream_acc, 1, FM_ANY)            // 1: bsacc_kernel (per-tile register accumulators, one reduction at the end, balanced K parts); 0: bstream_kernel
+FM_KNOB(rmsnorm_block, 0, FM_BOOL)         // 1: block-per-row RMSNorm (the pre-vectorisation kernel), 0: wave-per-row when shapes allow
+FM_KNOB(ksb_balance, 0, FM_BOOL)           // 1: prefer grids that are whole multiples of 256 blocks (one per CU)
+FM_KNOB(chain_max, 4, FM_RANGE(2, 4))      // gemv_chain: GEMVs per launch at most (2..GEMV_CHAIN_MAX)
+FM_KNOB(chain_sleep, 4, FM_SET(1, 4, 16))  // gemv_chain: s_sleep argument between a waiting block's polls (1, 4 or 16)
+FM_KNOB(gemv_chain, 0, FM_BOOL)            // 1: batch-1 decode runs wo -> w1||w3 -> w2 -> next qkv as one launch (gemv_chain_kernel)
+FM_KNOB(bs_xfirst, 1, FM_BOOL)             // bsacc: X operands before the weight ring (B=32 frame 6.48 -> 6.36 ms)
+FM_KNOB(bs_vec_epi, 1, FM_BOOL)            // bsacc: 4-row epilogue items (bit-identical to the scalar epilogue; B=32 frame 6.31 -> 6.18 ms)
+FM_KNOB(bsacc_kparts, 0, FM_SET(0, 1, 2, 4, 8))  // developer: force the K parts of the batched split-K (slab) linears (0: bsacc_plan's pick)
+FM_KNOB(q_u, 4, FM_SET(2, 4, 8, 16))       // int8 / int4 decode GEMV: ring units in flight per wave (2, 4, 8, 16; int8 frame 3.79 -> 3.59 ms at 8 -> 4)
+FM_KNOB(fin8, 1, FM_BOOL)                  // finalize_norm: all eight K parts' slab loads in one round trip (0: two batches of four)
+FM_KNOB(fin_split, 0, FM_RANGE(0, 16))     // batched finalize_norm: each row over this many blocks (0 / 1: one block per row)
+FM_KNOB(bstream_q8, 1, FM_BOOL)            // weight-only int8, 8 < R <= 32: 1 bsacc_kernel streams the int8 codes, 0 their bf16 fragment copy
+                                           // (bit-identical; int8 B=32 frame 6.441 -> 5.761 ms, the bf16 model's 6.184; profiles/b32_int8.md)
+FM_KNOB(int4_stream, 1, FM_BOOL)           // weight-only int4: 1 the batch <= 8 GEMVs stream the 4-bit codes, 0 the dequantised bf16 copy
+FM_KNOB(fw_delay, 0, FM_RANGE(0, 1000))    // fattn_wo: FattnWoArgs::delay (10-ns ticks)
+FM_KNOB(fw_cheap, 0, FM_BOOL)              // fattn_wo: FattnWoArgs::cheap
+FM_KNOB(fw_prio, 0, FM_BOOL)               // fattn_wo: FattnWoArgs::prio
+FM_KNOB(fattn_wo, 1, FM_BOOL)              // 1: batch-1 bf16 fast-model attention + wo as one launch (fm_rowgemv.hip fattn_wo_kernel)
+FM_KNOB(fattn_ilp, 1, FM_BOOL)             // 1: fattn_wo_kernel's attention chain without serial blocks: q / k prep chains side by side, score /
+                                           // softmax / PV over a compile-time position count, the softmax one position per lane (bit-identical
+                                           // to 0, the early-exit loops)
+FM_KNOB(row_qkv_rp, 8, FM_SET(4, 8, 16))   // developer: rows per block of the bf16 row-block wqkv (4, 8 or 16)
+FM_KNOB(rowgemv_q4, 31, FM_RANGE(0, 31))   // rowgemv's bits for weight-only int4 models (w1 || w3 too: int4 frame 3.06 -> 3.01 ms; bf16 4.07 -> 4.10, int8 3.11 -> 3.20 with it)
+FM_KNOB(rowgemv, 123, FM_RANGE(0, 127))    // batch-1 decode linears on the row-block GEMV (fm_rowgemv.hip): bit 0 wo / w2, bit 1 wqkv, bit 2 w1 || w3,
+                                           // bit 3 the codebook head, bit 4 the first layers' wqkv (0: 16-row MFMA tiles; 3 -> 27: 4.066 -> 4.032 ms);
+                                           // bit 5: the first fast layer's QKV at codebooks >= 1 read from a table of its codebook_size possible
+                                           // rows (no launch); bit 6: at codebook 0 the fast layers compute K / V only (one position: attention = v)
+FM_KNOB(row_copies, 1, FM_BOOL)            // 1: fm_llm_finalize keeps a row-major copy of every linear the row-block GEMV can take, so any
+                                           // rowgemv bits work later (bf16 S2-Pro: ~3.7 GB beside the packed tiles); 0: only the copies the
+                                           // rowgemv / rowgemv_q4 bits in force at finalize select (w1 || w3 bf16 / int8: ~3.6 GB saved)
+FM_KNOB(prefix_vec, 1, FM_BOOL)            // voice prefix copy (fm_prefix.hip): 1 16-byte accesses where the runs allow, 0 the scalar path
+#endif

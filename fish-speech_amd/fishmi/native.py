@@ -23,7 +23,7 @@ _lib = None
 ABI_SYMBOLS = [
     "fm_device_count", "fm_last_error", "fm_stream_peak", "fm_llm_open", "fm_llm_set_quant", "fm_llm_set_quant_int4", "fm_llm_set_tensor", "fm_llm_synth_tensor",
     "fm_llm_finalize", "fm_llm_prefill", "fm_llm_prefill_batch", "fm_llm_decode", "fm_llm_decode_frames", "fm_llm_generate", "fm_llm_generate_at", "fm_llm_prefill_at", "fm_llm_slot_pos", "fm_llm_teacher_step",
-    "fm_llm_frame_bytes", "fm_llm_profile", "fm_llm_profile_read", "fm_llm_kernel_bench", "fm_llm_use_graph", "fm_llm_debug_vec", "fm_tune", "fm_debug_ts_read",
+    "fm_llm_frame_bytes", "fm_llm_profile", "fm_llm_profile_read", "fm_llm_kernel_bench", "fm_llm_use_graph", "fm_llm_debug_vec", "fm_tune", "fm_tune_get", "fm_debug_ts_read",
     "fm_llm_close", "fm_source_hash", "fm_codec_open", "fm_codec_set_tensor", "fm_codec_synth_tensor",
     "fm_codec_finalize", "fm_codec_decode", "fm_codec_stream_reset", "fm_codec_decode_chunk",
     "fm_codec_stream_open", "fm_codec_stream_decode", "fm_codec_stream_rewind", "fm_codec_stream_close",
@@ -138,6 +138,7 @@ def lib():
     L.fm_llm_use_graph.argtypes = [vp, i32]
     L.fm_llm_debug_vec.argtypes = [vp, ctypes.c_char_p, i32, pf32, i64]
     L.fm_tune.argtypes = [ctypes.c_char_p, i32]
+    L.fm_tune_get.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)]
     L.fm_debug_ts_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), i64, ctypes.POINTER(ctypes.c_int64)]
     L.fm_llm_close.argtypes = [vp]
     L.fm_llm_force.argtypes = [vp, i32, pi32]
@@ -206,6 +207,13 @@ def f32p(a: np.ndarray):
 def tune(key: str, value: int):
     """Process-wide developer knob of the decode GEMV (see fm_tune in include/fishmi.h)."""
     check(lib().fm_tune(key.encode(), int(value)))
+
+
+def tune_get(key: str) -> int:
+    """The value of a developer knob now in force (its default, a FISHMI_TUNE setting or the last tune())."""
+    v = ctypes.c_int(0)
+    check(lib().fm_tune_get(key.encode(), ctypes.byref(v)))
+    return v.value
 
 
 def debug_ts_read(max_records: int = 1 << 20) -> np.ndarray:

@@ -215,17 +215,13 @@ int fm_llm_debug_vec(fm_llm* h, const char* name, int index, float* out, int64_t
 int fm_llm_force(fm_llm* h, int slot, const int32_t* col);
 int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logits);
 /* process-wide developer knobs selecting kernel variants (every variant stays under the default
-   path's parity bar, tests/test_gpu_knobs.py): decode GEMV "gemv_nt" 0|1, "gemv_u" 2|4|8,
-   "gemv_wpb" 4|8, "ksb_blocks" n, "ksb_balance" 0|1, "fin_ksb" n, "kv_prefetch" 0|1, "gemv_dummy" 0|1|2, "gemv_chain" 0|1,
-   "chain_max" 2..4, "chain_sleep" 1|4|16; attention "attn_fd" 0|1, "attn3" 0|1,
-   "attn_cap" n, "attn_cap_batched" n, "fd_min" n, "fd_min_batched" n, "fd_nw" 4|8|16, "fd_min16" n,
-   "fd_nw_batched" 4|8|16, "attn_wo" 0|1,
-   "batched_fused_attn" 0|1; batched linears "bstream" 0|1, "bstream_acc" 0|1, "bstream_chain" 0|1, "bstream_kparts" n, "bstream_nw" n, "bs_dummy" 0|1|2, "bs_qkv_slab" 0|1,
-   "bs_xfirst" 0|1, "bs_vec_epi" 0|1, "bstream_q8" 0|1 (weight-only int8 bf16 models opened with more than
-   8 slots: 1, the default, the batched decode linears stream the int8 codes -- bit-identical
-   outputs, half the weight bytes -- 0 the bf16 copy of the codes; inert for every other model),
-   "linear_u32" n, "linear_fill" n; prompt "prefill_attn", "prompt_gemm"; voice prefix copy "prefix_vec" 0|1; codec "conv2",
-   "conv_splitk"; "sampler_fast" 0|1, "rmsnorm_block" 0|1, "debug_ts" n; batch-1 row-block GEMV
+   path's parity bar, tests/test_gpu_knobs.py).  The keys, their defaults and their accepted values
+   are the entries of fish-speech_amd/csrc/fm_tune_table.h, plus "debug_ts" n (arms the records of
+   fm_debug_ts_read); an unknown key or a value outside the accepted ones fails with FM_ERR_ARG.
+   fm_tune_get reads the value in force ("debug_ts": whether it is armed).
+   "bstream_q8" 0|1 (weight-only int8 bf16 models opened with more than 8 slots: 1, the default, the
+   batched decode linears stream the int8 codes -- bit-identical outputs, half the weight bytes -- 0
+   the bf16 copy of the codes; inert for every other model).
    "rowgemv" / "rowgemv_q4" bits, "row_copies" 0|1 (0: finalize keeps only the row-major weight
    copies those bits select).  "rowgemv" 0..127, default 123: bits 0-4 put wo / w2, wqkv, w1 || w3,
    the codebook head and the first layers' wqkv on the row-block GEMV; bit 5 (32): the first fast
@@ -235,11 +231,13 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    frame after any fm_tune call but "debug_ts") instead of being launched; bit 6 (64): at codebook
    0, where the fast attention has one position and its output is v, the fast layers project K / V
    only and the attention reads no Q.  Bits 5 and 6 change no output bit (finite scores); they act
-   on bf16 unquantised models, batch 1, and are inert elsewhere.  They apply to launches
-   recorded after the call (graphs captured earlier keep theirs).  "fattn_ilp" 0|1 (default 1: the
-   fused fast attention + wo launch runs its q / k preparation and score / softmax / PV over a
-   compile-time position count in one basic block) changes no output bit either. */
+   on bf16 unquantised models, batch 1, and are inert elsewhere.  Knobs apply to launches
+   recorded after the call (graphs captured earlier keep theirs; fm_llm_use_graph drops them).
+   "fattn_ilp" 0|1 (default 1: the fused fast attention + wo launch runs its q / k preparation and
+   score / softmax / PV over a compile-time position count in one basic block) changes no output
+   bit either. */
 int fm_tune(const char* key, int value);
+int fm_tune_get(const char* key, int* value);
 /* developer hook ("debug_ts" armed): per-block records of 8 words {tag = N<<32 | blockIdx.y<<16 |
    blockIdx.x, start, staged, streamed, end, 3 kernel-specific} of the decode GEMVs,
    s_memrealtime ticks (100 MHz). */

@@ -4,9 +4,45 @@ The bf16 bound: the build's bf16 error against the reference's fp32 logits (same
 teacher-forced stream) may be at most BF16_RATIO x the reference's OWN bf16-vs-fp32 error, in RMS
 and in max, over the whole stream; top-1 must agree wherever the fp32 top-1/top-2 margin exceeds
 twice the larger of the bf16 errors (both builds' argmax are then pinned)."""
+import contextlib
+
 import numpy as np
+import pytest
 
 BF16_RATIO = 1.5
+
+
+@pytest.fixture
+def knob():
+    """put(key, value): set a process-wide fm_tune knob for this test.  Afterwards every knob the test
+    touched goes back to the value that was in force before its first put (read with tune_get: the
+    default, or whatever FISHMI_TUNE set) -- test modules import this fixture by name."""
+    from fishmi import native
+
+    saved = {}
+
+    def put(key, value):
+        saved.setdefault(key, native.tune_get(key))
+        native.tune(key, value)
+
+    yield put
+    for k, v in saved.items():
+        native.tune(k, v)
+
+
+@contextlib.contextmanager
+def tuned(**knobs):
+    """with tuned(key=value, ...): the knob fixture's save-and-restore around a block (helpers, loops)."""
+    from fishmi import native
+
+    saved = {k: native.tune_get(k) for k in knobs}
+    for k, v in knobs.items():
+        native.tune(k, v)
+    try:
+        yield
+    finally:
+        for k, v in saved.items():
+            native.tune(k, v)
 
 
 def bits_to_f32(b):

@@ -21,7 +21,7 @@ import json
 import numpy as np
 import pytest
 
-from parity_util import bf16_vs_golden, bf16_vs_reference, bits_to_f32
+from parity_util import bf16_vs_golden, bf16_vs_reference, bits_to_f32, knob  # noqa: F401  (knob: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -127,21 +127,6 @@ def test_long_context_4_layers_bf16_vs_reference(golden):
 _RAGGED_LOGITS = {}  # (prefill, chain, slab) -> the default forms' logits (the older-forms case compares)
 
 
-@pytest.fixture
-def knob():
-    from fishmi import native
-
-    set_ = {}
-
-    def put(key, value, default):
-        set_[key] = default
-        native.tune(key, value)
-
-    yield put
-    for k, d in set_.items():
-        native.tune(k, d)
-
-
 @pytest.mark.parametrize("prefill,chain,slab,older", [("batch", 0, 1, 0), ("single", 0, 1, 0), ("batch", 1, 1, 0),
                                                       ("batch", 0, 0, 0), ("batch", 0, 1, 1)])
 def test_config3_ragged_32_slots_bf16_vs_reference(prefill, chain, slab, older, golden, knob):
@@ -156,10 +141,10 @@ def test_config3_ragged_32_slots_bf16_vs_reference(prefill, chain, slab, older, 
     default's bit for bit (same loads, same fp32 sums in the same order)."""
     from fishmi.llm import DualARModel
 
-    knob("bstream_chain", chain, 0)
-    knob("bs_qkv_slab", slab, 1)
-    knob("bs_xfirst", 1 - older, 1)
-    knob("bs_vec_epi", 1 - older, 1)
+    knob("bstream_chain", chain)
+    knob("bs_qkv_slab", slab)
+    knob("bs_xfirst", 1 - older)
+    knob("bs_vec_epi", 1 - older)
     g = golden("llm_ragged_bf16.npz")
     cfg = _cfg(g)
     B = int(g["lens"].size)

@@ -9,7 +9,7 @@ import json
 import numpy as np
 import pytest
 
-from parity_util import bf16_vs_golden
+from parity_util import bf16_vs_golden, knob  # noqa: F401  (knob: the shared fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,20 +25,15 @@ def _cfg(g):
 
 
 @pytest.fixture
-def chain():
+def chain(knob):
     """gemv_chain on / off against the 16-row tile launch chain it replaces: the row-block GEMVs
     (rowgemv) and the fused fast attention + wo (fattn_wo) are off in both runs."""
-    from fishmi import native
-
     def put(on):
-        native.tune("gemv_chain", int(on))
+        knob("gemv_chain", int(on))
 
-    native.tune("rowgemv", 0)
-    native.tune("fattn_wo", 0)
-    yield put
-    native.tune("gemv_chain", 0)
-    native.tune("rowgemv", 27)
-    native.tune("fattn_wo", 1)
+    knob("rowgemv", 0)
+    knob("fattn_wo", 0)
+    return put
 
 
 def _prompt(cfg, T, seed):

@@ -13,6 +13,8 @@ import json
 import numpy as np
 import pytest
 
+from parity_util import tuned
+
 pytestmark = pytest.mark.gpu
 
 
@@ -26,13 +28,8 @@ def _codec(golden, max_frames):
 
 
 def _both(m, f, knob="codec_fuse"):
-    from fishmi import native
-
-    native.tune(knob, 0)
-    try:
+    with tuned(**{knob: 0}):
         two = f()
-    finally:
-        native.tune(knob, 1)
     return f(), two
 
 
@@ -80,7 +77,6 @@ def test_fused_random_ragged(golden):
 def test_fused_encoder_units_equal_two_launch(golden):
     """The encoder's ResidualUnits (64 / 128 / 256 / 512 channels at codec_enc_full's widths) run
     the same fused kernel: z_enc and the codes bit-identical to the two-launch form, bf16."""
-    from fishmi import native
     from fishmi.codec import FishMICodec
     from fishmi.config import CodecConfig
 
@@ -96,11 +92,8 @@ def test_fused_encoder_units_equal_two_launch(golden):
         codes = m.encode_audio(g["audio"])
         return codes, m.debug_read(10, codes.shape[1])
 
-    native.tune("resunit_enc", 0)
-    try:
+    with tuned(resunit_enc=0):
         c0, z0 = run()
-    finally:
-        native.tune("resunit_enc", 1)
     c1, z1 = run()
     np.testing.assert_array_equal(z1, z0)
     np.testing.assert_array_equal(c1, c0)
@@ -149,15 +142,11 @@ def test_norm_in_residual_epilogue_equals_rmsnorm_kernel(golden):
 def test_fused_tile_variants_equal_two_launch(cfg, golden):
     """The non-default resunit tile variants (fm_tune resunit_cfg 0: BM 128 / 256 with 8 time tiles
     per wave; 2: BM 128 at both widths) are bit-identical to the two-launch form as well."""
-    from fishmi import native
 
     m, g = _codec(golden, 216)
     codes = g["codes"][0]
-    native.tune("resunit_cfg", cfg)
-    try:
+    with tuned(resunit_cfg=cfg):
         fused, two = _both(m, lambda: m.decode_codes(codes))
-    finally:
-        native.tune("resunit_cfg", 1)
     np.testing.assert_array_equal(fused, two)
     m.close()
 

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from parity_util import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -162,7 +163,6 @@ def test_decode_written_kv_rows(golden, tmp_path):
     thousands of ulps from layer 1 on.  (2) With the prompt linears on the GEMV-order linear kernel
     (fm_tune prompt_gemm 0) the rows are bit-identical; with the default LDS-tiled prompt GEMM, whose
     K accumulation order differs, at most a few elements differ, by at most 2 bf16 ulps."""
-    from fishmi import native
     from fishmi.llm import DualARModel
 
     gl = golden("llm_a_bf16.npz")
@@ -196,17 +196,14 @@ def test_decode_written_kv_rows(golden, tmp_path):
                   for x, y in d)
         return cnt, ulp, sum(x.size for x, _ in d)
 
-    try:
-        a1 = decode_rows()
-        a2 = decode_rows()
-        assert diff(a1, a2)[0] == 0, "decode-written K / V rows differ between two identical runs"
-        cnt, ulp, tot = diff(a1, prompt_rows())
-        print(f"default prompt GEMM: {cnt} of {tot} decode-written elements differ (max {ulp} ulp)")
-        assert cnt <= tot // 100 and ulp <= 2
-        native.tune("prompt_gemm", 0)
+    a1 = decode_rows()
+    a2 = decode_rows()
+    assert diff(a1, a2)[0] == 0, "decode-written K / V rows differ between two identical runs"
+    cnt, ulp, tot = diff(a1, prompt_rows())
+    print(f"default prompt GEMM: {cnt} of {tot} decode-written elements differ (max {ulp} ulp)")
+    assert cnt <= tot // 100 and ulp <= 2
+    with tuned(prompt_gemm=0):
         assert diff(decode_rows(), prompt_rows())[0] == 0
-    finally:
-        native.tune("prompt_gemm", 1)
 
 
 def test_worker_queue_contract(golden, tmp_path):

@@ -10,6 +10,7 @@ import dataclasses
 import numpy as np
 import pytest
 
+from parity_util import knob  # noqa: F401  (fixture)
 from test_gpu_fast_deadwork import _forced
 from test_gpu_llm import _bf16_vs_reference, _cfg
 from test_gpu_rowgemv import FW_TAG, _biased_cfg, _row_blocks_ran
@@ -21,14 +22,11 @@ NF = 7  # teacher-forced frames: the prefill's frame + 6 decoded ones
 
 
 @pytest.fixture
-def knobs():
-    from fishmi import native
-
+def knobs(knob):
     def set_(ilp):
-        native.tune("fattn_ilp", ilp)
+        knob("fattn_ilp", ilp)
 
-    yield set_
-    native.tune("fattn_ilp", 1)
+    return set_
 
 
 def _layout_cfg(layout, codebooks=10):

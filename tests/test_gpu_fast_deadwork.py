@@ -10,26 +10,24 @@ import dataclasses
 import numpy as np
 import pytest
 
+from parity_util import knob  # noqa: F401  (fixture)
 from test_gpu_llm import _bf16_vs_reference, _cfg
 from test_gpu_rowgemv import FW_TAG, ROW_TAG, _biased_cfg, _row_blocks_ran
 
 pytestmark = pytest.mark.gpu
 
-DEFAULT = 123
 SETTINGS = (27, 59, 91, 123)
 NF = 7  # teacher-forced frames: the prefill's frame + 6 decoded ones
 
 
 @pytest.fixture
-def rowgemv():
-    from fishmi import native
-
+def rowgemv(knob):
+    """set_(v): the rowgemv bits; set_.knob: the shared fixture, for the other knobs a test sets"""
     def set_(v):
-        native.tune("rowgemv", v)
+        knob("rowgemv", v)
 
-    yield set_
-    native.tune("rowgemv", DEFAULT)
-    native.tune("row_qkv_rp", 8)
+    set_.knob = knob
+    return set_
 
 
 def _variant_cfg(variant):
@@ -171,7 +169,7 @@ def test_wide_bf16_vs_reference_under_default(golden, rowgemv):
     bf16 bound of the reference, as test_wide_bf16_variants_vs_reference checks the other knobs."""
     from fishmi.llm import DualARModel
 
-    rowgemv(DEFAULT)
+    rowgemv(123)  # the default, whatever the process runs under
     g = golden("llm_wide_bf16.npz")
     cfg = _cfg("llm_wide")
     m = DualARModel.synthetic(cfg, int(g["synth_seed"]), int(g["log2_half"]), 0, "bf16", 1)
@@ -186,7 +184,6 @@ def test_wide_bf16_vs_reference_under_default(golden, rowgemv):
 def test_table_follows_the_kernel_it_is_built_with(rowgemv):
     """row_qkv_rp picks another wqkv kernel (4, then 8 rows per block): with bit 5 on, the table is
     rebuilt under each value and the logits equal the bit-5-off logits of the same value."""
-    from fishmi import native
     from fishmi.llm import DualARModel
 
     cfg = _variant_cfg("a")
@@ -197,7 +194,7 @@ def test_table_follows_the_kernel_it_is_built_with(rowgemv):
             out = {}
             for v in (123, 91):
                 rowgemv(v)
-                native.tune("row_qkv_rp", rp)
+                rowgemv.knob("row_qkv_rp", rp)
                 m.use_graph(True)
                 out[v] = _forced(m, prompt, cols[:, :4])
             for a, b in zip(out[91], out[123]):

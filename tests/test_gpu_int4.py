@@ -7,7 +7,7 @@ MI355X box: pytest -m gpu."""
 import numpy as np
 import pytest
 
-from parity_util import bits_to_f32
+from parity_util import bits_to_f32, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -69,7 +69,6 @@ def test_int4_model_stream_matches_dequantized_model(golden, rowgemv):
     (int4_stream 0) -- logits equal up to
     the rounding of the dequantised weights (the streamed form applies the affine map exactly, the
     copy holds it rounded to bf16); and the int4 model tracks the bf16 model (quantization error only)."""
-    from fishmi import native
     from fishmi.config import DualARConfig
     from fishmi.llm import DualARModel
 
@@ -85,15 +84,12 @@ def test_int4_model_stream_matches_dequantized_model(golden, rowgemv):
     m = DualARModel.synthetic(cfg, int(g["synth_seed"]), int(g["log2_half"]), 0, "bf16", 1, quant="int4",
                               groupsize=128)
     out = {}
-    native.tune("rowgemv_q4", rowgemv)
     try:
         for st in (1, 0):
-            native.tune("int4_stream", st)
-            m.use_graph(True)
-            out[st] = m.teacher_decode(g["prompt"], cols)
+            with tuned(rowgemv_q4=rowgemv, int4_stream=st):
+                m.use_graph(True)
+                out[st] = m.teacher_decode(g["prompt"], cols)
     finally:
-        native.tune("int4_stream", 1)
-        native.tune("rowgemv_q4", 31)
         m.close()
     mb = DualARModel.synthetic(cfg, int(g["synth_seed"]), int(g["log2_half"]), 0, "bf16", 1)
     try:

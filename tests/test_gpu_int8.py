@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from parity_util import tuned
 from test_gpu_llm import IM_END, _bf16_vs_reference, _cfg
 
 pytestmark = pytest.mark.gpu
@@ -74,7 +75,6 @@ def test_int8_batched_slots_match_single(n, bstream, golden):
     """int8 at B <= 8 (gemv_kernel int8 stream), 8 < B <= 32 on bstream_kernel (scales in the
     epilogues and in finalize_norm) or linear_kernel: every slot's stream == its batch-1 stream, and
     slot 0 (the golden prompt) == the reference int8 model's (fp32 mode)."""
-    from fishmi import native
     from fishmi.llm import DualARModel
 
     g = golden("llm_q_int8_fp32.npz")
@@ -88,14 +88,11 @@ def test_int8_batched_slots_match_single(n, bstream, golden):
             p[0, 1:5] = rng.integers(16, cfg.semantic_begin_id, 4)
         prompts.append(p)
     n_new = 10
-    native.tune("bstream", bstream)
-    try:
+    with tuned(bstream=bstream):
         single = [m.generate(p, n_new, top_k=1, slot=s, mask_im_end=True) for s, p in enumerate(prompts)]
         sp = DualARModel.sampling(top_k=1, mask_im_end=True)
         firsts = [m.prefill(s, p, sp) for s, p in enumerate(prompts)]
         fr = m.decode_frames(list(range(n)), n_new - 1)
-    finally:
-        native.tune("bstream", 1)
     T = g["prompt"].shape[1]
     np.testing.assert_array_equal(single[0], g["seq"][:, T:T + n_new])
     for s in range(n):
@@ -109,14 +106,10 @@ def test_int8_wide_real_widths_vs_reference(golden, rowgemv):
     the synthetic bf16 weights quantized on the device, bf16 production decode path teacher-forced
     with the reference int8 model's columns: within BF16_RATIO x its own bf16 error -- with wo / w2
     on the int8 row-block GEMV (fm_rowgemv.hip QM 1, the default) and on the 16-row tiles."""
-    from fishmi import native
     from fishmi.llm import DualARModel
 
-    native.tune("rowgemv", rowgemv)
-    try:
+    with tuned(rowgemv=rowgemv):
         _int8_wide(golden)
-    finally:
-        native.tune("rowgemv", 27)
 
 
 def _int8_wide(golden):

@@ -9,11 +9,11 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from parity_util import tuned
 from test_gpu_llm import IM_END, _bf16_vs_reference, _cfg
 
 pytestmark = pytest.mark.gpu
 
-Q8_DEFAULT = 1  # FmTuning::bstream_q8's default: restored after every test (the knob is process-wide)
 
 
 def _prompts(g, cfg, n):
@@ -41,13 +41,9 @@ def _linear_bytes(m, slots):
 def _tiny_run(g, prec, n, q8, extra=None):
     """A fresh llm_q_int8 model with the knob set before its first frame: greedy mask_im_end prefill +
     8 decode_frames of n slots, then one frame with slot 0 forced (its logits), then one profiled frame."""
-    from fishmi import native
     from fishmi.llm import DualARModel
 
-    for k, v in (extra or {}).items():
-        native.tune(k, v)
-    native.tune("bstream_q8", q8)
-    try:
+    with tuned(bstream_q8=q8, **(extra or {})):
         m = DualARModel.from_pretrained(os.path.join(GOLDEN, "llm_q_int8"), 0, prec, n, im_end_id=IM_END)
         assert m.quant == "int8"
         slots = list(range(n))
@@ -64,10 +60,6 @@ def _tiny_run(g, prec, n, q8, extra=None):
             m.force(0, None)
         b = _linear_bytes(m, slots)
         m.close()
-    finally:
-        native.tune("bstream_q8", Q8_DEFAULT)
-        for k in (extra or {}):
-            native.tune(k, 1)
     return cols, slow, fast, b
 
 
@@ -111,7 +103,6 @@ def _wide_runs(golden):
     (so every frame is the batched one), then one profiled frame.  Computed once, shared by the tests."""
     if _WIDE:
         return _WIDE
-    from fishmi import native
     from fishmi.llm import DualARModel
 
     path = os.path.join(GOLDEN, "llm_wide_int8_bf16.npz")
@@ -126,8 +117,7 @@ def _wide_runs(golden):
     nf = cols.shape[1]
     runs = {}
     for q8 in (0, 1):
-        native.tune("bstream_q8", q8)
-        try:
+        with tuned(bstream_q8=q8):
             m = DualARModel.synthetic(cfg, int(g["synth_seed"]), int(g["log2_half"]), 0, "bf16", n, quant="int8")
             slow = np.zeros((nf, cfg.vocab_size), np.float32)
             fast = np.zeros((nf, cfg.num_codebooks - 1, cfg.codebook_size), np.float32)
@@ -145,8 +135,6 @@ def _wide_runs(golden):
                 m.force(0, None)
             runs[q8] = (slow, fast, _linear_bytes(m, slots))
             m.close()
-        finally:
-            native.tune("bstream_q8", Q8_DEFAULT)
     _WIDE.update(g=g, cfg=cfg, runs=runs)
     return _WIDE
 

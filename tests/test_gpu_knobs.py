@@ -10,15 +10,10 @@ import json
 import numpy as np
 import pytest
 
+from parity_util import knob  # noqa: F401  (fixture)
 from test_gpu_llm import _bf16_vs_reference, _cfg, _model
 
 pytestmark = pytest.mark.gpu
-
-# FmTuning's defaults (fm_kernels.h), restored after every test
-DEFAULTS = {"attn3": 1, "attn_fd": 1, "fd_min": 32, "fd_nw": 8, "fd_min16": 256, "gemv_chain": 0, "gemv_nt": 1, "gemv_u": 8, "gemv_wpb": 4,
-            "ksb_balance": 0, "ksb_blocks": 512, "attn_cap": 32, "prefill_attn": 1, "prompt_gemm": 1,
-            "conv2": 1, "conv_splitk": 1, "kv_prefetch": 1, "fin_ksb": 0, "gemv_dummy": 2, "rowgemv": 27, "rowgemv_q4": 31, "sampler_kth": 1, "row_qkv_rp": 8,
-            "fattn_wo": 1, "fw_cheap": 0, "fw_delay": 0, "prompt_skinny": 1, "prompt_skinny_blocks": 256, "prompt_swiglu": 1, "prompt_fin": 1, "prompt_qkv_slab": 1, "prompt_unroll": 1}
 
 DECODE_KNOBS = [{"attn3": 0}, {"attn3": 0, "attn_fd": 0}, {"fd_nw": 4}, {"fd_nw": 4, "fd_min": 16}, {"fd_nw": 16},
                 {"fd_min16": 16}, {"fd_nw": 16, "fd_min16": 16}, {"gemv_chain": 1}, {"gemv_nt": 0}, {"gemv_u": 4},
@@ -30,19 +25,12 @@ DECODE_KNOBS = [{"attn3": 0}, {"attn3": 0, "attn_fd": 0}, {"fd_nw": 4}, {"fd_nw"
 
 
 @pytest.fixture
-def tune():
-    from fishmi import native
-
-    touched = []
-
+def tune(knob):
     def put(knobs):
         for k, v in knobs.items():
-            touched.append(k)
-            native.tune(k, v)
+            knob(k, v)
 
-    yield put
-    for k in touched:
-        native.tune(k, DEFAULTS[k])
+    return put
 
 
 def _ids(knobs):
@@ -100,9 +88,9 @@ def test_codec_variants_vs_reference(prec, knobs, golden, tune):
         assert rms(wave - ref) <= 1.5 * ref_bf16_err + 1e-4, (rms(wave - ref), ref_bf16_err)
 
 
-@pytest.mark.parametrize("knob,blocks", [("prompt_swiglu", 1), ("prompt_swiglu", 4096), ("prompt_qkv_slab", 256),
+@pytest.mark.parametrize("key,blocks", [("prompt_swiglu", 1), ("prompt_swiglu", 4096), ("prompt_qkv_slab", 256),
                                           ("prompt_qkv_slab", 4096), ("prompt_unroll", 256), ("prompt_unroll", 1)])
-def test_prompt_fusions_bit_identical(golden, tune, knob, blocks):
+def test_prompt_fusions_bit_identical(golden, tune, key, blocks):
     """The skinny prompt GEMM's fused epilogues give the teacher-forced logits of the unfused launches
     bit for bit (the same roundings on the same sums): w1 || w3 with the interleaved SwiGLU -- stored
     by the kernel itself when unsliced (blocks 1), in the split-K epilogue (CE_SWIGLU8) when sliced --
@@ -114,7 +102,7 @@ def test_prompt_fusions_bit_identical(golden, tune, knob, blocks):
     cfg = _cfg("llm_wide")
     out = []
     for v in (1, 0):
-        tune({knob: v, "prompt_skinny_blocks": blocks})
+        tune({key: v, "prompt_skinny_blocks": blocks})
         m = DualARModel.synthetic(cfg, int(g["synth_seed"]), int(g["log2_half"]), 0, "bf16", 1)
         T = g["prompt"].shape[1]
         out.append(m.teacher_decode(g["prompt"], g["seq"][:, T:]))

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from parity_util import bf16_vs_golden
+from parity_util import bf16_vs_golden, knob  # noqa: F401  (knob: the shared fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -94,7 +94,7 @@ def test_fp32_teacher_step_prefill_path_logits(name, rmsnorm_block, golden, knob
     """fm_llm_teacher_step (every step through the PREFILL kernels: linear_kernel, row RMSNorm,
     qk_rope_cache + split attention): logits, hidden states and fast logits within 1e-4 of the
     reference's, with the wave-per-row RMSNorm (default) and the block-per-row one."""
-    knob("rmsnorm_block", rmsnorm_block, 0)
+    knob("rmsnorm_block", rmsnorm_block)
     m, g, cfg = _model(name, "fp32", golden)
     T = g["prompt"].shape[1]
     seq = g["seq"]
@@ -273,13 +273,12 @@ def test_batched_32_slots_match_single_fp32(golden):
 
 
 @pytest.mark.parametrize("name", ["llm_a", "llm_b"])
-def test_top_k_above_64_matches_oracle_fp32(name, golden):
+def test_top_k_above_64_matches_oracle_fp32(name, golden, knob):
     """top_k > 64 (the reference's logits_to_probs takes any top_k, inference.py:54-77): the
     samplers' wide path (the row sorted in LDS, the reference's cumsum in rank order) draws the
     same streams as the CPU restatement's full sort, slow head with RAS and fast head, with nuclei
     far wider than 64 tokens (top_p 1.0 / 0.99) and top_k past the row length."""
     import oracle as O
-    from fishmi import native
 
     m, g, cfg = _model(name, "fp32", golden)
     o = O.OracleLLM(cfg, False)
@@ -290,7 +289,7 @@ def test_top_k_above_64_matches_oracle_fp32(name, golden):
     else:
         o.synth(int(g["synth_seed"]), int(g["log2_half"]))
     for fast in (1, 0):
-        native.tune("sampler_fast", fast)
+        knob("sampler_fast", fast)
         try:
             for top_k, top_p, temp, seed in ((100, 1.0, 0.9, 5), (1000, 0.99, 1.3, 6), (65, 0.95, 0.7, 7)):
                 ref = o.generate(g["prompt"], 16, temperature=temp, top_p=top_p, top_k=top_k, seed=seed)
@@ -298,18 +297,16 @@ def test_top_k_above_64_matches_oracle_fp32(name, golden):
                 out = m.generate(g["prompt"], 16, temperature=temp, top_p=top_p, top_k=top_k, seed=seed)
                 np.testing.assert_array_equal(out, ref, err_msg=f"top_k {top_k} sampler_fast {fast}")
         finally:
-            native.tune("sampler_fast", 1)
             m.use_graph(True)
 
 
-def test_top_k_above_64_at_s2_pro_head_width(golden):
+def test_top_k_above_64_at_s2_pro_head_width(golden, knob):
     """The samplers' wide path (top_k > 64) at the production head widths (slow head: the 4096
     semantic tokens + <|im_end|> of a 155776-token vocabulary; fast head: 4096 codes), bf16: a free
     slot samples each frame, a twin slot replays that column forced and taps the logits its
     samplers were handed; every emitted token equals the C oracle's draw (logits_to_probs +
     multinomial, inference.py:43-93, with RAS, inference.py:117-144) on those same logits."""
     import oracle as O
-    from fishmi import native
     from fishmi.llm import DualARModel
 
     g = golden("llm_wide_bf16.npz")
@@ -321,7 +318,7 @@ def test_top_k_above_64_at_s2_pro_head_width(golden):
     n_new = 8
     try:
         for fast in (1, 0):
-            native.tune("sampler_fast", fast)
+            knob("sampler_fast", fast)
             m.use_graph(fast == 1)
             for top_k, top_p, temp, seed in ((100, 1.0, 0.9, 5), (1000, 0.99, 1.3, 6), (4096, 0.95, 0.7, 7)):
                 sp = DualARModel.sampling(temperature=temp, top_p=top_p, top_k=top_k, seed=seed, mask_im_end=True)
@@ -349,7 +346,6 @@ def test_top_k_above_64_at_s2_pro_head_width(golden):
                         prev = np.roll(prev, -1, axis=1)
                         prev[:, -1] = col
     finally:
-        native.tune("sampler_fast", 1)
         m.use_graph(True)
         m.close()
 
@@ -406,22 +402,6 @@ def test_decode_frames_matches_generate(golden):
         np.testing.assert_array_equal(got, single[s])
 
 
-@pytest.fixture
-def knob():
-    """fm_tune knobs set by a test, restored to their defaults afterwards."""
-    from fishmi import native
-
-    set_ = {}
-
-    def put(key, value, default):
-        set_[key] = default
-        native.tune(key, value)
-
-    yield put
-    for k, d in set_.items():
-        native.tune(k, d)
-
-
 @pytest.mark.parametrize("bstream", [1, 0])
 @pytest.mark.parametrize("n", [12, 20])
 def test_batched_slots_past_gemv_match_single(n, bstream, golden, knob):
@@ -430,7 +410,7 @@ def test_batched_slots_past_gemv_match_single(n, bstream, golden, knob):
     MFMA linear_kernel (fm_tune bstream=0)."""
     from fishmi.llm import DualARModel
 
-    knob("bstream", bstream, 1)
+    knob("bstream", bstream)
 
     m, g, cfg = _model("llm_b", "fp32", golden, max_slots=n)
     rng = np.random.default_rng(7)
@@ -462,11 +442,8 @@ def test_batched_wide_split_k_matches_single(knobs, golden, knob):
     reproduce every slot's batch-1 greedy stream (fp32 mode)."""
     from fishmi.llm import DualARModel
 
-    defaults = {"bstream": 1, "linear_fill": 0, "bstream_nw": 0, "bstream_kparts": 0, "batched_fused_attn": 1,
-                "attn_cap_batched": 128, "fd_min_batched": 512, "linear_u32": 4, "bstream_acc": 1, "fd_nw_batched": 4,
-                "bs_qkv_slab": 1}
     for k, v in knobs.items():
-        knob(k, v, defaults[k])
+        knob(k, v)
 
     g = golden("llm_wide_bf16.npz")
     cfg = _cfg("llm_wide")
@@ -513,39 +490,32 @@ def test_long_context_split_attention_matches_oracle(golden):
     np.testing.assert_array_equal(out, ref)
 
 
-def test_fast_sampler_equals_radix_sampler(golden):
+def test_fast_sampler_equals_radix_sampler(golden, knob):
     """The two-stage register top-K sampler and the LDS radix-select sampler draw the same
     streams (same candidates in the same order, same RNG draws), sampled and greedy."""
-    from fishmi import native
 
     m, g, cfg = _model("llm_a", "bf16", golden)
     outs = {}
     for fast in (1, 0):
-        native.tune("sampler_fast", fast)
+        knob("sampler_fast", fast)
         m.use_graph(False)
         outs[fast] = [m.generate(g["prompt"], 24, top_k=k, seed=s, temperature=0.9, top_p=0.95)
                       for k, s in ((30, 1), (64, 2), (1, 3), (5, 4))]
-    native.tune("sampler_fast", 1)
     m.use_graph(True)
     for a, b in zip(outs[1], outs[0]):
         np.testing.assert_array_equal(a, b)
 
 
 @pytest.mark.parametrize("name", ["llm_a", "llm_b"])
-def test_fast_attention_in_wo_prologue(name, golden):
+def test_fast_attention_in_wo_prologue(name, golden, knob):
     """fm_tune attn_wo=1 (PRO_FATT): the fast model's attention recomputed by every block of the
     Wo GEMV from LDS-staged operands gives the same fp32 greedy stream as the reference."""
-    from fishmi import native
-
-    native.tune("attn_wo", 1)
-    try:
-        m, g, _ = _model(name, "fp32", golden)
-        T = g["prompt"].shape[1]
-        ref = g["seq"][:, T:]
-        out = m.generate(g["prompt"], ref.shape[1], top_k=1)
-        np.testing.assert_array_equal(out, ref)
-    finally:
-        native.tune("attn_wo", 0)
+    knob("attn_wo", 1)
+    m, g, _ = _model(name, "fp32", golden)
+    T = g["prompt"].shape[1]
+    ref = g["seq"][:, T:]
+    out = m.generate(g["prompt"], ref.shape[1], top_k=1)
+    np.testing.assert_array_equal(out, ref)
 
 
 @pytest.mark.parametrize("n", [3, 10])

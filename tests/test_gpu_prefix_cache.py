@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from parity_util import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -105,13 +106,11 @@ def test_copy_bit_for_bit(prec, name, npos, models):
 def test_copy_scalar_path_bit_for_bit(models):
     """The copy's scalar path (taken where a run or a base is not 16-byte aligned; forced here by the
     prefix_vec knob) moves the same rows as the vector path."""
-    from fishmi import native
 
     m = models("llm_a", "bf16")
     a, b = _prompt(m.cfg, LEN_A, 1), _prompt(m.cfg, LEN_B, 2)
     npos = 37
-    native.tune("prefix_vec", 0)
-    try:
+    with tuned(prefix_vec=0):
         m.prefill(0, a, _greedy())
         rows_a = _read_all(m)
         pid = m.save_prefix(0, npos)
@@ -119,8 +118,6 @@ def test_copy_scalar_path_bit_for_bit(models):
         rows_b = _read_all(m)
         m.load_prefix(pid, [0])
         got = _read_all(m)
-    finally:
-        native.tune("prefix_vec", 1)
     np.testing.assert_array_equal(got[:, :, :, :npos], rows_a[:, :, :, :npos])
     np.testing.assert_array_equal(got[:, :, :, npos:], rows_b[:, :, :, npos:])
     m.drop_prefix(pid)

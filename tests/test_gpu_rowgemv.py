@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from parity_util import bf16_vs_golden
+from parity_util import bf16_vs_golden, knob  # noqa: F401  (knob: the shared fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -18,16 +18,12 @@ FW_TAG = 0xFFF9   # fused fast attention + wo: attention waves
 
 
 @pytest.fixture
-def rowgemv_mode():
-    from fishmi import native
-
+def rowgemv_mode(knob):
     def set_(v, fused=1):
-        native.tune("rowgemv", v)
-        native.tune("fattn_wo", fused)
+        knob("rowgemv", v)
+        knob("fattn_wo", fused)
 
-    yield set_
-    native.tune("rowgemv", 27)
-    native.tune("fattn_wo", 1)
+    return set_
 
 
 def _row_blocks_ran(m, step, tag=ROW_TAG):
