@@ -15,6 +15,11 @@
 //   fm_op_embed     the Dual-AR input embedding (llama.py:399-420)
 //   fm_op_batched_linear_q8  the batched decode linear (bsacc_kernel) on weight-only int8 codes and on
 //                   their bf16 fragment copy (fm_tune bstream_q8)
+//   fm_op_linear / fm_op_gemv / fm_op_rowgemv / fm_op_bstream / fm_op_finalize_norm / fm_op_prompt_skinny
+//                   the decode linears, one production launcher each (launch_linear, launch_gemv, launch_rowgemv,
+//                   launch_bstream on bstream_plan's geometry, launch_finalize_norm, launch_prompt_skinny): outputs
+//                   are in/out arrays with spare rows / columns, the launch can be repeated on the same scratch,
+//                   and the ticket words left non-zero are counted (tests/test_gpu_linear_ops.py)
 //   fm_rope_table   the host-built bf16 cos/sin table (no device needed)
 // Operands are fp32 host arrays, converted to the precision's storage type (bf16 rounding is the
 // caller's business: pass bf16-valued floats for bit-level comparisons).
@@ -303,6 +308,429 @@ void embed_t(hipStream_t s, const int32_t* tok, int R, const float* emb, int V, 
     download<T>(xd, (size_t)R * d, x, s);
 }
 
+// ---- linear hooks (fm_op_linear .. fm_op_prompt_skinny) -----------------------------------------
+// A caller output array, in/out: uploaded before the launches (the caller's sentinel fill lands in
+// the padding columns and rows the kernel must not touch) and downloaded after them.
+template <typename T> struct InOut {
+    T* d;
+    float* h;
+    size_t n;
+    InOut(DevBufs& b, float* host, size_t count) : d(b.upload<T>(host, count)), h(host), n(count) {}
+    void get(hipStream_t s) { download<T>(d, n, h, s); }
+};
+
+int count_nonzero(const int* d, size_t n, hipStream_t s) {
+    std::vector<int> h(n);
+    HIPCHK(hipMemcpyAsync(h.data(), d, n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return (int)std::count_if(h.begin(), h.end(), [](int v) { return v != 0; });
+}
+
+// row-major fp32 host weight [N][K] -> the packed MFMA-fragment layout, rows padded to 16 (zeros)
+template <typename T> T* upload_packed(DevBufs& b, const float* w, int N, int K) {
+    T* t = b.upload<T>(w, (size_t)N * K);
+    T* pk = (T*)b.alloc((size_t)((N + 15) / 16 * 16) * K * sizeof(T));
+    launch_pack<T>(b.s, t, N, K, pk);
+    HIPCHK(hipGetLastError());
+    return pk;
+}
+
+template <typename T>
+void linear_op_t(hipStream_t s, int epi, const float* w, const float* w2, const float* bias, const float* x, int ldx,
+                 const float* res, int ldr, int R, int N, int K, int split, float* y, int ldy, int y_rows, int reps,
+                 int* ksb_out, int* dirty) {
+    DevBufs b(s);
+    const bool f32 = epi == EPI_F32;
+    LinearArgs<T> a{};
+    a.W = upload_packed<T>(b, w, N, K);
+    if (epi == EPI_SWIGLU) a.W2 = upload_packed<T>(b, w2, N, K);
+    if (bias) a.bias = b.upload<T>(bias, (size_t)N);
+    a.X = b.upload<T>(x, (size_t)R * ldx);
+    a.ldx = ldx;
+    a.R = R;
+    a.N = N;
+    a.K = K;
+    a.ldy = ldy;
+    if (epi == EPI_RESID) {
+        a.res = b.upload<T>(res, (size_t)R * ldr);
+        a.ldr = ldr;
+    }
+    InOut<T> yt(b, y, f32 ? 1 : (size_t)y_rows * ldy);
+    InOut<float> yf(b, y, f32 ? (size_t)y_rows * ldy : 1);
+    a.Y = f32 ? nullptr : yt.d;
+    a.Yf = f32 ? yf.d : nullptr;
+    const int nacc = epi == EPI_SWIGLU ? 2 : 1, tiles = (N + 15) / 16;
+    const bool can_split = split && R > 8 && R <= 64;  // as the batched decode frame offers it
+    const int ksb = linear_ksb(N, K, R, nacc, can_split);
+    int* tickets = (int*)b.alloc((size_t)tiles * 4);
+    if (can_split) {
+        a.part = (float*)b.alloc((size_t)ksb * nacc * R * N * 4);
+        a.tickets = tickets;
+    }
+    for (int i = 0; i < reps; ++i) launch_linear<T>(s, a, epi);
+    HIPCHK(hipGetLastError());
+    if (f32) yf.get(s);
+    else yt.get(s);
+    *ksb_out = ksb;
+    *dirty = count_nonzero(tickets, (size_t)tiles, s);
+}
+
+struct GemvOp {
+    int pro, epi, ksb;
+    const float *w, *w2, *bias, *nw;
+    float eps;
+    const float* x;
+    int x_rows, ldx;
+    const int32_t* idx;
+    int idx_ld, idx_col, idx_rows;
+    const float* res;
+    int res_rows, ldr, ss_gran, R, N, K;
+    float* y;
+    int ldy, y_rows;
+    float* ss_out;
+    int reps;
+    int* dirty;
+};
+
+template <typename T> void gemv_op_t(hipStream_t s, const GemvOp& o) {
+    DevBufs b(s);
+    const int R = o.R, N = o.N, K = o.K, tiles = (N + 15) / 16;
+    const bool f32 = o.epi == EPI_F32 || o.epi == EPI_SLAB;
+    GemvArgs<T> a{};
+    a.W = upload_packed<T>(b, o.w, N, K);
+    if (o.epi == EPI_SWIGLU) a.W2 = upload_packed<T>(b, o.w2, N, K);
+    if (o.bias) a.bias = b.upload<T>(o.bias, (size_t)N);
+    if (o.nw) a.nw = b.upload<T>(o.nw, (size_t)K);
+    a.eps = o.eps;
+    a.ldx = o.ldx;
+    a.R = R;
+    a.N = N;
+    a.K = K;
+    a.dummy_tail = fm_tuning().gemv_dummy;
+    int* tickets = (int*)b.alloc((size_t)(tiles + 16) * 4);
+    a.tickets = tickets;
+    T* xd = b.upload<T>(o.x, (size_t)o.x_rows * o.ldx);
+    a.X = xd;
+    if (o.idx) {
+        int32_t* id = (int32_t*)b.alloc((size_t)R * o.idx_ld * 4);
+        b.put(id, o.idx, (size_t)R * o.idx_ld * 4);
+        if (o.pro == PRO_NORM) a.xidx = id;
+        else a.residx = id;
+        a.xidx_ld = o.idx_ld;
+        a.xidx_col = o.idx_col;
+        a.xidx_rows = o.idx_rows;
+    }
+    if (o.pro == PRO_PRENORM) {
+        // as rmsnorm_t: a zero-weight EPI_SLABFIN GEMV finalises x = round(x + round(0)) and leaves the
+        // per-16-column sums of squares [K/16][R] the way the wo / w2 GEMVs do for the next norm
+        T* xz = (T*)b.alloc((size_t)R * 32 * sizeof(T));
+        T* wz = (T*)b.alloc((size_t)K * 32 * sizeof(T));
+        float* slab = (float*)b.alloc((size_t)R * K * 4);
+        float* ss = (float*)b.alloc((size_t)(K / 16) * R * 4);
+        T* xf = b.upload<T>(o.x, (size_t)R * o.ldx);
+        GemvArgs<T> f{};
+        f.W = wz;
+        f.X = xz;
+        f.ldx = 32;
+        f.R = R;
+        f.N = K;
+        f.K = 32;
+        f.Yf = slab;
+        f.ldy = K;
+        f.res = xd;
+        f.ldr = o.ldx;
+        f.res_out = xf;
+        f.ldro = o.ldx;
+        f.ss_out = ss;
+        f.tickets = tickets;
+        f.eps = o.eps;
+        launch_gemv<T>(s, f, PRO_PLAIN, EPI_SLABFIN, 1);
+        HIPCHK(hipGetLastError());
+        a.X = xf;
+        a.ss_in = ss;
+        a.ss_gran = o.ss_gran;
+    }
+    const int ycols_rows = o.y_rows;
+    InOut<T> yt(b, o.y, f32 ? 1 : (size_t)ycols_rows * o.ldy);
+    InOut<float> yf(b, o.y, f32 ? (size_t)ycols_rows * o.ldy : 1);
+    std::vector<float> one(1, 0.f);
+    InOut<float> ss(b, o.epi == EPI_SLABFIN ? o.ss_out : one.data(), o.epi == EPI_SLABFIN ? (size_t)(N / 16) * R : 1);
+    a.ldy = o.ldy;
+    if (o.epi == EPI_SLABFIN) {
+        a.res = b.upload<T>(o.res, (size_t)o.res_rows * o.ldr);
+        a.ldr = o.ldr;
+        a.res_out = yt.d;
+        a.ldro = o.ldy;
+        a.ss_out = ss.d;
+        a.Yf = (float*)b.alloc((size_t)o.ksb * R * N * 4);  // K-slice partials (scratch)
+        a.ldy = N;
+    } else if (f32) {
+        a.Yf = yf.d;
+    } else {
+        a.Y = yt.d;
+    }
+    for (int i = 0; i < o.reps; ++i) launch_gemv<T>(s, a, o.pro, o.epi, o.ksb);
+    HIPCHK(hipGetLastError());
+    if (f32) yf.get(s);
+    else yt.get(s);
+    if (o.epi == EPI_SLABFIN) ss.get(s);
+    *o.dirty = count_nonzero(tickets, (size_t)tiles + 16, s);
+}
+
+struct BstreamOp {
+    int pro, epi;
+    const float *w, *bias, *nw;
+    float eps;
+    const float* x;
+    int ldx;
+    const float* res;
+    int ldr, R, N, K;
+    float* y;
+    int ldy, y_rows;
+    float* ss_out;
+    int reps;
+    int* plan;
+    int* dirty;
+};
+
+template <typename T> void bstream_op_t(hipStream_t s, const BstreamOp& o) {
+    DevBufs b(s);
+    bsacc_init();
+    const int R = o.R, N = o.N, K = o.K, tiles = (N + 15) / 16;
+    const BstreamPlan p = bstream_plan(N, K, R, o.epi, sizeof(T));
+    FMCHECK(p.ok, "bstream: no plan for this shape");
+    FMCHECK((o.epi != EPI_SLABFIN && o.pro != PRO_PRENORM) || p.acc, "bstream: SLABFIN / PRENORM run on bsacc_kernel only");
+    const int slabs = (o.epi == EPI_SLAB) ? p.kparts : 1;
+    FMCHECK(o.y_rows >= slabs * R, "bstream: the output holds fewer rows than [kparts][R]");
+    const bool f32 = o.epi == EPI_F32 || o.epi == EPI_SLAB;
+    BstreamArgs<T> a{};
+    a.W = upload_packed<T>(b, o.w, N, K);
+    if (o.bias) a.bias = b.upload<T>(o.bias, (size_t)N);
+    T* xd = b.upload<T>(o.x, (size_t)R * o.ldx);
+    a.X = xd;
+    a.ldx = o.ldx;
+    a.R = R;
+    a.N = N;
+    a.K = K;
+    a.eps = o.eps;
+    const size_t ntk = (size_t)tiles + 1024;  // one word per tile group (at most one per CU), the producer's too
+    int* tickets = (int*)b.alloc(ntk * 4);
+    if constexpr (sizeof(T) == 2) {
+        if (o.pro == PRO_PRENORM) {
+            // the producer's sums of squares [R][K/16]: a zero-weight bsacc EPI_SLABFIN launch (N = K, 8 k-steps)
+            // finalises x = round(x + round(0)) and its per-tile sums as the batched wo / w2 do
+            const BstreamPlan pz = bstream_plan(K, 256, R, EPI_SLABFIN, sizeof(T));
+            FMCHECK(pz.ok && pz.acc && pz.kparts == 1, "bstream: no plan for the sums-of-squares producer");
+            BstreamArgs<T> f{};
+            f.W = (T*)b.alloc((size_t)K * 256 * sizeof(T));
+            f.X = (T*)b.alloc((size_t)R * 256 * sizeof(T));
+            f.ldx = 256;
+            f.R = R;
+            f.N = K;
+            f.K = 256;
+            f.Yf = (float*)b.alloc((size_t)R * K * 4);
+            f.ldy = K;
+            f.res = xd;
+            f.ldr = o.ldx;
+            T* xf = b.upload<T>(o.x, (size_t)R * o.ldx);
+            f.res_out = xf;
+            f.ldro = o.ldx;
+            float* ss = (float*)b.alloc((size_t)R * (K / 16) * 4);
+            f.ss_out = ss;
+            f.tickets = tickets;
+            FMCHECK(launch_bstream<T>(s, f, EPI_SLABFIN, pz), "bstream: no kernel for the producer's plan");
+            HIPCHK(hipGetLastError());
+            a.X = xf;
+            a.pro = PRO_PRENORM;
+            a.ss_in = ss;
+            a.nw = b.upload<T>(o.nw, (size_t)K);
+        }
+    }
+    InOut<T> yt(b, o.y, f32 ? 1 : (size_t)o.y_rows * o.ldy);
+    InOut<float> yf(b, o.y, f32 ? (size_t)o.y_rows * o.ldy : 1);
+    std::vector<float> one(1, 0.f);
+    InOut<float> ss(b, o.epi == EPI_SLABFIN ? o.ss_out : one.data(), o.epi == EPI_SLABFIN ? (size_t)R * tiles : 1);
+    a.ldy = o.ldy;
+    if (o.epi == EPI_SLABFIN) {
+        a.res = b.upload<T>(o.res, (size_t)R * o.ldr);
+        a.ldr = o.ldr;
+        a.res_out = yt.d;
+        a.ldro = o.ldy;
+        a.ss_out = ss.d;
+        a.tickets = tickets;
+        a.Yf = (float*)b.alloc((size_t)p.kparts * R * N * 4);  // K-part partials (scratch)
+        a.ldy = N;
+    } else if (f32) {
+        a.Yf = yf.d;
+    } else {
+        a.Y = yt.d;
+    }
+    for (int i = 0; i < o.reps; ++i)
+        FMCHECK(launch_bstream<T>(s, a, o.epi, p), "bstream: no kernel for the plan");
+    HIPCHK(hipGetLastError());
+    if (f32) yf.get(s);
+    else yt.get(s);
+    if (o.epi == EPI_SLABFIN) ss.get(s);
+    const int pl[7] = {p.acc, p.kparts, p.nw, p.spw, p.tpi, p.ntm, p.grid};
+    memcpy(o.plan, pl, sizeof(pl));
+    *o.dirty = count_nonzero(tickets, ntk, s);
+}
+
+struct FinalizeOp {
+    const float* slab;
+    int kparts, lds;
+    const float *bias, *res;
+    int ldr;
+    const float *nw, *wscale;
+    float eps;
+    int d, R;
+    float* x_out;
+    int ldx, x_rows;
+    float* xn_out;
+    int ldxn, xn_rows, reps;
+    int *split, *err, *dirty;
+};
+
+template <typename T> void finalize_op_t(hipStream_t s, const FinalizeOp& o) {
+    DevBufs b(s);
+    const int R = o.R, d = o.d;
+    FinalizeArgs<T> f{};
+    float* slab = (float*)b.alloc((size_t)o.kparts * R * o.lds * 4);
+    b.put(slab, o.slab, (size_t)o.kparts * R * o.lds * 4);
+    f.slab = slab;
+    f.kparts = o.kparts;
+    f.lds = o.lds;
+    if (o.bias) f.bias = b.upload<T>(o.bias, (size_t)d);
+    f.res = b.upload<T>(o.res, (size_t)R * o.ldr);
+    f.ldr = o.ldr;
+    InOut<T> xo(b, o.x_out, (size_t)o.x_rows * o.ldx);
+    f.x_out = xo.d;
+    f.ldx = o.ldx;
+    std::vector<float> one(1, 0.f);
+    InOut<T> xn(b, o.nw ? o.xn_out : one.data(), o.nw ? (size_t)o.xn_rows * o.ldxn : 1);
+    if (o.nw) {
+        f.nw = b.upload<T>(o.nw, (size_t)d);
+        f.xn_out = xn.d;
+        f.ldxn = o.ldxn;
+    }
+    f.eps = o.eps;
+    f.d = d;
+    f.R = R;
+    if (o.wscale) f.wscale = b.upload<T>(o.wscale, (size_t)d);
+    // the split form as the batched frame arms it (fm_tune fin_split): counters, partial sums, err word
+    const int ch = fm_tuning().fin_split;
+    int* cnt = (int*)b.alloc((size_t)2 * R * 4);
+    int* err = (int*)b.alloc(4);
+    if (ch > 1) {
+        f.ch = ch;
+        f.cnt = cnt;
+        f.ss_part = (float*)b.alloc((size_t)R * ch * 4);
+        f.err = err;
+    }
+    *o.split = ch > 1 && R * ch <= 1024 && (d / 8 + ch - 1) / ch <= 64;  // launch_finalize_norm's own condition
+    for (int i = 0; i < o.reps; ++i) launch_finalize_norm<T>(s, f);
+    HIPCHK(hipGetLastError());
+    xo.get(s);
+    if (o.nw) xn.get(s);
+    HIPCHK(hipMemcpyAsync(o.err, err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *o.dirty = count_nonzero(cnt, (size_t)2 * R, s);
+}
+
+struct RowGemvOp {
+    int kind, q8;
+    const float *w, *bias, *nw;
+    float eps;
+    const float* x;
+    int x_rows, ldx;
+    const float* res;
+    int res_rows, ldr;
+    const int32_t* idx;
+    int idx_n, idx_col, N, K;
+    float* y;
+    int y_len, reps;
+    int8_t* q_out;
+    float* scale_out;
+};
+
+void rowgemv_op(hipStream_t s, const RowGemvOp& o) {
+    DevBufs b(s);
+    const int N = o.N, K = o.K;
+    const bool f32 = o.kind == ROWGEMV_NORM_F32, fin = o.kind == ROWGEMV_FIN;
+    RowGemvArgs a{};
+    bf16_t* wd = b.upload<bf16_t>(o.w, (size_t)N * K);
+    if (o.q8) {  // the int8 rule on the device, as fm_llm_set_quant applies it: codes row-major, bf16 row scales
+        int8_t* dq = (int8_t*)b.alloc((size_t)N * K);
+        bf16_t* ds = (bf16_t*)b.alloc((size_t)N * 2);
+        launch_quant_rows<bf16_t>(s, wd, N, K, dq, ds);
+        HIPCHK(hipGetLastError());
+        a.Wq = dq;
+        a.wscale = ds;
+        if (o.q_out) {
+            HIPCHK(hipMemcpyAsync(o.q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        if (o.scale_out) download<bf16_t>(ds, (size_t)N, o.scale_out, s);
+    } else {
+        a.W = wd;
+    }
+    a.X = b.upload<bf16_t>(o.x, (size_t)o.x_rows * o.ldx);
+    a.ldx = o.ldx;
+    if (o.bias) a.bias = b.upload<bf16_t>(o.bias, (size_t)N);
+    if (o.nw) a.nw = b.upload<bf16_t>(o.nw, (size_t)K);
+    a.eps = o.eps;
+    int32_t* id = nullptr;
+    if (o.idx) {
+        id = (int32_t*)b.alloc((size_t)o.idx_n * 4);
+        b.put(id, o.idx, (size_t)o.idx_n * 4);
+    }
+    if (fin) {
+        a.res = b.upload<bf16_t>(o.res, (size_t)o.res_rows * o.ldr);
+        a.ldr = o.ldr;
+        a.residx = id;
+        a.res_col = o.idx_col;
+        a.res_rows = o.res_rows;
+    } else {
+        a.xidx = id;
+        a.xcol = o.idx_col;
+        a.xrows = o.x_rows;
+    }
+    a.N = N;
+    a.K = K;
+    InOut<bf16_t> yt(b, o.y, f32 ? 1 : (size_t)o.y_len);
+    InOut<float> yf(b, o.y, f32 ? (size_t)o.y_len : 1);
+    if (fin) a.res_out = yt.d;
+    else if (f32) a.Yf = yf.d;
+    else a.Y = yt.d;
+    for (int i = 0; i < o.reps; ++i) launch_rowgemv(s, a, o.kind);
+    HIPCHK(hipGetLastError());
+    if (f32) yf.get(s);
+    else yt.get(s);
+}
+
+void prompt_skinny_op(hipStream_t s, const float* w, const float* x, int ldx, int R, int N, int K, int ks, int act,
+                      float* out, int out_rows, int ldo, int reps) {
+    DevBufs b(s);
+    PromptSkinnyArgs p{};
+    p.w = upload_packed<bf16_t>(b, w, N, K);
+    p.x = b.upload<bf16_t>(x, (size_t)R * ldx);
+    p.ldx = ldx;
+    p.R = R;
+    p.N = N;
+    p.K = K;
+    InOut<float> slab(b, out, act ? 1 : (size_t)out_rows * N);
+    InOut<bf16_t> av(b, out, act ? (size_t)out_rows * ldo : 1);
+    p.slab = slab.d;  // (the launcher wants it set in the direct form too; the kernel does not write it then)
+    if (act) {
+        p.act = av.d;
+        p.lda = ldo;
+    }
+    for (int i = 0; i < reps; ++i) launch_prompt_skinny(s, p, ks);
+    HIPCHK(hipGetLastError());
+    if (act) av.get(s);
+    else slab.get(s);
+}
+
 }  // namespace
 
 extern "C" {
@@ -524,6 +952,144 @@ int fm_op_batched_linear_q8(int device, const float* w, int N, int K, const floa
             }
         }
         if (kparts) *kparts = p.kparts;
+    });
+}
+
+// ---- the decode linears, one production launcher each (include/fishmi.h) -------------------------
+int fm_op_linear(int device, int precision, int epi, const float* w, const float* w2, const float* bias,
+                 const float* x, int ldx, const float* res, int ldr, int R, int N, int K, int split, float* y, int ldy,
+                 int y_rows, int reps, int* ksb, int* dirty) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y && ksb && dirty, "null argument");
+        FMCHECK(epi == EPI_STORE || epi == EPI_RESID || epi == EPI_SWIGLU || epi == EPI_F32, "epi must be 0..3");
+        FMCHECK((epi == EPI_SWIGLU) == (w2 != nullptr), "w2 goes with EPI_SWIGLU (2) only");
+        FMCHECK((epi == EPI_RESID) == (res != nullptr), "res goes with EPI_RESID (1) only");
+        FMCHECK(R >= 1 && R <= 1024 && N >= 1 && K >= 32 && K % 32 == 0, "need 1 <= R <= 1024, N >= 1, K a multiple of 32");
+        FMCHECK(ldx >= K && ldx % 8 == 0 && ldy >= N && y_rows >= R && (!res || ldr >= N), "bad row strides / output rows");
+        FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
+        StreamGuard g(device);
+        if (precision == FM_PREC_BF16)
+            linear_op_t<bf16_t>(g.s, epi, w, w2, bias, x, ldx, res, ldr, R, N, K, split, y, ldy, y_rows, reps, ksb, dirty);
+        else
+            linear_op_t<float>(g.s, epi, w, w2, bias, x, ldx, res, ldr, R, N, K, split, y, ldy, y_rows, reps, ksb, dirty);
+    });
+}
+
+int fm_op_gemv(int device, int precision, int pro, int epi, int ksb, const float* w, const float* w2, const float* bias,
+               const float* nw, float eps, const float* x, int ldx, const int32_t* idx, int idx_ld, int idx_col,
+               int idx_rows, const float* res, int ldr, int ss_gran, int R, int N, int K, float* y, int ldy, int y_rows,
+               float* ss_out, int reps, int* dirty) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y && dirty, "null argument");
+        const bool plain = pro == PRO_PLAIN, norm = pro == PRO_NORM, pre = pro == PRO_PRENORM;
+        // the (prologue, epilogue) pairs launch_gemv dispatches (PRO_FATT needs attention state: not here)
+        FMCHECK((plain && (epi == EPI_STORE || epi == EPI_SLABFIN || epi == EPI_F32 || epi == EPI_SLAB)) ||
+                    (norm && (epi == EPI_STORE || epi == EPI_SWIGLU || epi == EPI_F32)) ||
+                    (pre && (epi == EPI_STORE || epi == EPI_SWIGLU || epi == EPI_F32 || epi == EPI_SWIGLU8)),
+                "no GEMV kernel for this prologue / epilogue");
+        FMCHECK(R >= 1 && R <= 8 && N >= 1 && K >= 32 && K % 32 == 0, "need 1 <= R <= 8, N >= 1, K a multiple of 32");
+        const bool slabs = epi == EPI_SLAB || epi == EPI_SLABFIN;
+        FMCHECK(ksb >= 1 && ksb <= 16 && K % (32 * ksb) == 0 && (slabs || ksb == 1), "ksb: whole k-steps per slice; > 1 only into slabs");
+        FMCHECK((epi == EPI_SWIGLU) == (w2 != nullptr), "w2 goes with EPI_SWIGLU (2) only");
+        FMCHECK(plain == (nw == nullptr), "the norm weight goes with PRO_NORM / PRO_PRENORM");
+        FMCHECK((epi != EPI_SLABFIN && epi != EPI_SWIGLU8) || N % 16 == 0, "EPI_SLABFIN / EPI_SWIGLU8 need whole 16-row tiles");
+        FMCHECK(epi != EPI_SLABFIN || (res && ss_out && ldr >= N), "EPI_SLABFIN needs res and ss_out");
+        FMCHECK(!norm || K <= 8192, "PRO_NORM stages at most 8192 columns");
+        FMCHECK(!pre || (K <= 4096 && (ss_gran == 0 || (ss_gran == 1 && R == 1 && K <= 3 * 8 * 256))),
+                "PRO_PRENORM: K <= 4096; ss_gran 1 needs one row and K <= 6144");
+        FMCHECK(!idx || ((norm || epi == EPI_SLABFIN) && idx_rows >= 1 && idx_ld >= 1 && idx_col >= 0 && idx_col < idx_ld),
+                "a row gather needs PRO_NORM (x) or EPI_SLABFIN (res), its table's row count and a column of idx");
+        FMCHECK(ldx >= K && ldx % 8 == 0 && ldy >= (epi == EPI_SWIGLU8 ? N / 2 : N), "bad row strides");
+        FMCHECK(y_rows >= (epi == EPI_SLAB ? ksb * R : R) && reps >= 1 && reps <= 8, "too few output rows, or reps outside 1..8");
+        FMCHECK(gemv_lds_bytes(R, K / ksb, precision == FM_PREC_BF16 ? 2 : 4) <= 160 * 1024, "the x slice does not fit LDS");
+        GemvOp o{pro, epi, ksb, w, w2, bias, nw, eps, x, (idx && norm) ? idx_rows : R, ldx, idx, idx_ld, idx_col, idx_rows,
+                 res, (idx && !norm) ? idx_rows : R, ldr, ss_gran, R, N, K, y, ldy, y_rows, ss_out, reps, dirty};
+        StreamGuard g(device);
+        if (precision == FM_PREC_BF16) gemv_op_t<bf16_t>(g.s, o);
+        else gemv_op_t<float>(g.s, o);
+    });
+}
+
+int fm_op_rowgemv(int device, int kind, int q8, const float* w, const float* bias, const float* nw, float eps,
+                  const float* x, int x_rows, int ldx, const float* res, int res_rows, int ldr, const int32_t* idx,
+                  int idx_n, int idx_col, int N, int K, float* y, int y_len, int reps, int8_t* q_out, float* scale_out) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y, "null argument");
+        FMCHECK(kind >= ROWGEMV_FIN && kind <= ROWGEMV_NORM_F32, "kind must be 0 (fin), 1 (norm, store), 2 (norm, swiglu) or 3 (norm, f32)");
+        const bool fin = kind == ROWGEMV_FIN;
+        const int U = rowgemv_u(K, q8 ? 1 : 0);
+        FMCHECK(U > 0 && (fin || U <= 8), "K: whole chunks of 256 (int8: 512), at most 12 per wave (norm kinds: 8)");
+        const int rp = fin ? 2 : (kind == ROWGEMV_NORM_STORE && !q8 ? fm_tuning().row_qkv_rp : 8);
+        FMCHECK(N >= rp && N % rp == 0, "N must be whole row blocks (fin 2, else 8; wqkv: fm_tune row_qkv_rp)");
+        FMCHECK(fin == (nw == nullptr) && fin == (res != nullptr), "fin takes a residual, the other kinds a norm weight");
+        FMCHECK(!bias || (!q8 && kind != ROWGEMV_NORM_SWIGLU), "no bias on int8 codes or with the SwiGLU kind");
+        FMCHECK(x_rows >= 1 && ldx >= K && ldx % 8 == 0 && (!fin || (res_rows >= 1 && ldr >= N)), "bad tables / strides");
+        FMCHECK(!idx || (idx_n >= 1 && idx_col >= 0 && idx_col < idx_n && kind != ROWGEMV_NORM_F32), "bad gather (none on the f32 kind)");
+        FMCHECK(idx || ((fin || x_rows == 1) && (!fin || res_rows == 1)), "a table of several rows needs idx");
+        FMCHECK(!fin || x_rows == 1, "fin does not gather x");
+        FMCHECK(y_len >= (kind == ROWGEMV_NORM_SWIGLU ? N / 2 : N) && reps >= 1 && reps <= 8, "output too short, or reps outside 1..8");
+        RowGemvOp o{kind, q8, w, bias, nw, eps, x, x_rows, ldx, res, res_rows, ldr, idx, idx_n, idx_col, N, K, y, y_len, reps,
+                    q_out, scale_out};
+        StreamGuard g(device);
+        rowgemv_op(g.s, o);
+    });
+}
+
+int fm_op_bstream(int device, int precision, int pro, int epi, const float* w, const float* bias, const float* nw,
+                  float eps, const float* x, int ldx, const float* res, int ldr, int R, int N, int K, float* y, int ldy,
+                  int y_rows, float* ss_out, int reps, int* plan, int* dirty) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y && plan && dirty, "null argument");
+        FMCHECK(epi == EPI_STORE || epi == EPI_F32 || epi == EPI_SLAB || epi == EPI_SWIGLU8 || epi == EPI_SLABFIN,
+                "epi must be 0 (store), 3 (fp32), 4 (slabs), 5 (slabs + finalise) or 7 (SwiGLU8)");
+        FMCHECK(pro == PRO_PLAIN || (pro == PRO_PRENORM && nw && precision == FM_PREC_BF16 && K <= 3072 && K >= 256 &&
+                                     (epi == EPI_STORE || epi == EPI_SWIGLU8)),
+                "pro must be 0, or 3 (PRO_PRENORM: bf16, norm weight, 256 <= K <= 3072, STORE / SWIGLU8)");
+        FMCHECK(R > 8 && R <= 32 && N >= 1 && K >= 32 && K % 32 == 0, "need 8 < R <= 32, N >= 1, K a multiple of 32");
+        FMCHECK(epi != EPI_SWIGLU8 || N % 16 == 0, "SwiGLU8 needs whole interleaved tiles");
+        FMCHECK(epi != EPI_SLABFIN || (res && ss_out && ldr >= N && precision == FM_PREC_BF16), "EPI_SLABFIN: bf16, res and ss_out");
+        FMCHECK(ldx >= K && ldx % 8 == 0 && ldy >= (epi == EPI_SWIGLU8 ? N / 2 : N) && y_rows >= R, "bad row strides / output rows");
+        FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
+        BstreamOp o{pro, epi, w, bias, nw, eps, x, ldx, res, ldr, R, N, K, y, ldy, y_rows, ss_out, reps, plan, dirty};
+        StreamGuard g(device);
+        if (precision == FM_PREC_BF16) bstream_op_t<bf16_t>(g.s, o);
+        else bstream_op_t<float>(g.s, o);
+    });
+}
+
+int fm_op_finalize_norm(int device, int precision, const float* slab, int kparts, int lds, const float* bias,
+                        const float* res, int ldr, const float* nw, const float* wscale, float eps, int d, int R,
+                        float* x_out, int ldx, int x_rows, float* xn_out, int ldxn, int xn_rows, int reps, int* split,
+                        int* err, int* dirty) {
+    return fm_guard([&] {
+        FMCHECK(slab && res && x_out && split && err && dirty, "null argument");
+        FMCHECK(kparts >= 1 && kparts <= 64 && R >= 1 && R <= 1024, "need 1 <= kparts <= 64, 1 <= R <= 1024");
+        FMCHECK(d >= 8 && d % 8 == 0 && d <= 8192 && lds >= d && lds % 4 == 0, "d a multiple of 8 up to 8192, slab rows of lds >= d floats, lds % 4 == 0");
+        FMCHECK(ldr >= d && ldr % 8 == 0 && ldx >= d && x_rows >= R, "bad row strides / output rows");
+        FMCHECK(!nw || (xn_out && ldxn >= d && xn_rows >= R), "the norm needs its output");
+        FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
+        FinalizeOp o{slab, kparts, lds, bias, res, ldr, nw, wscale, eps, d, R, x_out, ldx, x_rows, xn_out, ldxn, xn_rows,
+                     reps, split, err, dirty};
+        StreamGuard g(device);
+        if (precision == FM_PREC_BF16) finalize_op_t<bf16_t>(g.s, o);
+        else finalize_op_t<float>(g.s, o);
+    });
+}
+
+int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int R, int N, int K, int target, int act,
+                        float* out, int out_rows, int ldo, int reps, int* ks) {
+    return fm_guard([&] {
+        FMCHECK(ks && N >= 16 && N % 16 == 0 && K >= 32 && K % 32 == 0 && target >= 1, "bad shape");
+        *ks = prompt_skinny_ks(N, K, target);
+        if (!out) return;  // the slice count alone (it sizes the caller's slab)
+        FMCHECK(w && x, "null argument");
+        FMCHECK(*ks >= 1, "K is too short for a slice of 8 k-steps");
+        FMCHECK(R >= 1 && R <= 64 && ldx >= K && ldx % 8 == 0, "need 1 <= R <= 64 and 16-byte rows of ldx >= K");
+        FMCHECK(act ? (*ks == 1 && ldo >= N / 2 && out_rows >= R) : (ldo == N && out_rows >= *ks * R),
+                "direct SwiGLU: one slice, act [>= R][ldo >= N / 2]; else slabs [>= ks * R][N]");
+        FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
+        StreamGuard g(device);
+        prompt_skinny_op(g.s, w, x, ldx, R, N, K, *ks, act, out, out_rows, ldo, reps);
     });
 }
 

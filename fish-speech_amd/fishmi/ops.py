@@ -171,3 +171,148 @@ def batched_linear_q8(w, x, epi, device=0):
     if epi == EPI_SLAB:
         return yq.reshape(-1)[:k * R * No].reshape(k, R, No), yb.reshape(-1)[:k * R * No].reshape(k, R, No), k, q, sc
     return yq[0], yb[0], k, q, sc
+
+
+# ---- the decode linears (fm_op_linear .. fm_op_prompt_skinny; tests/test_gpu_linear_ops.py) ----------
+# Kernel codes (csrc/fm_kernels.h)
+EPI_RESID, EPI_SWIGLU, EPI_SLABFIN = 1, 2, 5
+PRO_PLAIN, PRO_NORM, PRO_PRENORM = 0, 1, 3
+ROW_FIN, ROW_NORM_STORE, ROW_NORM_SWIGLU, ROW_NORM_F32 = 0, 1, 2, 3
+
+
+def _f(a):
+    return None if a is None else np.ascontiguousarray(a, np.float32)
+
+
+def _p(a):
+    return None if a is None else native.f32p(a)
+
+
+def _out(y):
+    """An in/out array: the caller's pre-filled float32 C array itself (the hook writes into it)."""
+    assert isinstance(y, np.ndarray) and y.dtype == np.float32 and y.flags.c_contiguous and y.flags.writeable
+    return y
+
+
+def linear(w, x, y, epi=EPI_STORE, w2=None, bias=None, res=None, precision="bf16", split=False, reps=1, device=0):
+    """fm_op_linear: launch_linear on x [R][ldx >= K], w [N][K]; y [rows >= R][ldy >= N] is filled in place.
+    Returns (ksb, dirty)."""
+    w, w2, bias, x, res = _f(w), _f(w2), _f(bias), _f(x), _f(res)
+    N, K = w.shape
+    R, ldx = x.shape
+    y = _out(y)
+    ksb, dirty = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_linear(device, _prec(precision), int(epi), _p(w), _p(w2), _p(bias), _p(x), ldx,
+                                           _p(res), 0 if res is None else res.shape[1], R, N, K, int(split), _p(y),
+                                           y.shape[1], y.shape[0], int(reps), native.i32p(ksb), native.i32p(dirty)))
+    return int(ksb[0]), int(dirty[0])
+
+
+def gemv(w, x, y, pro=PRO_PLAIN, epi=EPI_STORE, ksb=1, R=None, w2=None, bias=None, nw=None, eps=1e-6, idx=None,
+         idx_col=0, res=None, ss_gran=0, ss_out=None, precision="bf16", reps=1, device=0):
+    """fm_op_gemv: launch_gemv.  x [R][ldx] (pro 1 with idx: the gathered table, R given), idx [R][idx_ld]
+    int32 (x rows with pro 1, residual rows with epi 5; the table's row count is the clamp).  y (in/out):
+    [rows][ldy]; epi 4: [ksb * R (+ spare)][ldy]; epi 5: the finalised rows, ss_out [N / 16][R] in/out.
+    Returns dirty."""
+    w, w2, bias, nw, x, res = _f(w), _f(w2), _f(bias), _f(nw), _f(x), _f(res)
+    N, K = w.shape
+    ldx = x.shape[1]
+    idx_ld = idx_rows = 0
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, np.int32).reshape(len(idx), -1)
+        idx_ld = idx.shape[1]
+        idx_rows = x.shape[0] if pro == PRO_NORM else res.shape[0]
+        R = idx.shape[0]
+    elif R is None:
+        R = x.shape[0]
+    y = _out(y)
+    dirty = np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_gemv(device, _prec(precision), int(pro), int(epi), int(ksb), _p(w), _p(w2), _p(bias),
+                                         _p(nw), float(eps), _p(x), ldx, None if idx is None else native.i32p(idx),
+                                         idx_ld, int(idx_col), idx_rows, _p(res), 0 if res is None else res.shape[1],
+                                         int(ss_gran), R, N, K, _p(y), y.shape[1], y.shape[0],
+                                         None if ss_out is None else _p(_out(ss_out)), int(reps), native.i32p(dirty)))
+    return int(dirty[0])
+
+
+def rowgemv(w, x, y, kind, q8=False, bias=None, nw=None, eps=1e-6, res=None, idx=None, idx_col=0, reps=1, device=0):
+    """fm_op_rowgemv: launch_rowgemv on one row.  x [x_rows][ldx] (one row unless gathered through
+    idx[idx_col]; kind 0 gathers its residual res [res_rows][ldr] instead); y (in/out) a flat array of at
+    least N (kind 2: N / 2) values.  Returns (q [N][K] int8, scale [N]) with q8, else None."""
+    w, bias, nw, res = _f(w), _f(bias), _f(nw), _f(res)
+    x = _f(x).reshape(-1, np.shape(x)[-1])
+    if res is not None:
+        res = res.reshape(-1, res.shape[-1])
+    N, K = w.shape
+    y = _out(y)
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, np.int32).ravel()
+    q = np.zeros((N, K), np.int8) if q8 else None
+    sc = np.zeros(N, np.float32) if q8 else None
+    native.check(native.lib().fm_op_rowgemv(device, int(kind), int(q8), _p(w), _p(bias), _p(nw), float(eps), _p(x),
+                                            x.shape[0], x.shape[1], _p(res), 0 if res is None else res.shape[0],
+                                            0 if res is None else res.shape[1],
+                                            None if idx is None else native.i32p(idx), 0 if idx is None else idx.size,
+                                            int(idx_col), N, K, _p(y), y.size, int(reps),
+                                            q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)) if q8 else None, _p(sc)))
+    return (q, sc) if q8 else None
+
+
+PLAN_FIELDS = ("acc", "kparts", "nw", "spw", "tpi", "ntm", "grid")
+
+
+def bstream(w, x, y, pro=PRO_PLAIN, epi=EPI_STORE, bias=None, nw=None, eps=1e-6, res=None, ss_out=None,
+            precision="bf16", reps=1, device=0):
+    """fm_op_bstream: launch_bstream on bstream_plan's geometry.  y (in/out) [rows][ldy]; epi 4: slabs
+    [kparts * R (+ spare)][ldy] (kparts <= 8); epi 5: the finalised rows, ss_out [R][ceil(N / 16)] in/out.
+    Returns (plan dict, dirty)."""
+    w, bias, nw, x, res = _f(w), _f(bias), _f(nw), _f(x), _f(res)
+    N, K = w.shape
+    R, ldx = x.shape
+    y = _out(y)
+    plan, dirty = np.zeros(7, np.int32), np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_bstream(device, _prec(precision), int(pro), int(epi), _p(w), _p(bias), _p(nw),
+                                            float(eps), _p(x), ldx, _p(res), 0 if res is None else res.shape[1], R, N, K,
+                                            _p(y), y.shape[1], y.shape[0],
+                                            None if ss_out is None else _p(_out(ss_out)), int(reps),
+                                            native.i32p(plan), native.i32p(dirty)))
+    return dict(zip(PLAN_FIELDS, (int(v) for v in plan))), int(dirty[0])
+
+
+def finalize_norm(slab, res, x_out, d, bias=None, nw=None, wscale=None, xn_out=None, eps=1e-6, precision="bf16",
+                  reps=1, device=0):
+    """fm_op_finalize_norm: slab [kparts][R][lds] fp32, res [R][ldr]; x_out / xn_out in/out [rows][ld].
+    Returns (split form ran, err word, dirty)."""
+    slab, res, bias, nw, wscale = _f(slab), _f(res), _f(bias), _f(nw), _f(wscale)
+    kparts, R, lds = slab.shape
+    x_out = _out(x_out)
+    split, err, dirty = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_finalize_norm(device, _prec(precision), _p(slab), kparts, lds, _p(bias), _p(res),
+                                                  res.shape[1], _p(nw), _p(wscale), float(eps), int(d), R, _p(x_out),
+                                                  x_out.shape[1], x_out.shape[0],
+                                                  None if xn_out is None else _p(_out(xn_out)),
+                                                  0 if xn_out is None else xn_out.shape[1],
+                                                  0 if xn_out is None else xn_out.shape[0], int(reps),
+                                                  native.i32p(split), native.i32p(err), native.i32p(dirty)))
+    return bool(split[0]), int(err[0]), int(dirty[0])
+
+
+def prompt_skinny_ks(N, K, target, device=0):
+    """prompt_skinny_ks(N, K, target): the K slices the prompt path would use (0: K too short)."""
+    ks = np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_prompt_skinny(device, None, None, 0, 0, int(N), int(K), int(target), 0, None, 0, 0,
+                                                  1, native.i32p(ks)))
+    return int(ks[0])
+
+
+def prompt_skinny(w, x, out, target, act=False, reps=1, device=0):
+    """fm_op_prompt_skinny: out (in/out) the fp32 slabs [ks * R (+ spare)][N], or with act the SwiGLU rows
+    [rows >= R][ldo >= N / 2].  Returns ks."""
+    w, x = _f(w), _f(x)
+    N, K = w.shape
+    R, ldx = x.shape
+    out = _out(out)
+    ks = np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_prompt_skinny(device, _p(w), _p(x), ldx, R, N, K, int(target), int(act), _p(out),
+                                                  out.shape[0], out.shape[1], int(reps), native.i32p(ks)))
+    return int(ks[0])

@@ -297,6 +297,58 @@ int fm_op_quant4(int device, const float* w, int N, int K, int gs, uint8_t* q, f
    K parts.  q_out [N][K] / scale_out [N] (optional): the codes and bf16 row scales it used. */
 int fm_op_batched_linear_q8(int device, const float* w, int N, int K, const float* x, int R, int epi,
                             float* y_q8, float* y_bf16, int* kparts, int8_t* q_out, float* scale_out);
+/* ---- the decode linears (tests/test_gpu_linear_ops.py): each hook runs ONE production launcher on
+   caller operands.  Weights w are row-major [N][K] (the hook packs them as the model loader does);
+   epi / pro are the kernels' own codes: epi 0 store, 1 residual, 2 SwiGLU (w, w2), 3 fp32, 4 fp32 K-slice
+   slabs, 5 slabs + residual finalise, 7 SwiGLU over row-interleaved 8 gate + 8 up tiles; pro 0 plain,
+   1 RMSNorm from the row, 3 RMSNorm from the producer's per-tile sums of squares.  Every output array
+   is in/out: [y_rows >= rows written][ld >= columns written], uploaded before the launch and
+   downloaded after it, so what the kernel leaves alone comes back as the caller filled it.  reps: the
+   launch is repeated that many times on the same scratch (tickets, partials, sums of squares);
+   dirty: the ticket / counter words left non-zero afterwards (a correct kernel leaves 0). */
+/* launch_linear (the 16-row MFMA tile kernel), any R: y = epilogue(x . w^T + bias).  split != 0 and
+   8 < R <= 64: partials and tickets are supplied as the batched frame does, so fm_tune "linear_fill"
+   splits K; ksb returns the slices used. */
+int fm_op_linear(int device, int precision, int epi, const float* w, const float* w2, const float* bias,
+                 const float* x, int ldx, const float* res, int ldr, int R, int N, int K, int split, float* y, int ldy,
+                 int y_rows, int reps, int* ksb, int* dirty);
+/* launch_gemv (R <= 8) on ksb K slices (> 1 only with epi 4 / 5).  idx [R][idx_ld] (optional): column
+   idx_col gathers the x rows (pro 1) or the residual rows (epi 5) from a table of idx_rows rows, indices
+   clamped into it.  pro 3: x is first finalised by a zero-weight epi-5 launch, which leaves the sums of
+   squares the prologue reads (ss_gran 1: R == 1, the statistic from the staged row instead).  Outputs:
+   y [R][N] (epi 7: [R][N / 2]; epi 4: fp32 slabs [ksb][R][ldy], bias in slice 0; epi 5: the finalised
+   rows round(res + round(x . w^T + bias)), and ss_out [N / 16][R] their per-tile sums of squares). */
+int fm_op_gemv(int device, int precision, int pro, int epi, int ksb, const float* w, const float* w2, const float* bias,
+               const float* nw, float eps, const float* x, int ldx, const int32_t* idx, int idx_ld, int idx_col,
+               int idx_rows, const float* res, int ldr, int ss_gran, int R, int N, int K, float* y, int ldy, int y_rows,
+               float* ss_out, int reps, int* dirty);
+/* launch_rowgemv (one row, bf16): kind 0 fin (y = round(res + round(w x + bias)), res row idx[idx_col] of
+   [res_rows][ldr]), 1 norm + store, 2 norm + SwiGLU (w rows 8b .. 8b+3 gate, 8b+4 .. 8b+7 up; y [N / 2]),
+   3 norm + fp32; kinds 1 / 2 gather their x row idx[idx_col] from [x_rows][ldx].  q8: w is quantised on
+   the device by the int8 rule and the codes are streamed (q_out [N][K], scale_out [N] optional). */
+int fm_op_rowgemv(int device, int kind, int q8, const float* w, const float* bias, const float* nw, float eps,
+                  const float* x, int x_rows, int ldx, const float* res, int res_rows, int ldr, const int32_t* idx,
+                  int idx_n, int idx_col, int N, int K, float* y, int y_len, int reps, int8_t* q_out, float* scale_out);
+/* launch_bstream (8 < R <= 32) on bstream_plan's geometry, returned in plan[7] = {acc, kparts, nw, spw,
+   tpi, ntm, grid} (acc 1: bsacc_kernel; fm_tune "bstream_acc" 0 or fp32: bstream_kernel).  pro 3 (bsacc,
+   epi 0 / 7): the sums of squares come from a zero-weight epi-5 launch over x.  Outputs as fm_op_gemv's,
+   slabs [kparts][R][ldy] (no bias: finalize_norm adds it), ss_out [R][ceil(N / 16)]. */
+int fm_op_bstream(int device, int precision, int pro, int epi, const float* w, const float* bias, const float* nw,
+                  float eps, const float* x, int ldx, const float* res, int ldr, int R, int N, int K, float* y, int ldy,
+                  int y_rows, float* ss_out, int reps, int* plan, int* dirty);
+/* launch_finalize_norm on caller slabs [kparts][R][lds] (fp32): x_out = round(res + round(sum + bias))
+   (wscale: round(round(sum) * wscale) inside), xn_out = RMSNorm(x_out) * nw when nw is given.  fm_tune
+   "fin_split" > 1 arms the split form as the batched frame does; split returns whether it ran, err the
+   kernel's time-out word. */
+int fm_op_finalize_norm(int device, int precision, const float* slab, int kparts, int lds, const float* bias,
+                        const float* res, int ldr, const float* nw, const float* wscale, float eps, int d, int R,
+                        float* x_out, int ldx, int x_rows, float* xn_out, int ldxn, int xn_rows, int reps, int* split,
+                        int* err, int* dirty);
+/* launch_prompt_skinny (R <= 64, bf16) on ks = prompt_skinny_ks(N, K, target) K slices (returned; with
+   out null nothing else happens): raw fp32 slabs out [ks][R][N] (ldo == N), or with act != 0 (ks 1) the
+   SwiGLU of the row-interleaved w straight to out [R][ldo >= N / 2]. */
+int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int R, int N, int K, int target, int act,
+                        float* out, int out_rows, int ldo, int reps, int* ks);
 /* the RoPE cos/sin table the library builds on the host (precompute_freqs_cis, llama.py:1003-1022):
    out [seq_len][head_dim/2][2], bf16-valued floats.  No device needed. */
 int fm_rope_table(int seq_len, int head_dim, float base, float* out);
