@@ -162,12 +162,26 @@ __device__ __forceinline__ typename Frag<T>::f bs_norm8(typename Frag<T>::f x, f
 // its two MFMAs.  A slot is 2 VGPRs, not 4, so the ring is twice as many tiles deep (capped at the
 // NTM the block can own): the bytes in flight per wave stay what they were.  Partition, step order,
 // reduction and epilogues are the bf16 form's, so the results are bit-identical to it.
+// WQ 2 (weight-only int4, fm_tune bstream_q4): the ring holds the raw code words of a.Wq4, the step-
+// granular int4 copy [tile][K/32][64 lanes][4 B] (launch_pack_q4s), one VGPR a slot, so it is four times
+// as many tiles deep (capped at NTM: every geometry but SPW 10 then holds the block's whole run, and
+// nothing is refilled).  The (scale, zero) words come from a.wsz (launch_pack_sz4: one word per (tile,
+// 128-k unit, row), 64 distinct bytes a wave load): once per tile for each of the NUW units the wave's
+// <= SPW steps can touch, issued right before that tile's first code word -- never behind it, so in-
+// order vmcnt makes no MFMA wait for more than its own slot's predecessors -- into a ring of its own,
+// one tile deeper than the code ring where that one refills (a tile's words are still read while
+// the refill of its code slots runs ahead).  Slot (t, j) takes unit (wa & 3) + j >> 2 of its tile with
+// one select and becomes Frag::dq4s's fragment: bf16(fma(q - 8, scale, zero)), the bits the bf16
+// copy holds (launch_quant4), so the results are bit-identical to the bf16 form here too.
 template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO, int WQ = 0>
 __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
     using F = Frag<T>;
-    static_assert(!WQ || (sizeof(T) == 2 && PRO == PRO_PLAIN && EPI != EPI_SLABFIN), "bsacc int8 codes: bf16, plain forms");
+    static_assert(!WQ || (sizeof(T) == 2 && PRO == PRO_PLAIN && EPI != EPI_SLABFIN), "bsacc int8 / int4 codes: bf16, plain forms");
     extern __shared__ __attribute__((aligned(16))) f32x4_t bred[];  // [NTM][NW][2][64]
-    constexpr int TPR = WQ ? (2 * TPI < NTM ? 2 * TPI : NTM) : TPI;  // ring depth in tiles
+    constexpr int RD = WQ == 2 ? 4 : (WQ ? 2 : 1);
+    constexpr int TPR = RD * TPI < NTM ? RD * TPI : NTM;  // ring depth in tiles
+    constexpr int NUW = ((SPW + 2) >> 2) + 1;             // int4: 128-k units that SPW steps from any step on can touch
+    constexpr int TZ = TPR < NTM ? TPR + 1 : TPR;         // int4: (scale, zero) ring depth in tiles
     constexpr int U = SPW * TPR;
     const unsigned long long ts0 = a.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
     unsigned long long ts1 = 0, tsx = 0;
@@ -184,17 +198,30 @@ __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
     // weights (they do not depend on X): ring slot u = (t % TPR) * SPW + j holds (tile t, step j)
     const T* wbase = a.W + ((size_t)t0 * S + wa) * 512;
     const int tl = ntl - 1, jl = nst - 1;
-    typename std::conditional<WQ != 0, u32x2_t, typename F::f>::type fa[U];
+    typename std::conditional<WQ == 2, uint32_t, typename std::conditional<WQ == 1, u32x2_t, typename F::f>::type>::type fa[U];
+    uint32_t fz[WQ == 2 ? TZ * NUW : 1];
     auto issue = [&](int t, int j) {
         const int tt = t < tl ? t : tl, jj = j < jl ? j : jl;
         const bool past = a.dummy_tail && (t > tl || j > jl);  // not this block's: one cached fragment
-        if constexpr (WQ) {  // the same (tile, step) indices into 512-byte code fragments
+        if constexpr (WQ) {  // the same (tile, step) indices into 512-byte (int4: 256-byte) code fragments
             const size_t dfrag = a.dummy_tail == 2 ? (size_t)((blockIdx.x * 8 + wave) & 255) % ((size_t)T_ * S) : 0;
             const size_t frag = past ? dfrag : (size_t)(t0 + tt) * S + wa + jj;
-            fa[(t % TPR) * SPW + j] = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(a.Wq8 + frag * 512) + lane);
+            if constexpr (WQ == 2) fa[(t % TPR) * SPW + j] = __builtin_nontemporal_load(a.Wq4 + frag * 64 + lane);
+            else fa[(t % TPR) * SPW + j] = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(a.Wq8 + frag * 512) + lane);
         } else {
             const T* dsrc = a.W + (a.dummy_tail == 2 ? (size_t)((blockIdx.x * 8 + wave) & 255) % ((size_t)T_ * S) * 512 : 0);
             fa[(t % TPI) * SPW + j] = F::template load_w<true>(past ? dsrc : wbase + ((size_t)tt * S + jj) * 512, lane);
+        }
+    };
+    // int4: tile t's (scale, zero) words of units (wa >> 2) + i; a unit past the wave's last step re-reads
+    // the last one's line (its slot is never selected)
+    const int zo = wa & 3;
+    auto issue_sz = [&](int t) {
+        if constexpr (WQ == 2) {
+            const int tt = t < tl ? t : tl, ub = wa >> 2, ul = (wa + jl) >> 2;
+#pragma unroll
+            for (int i = 0; i < NUW; ++i)
+                fz[(t % TZ) * NUW + i] = a.wsz[((size_t)(t0 + tt) * (a.K >> 7) + (ub + i < ul ? ub + i : ul)) * 16 + r];
         }
     };
     // X operands.  PRO_PRENORM also loads the norm weight and the producer's per-tile sums of squares
@@ -227,12 +254,18 @@ __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
                 }
         }
     };
-    if (a.xfirst) load_x();
+    // (WQ 2 issues X first whatever a.xfirst says: behind a run-time choice the two orders' wait counts
+    // merge where the paths join, and with a ring that is the whole run the first MFMAs would wait for
+    // most of it)
+    const bool xfirst = WQ == 2 || a.xfirst;
+    if (xfirst) load_x();
 #pragma unroll
-    for (int t = 0; t < TPR; ++t)
+    for (int t = 0; t < TPR; ++t) {
+        issue_sz(t);
 #pragma unroll
         for (int j = 0; j < SPW; ++j) issue(t, j);
-    if (!a.xfirst) load_x();
+    }
+    if (!xfirst) load_x();
     if constexpr (PRO == PRO_PRENORM) {
         // 1/rms of each X row (wave w: rows w, w + 8, w + 16, w + 24), then every lane's two rows from LDS
         __shared__ float rs_s[32];
@@ -265,7 +298,14 @@ __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
 #pragma unroll
         for (int j = 0; j < SPW; ++j) {
             const int u = (t % TPR) * SPW + j;
-            if constexpr (WQ) {
+            if constexpr (WQ == 2) {
+                const int zl = (t % TZ) * NUW + (j >> 2);  // step wa + j is in unit (wa >> 2) + (zo + j >> 2)
+                uint32_t z = fz[zl];
+                if ((j & 3) != 0) z = zo + (j & 3) >= 4 ? fz[zl + 1] : z;  // (j & 3) == 0: zl + 1 may be past NUW
+                const typename F::f w = F::dq4s(fa[u], __uint_as_float(z << 16), __uint_as_float(z & 0xffff0000u));
+                acc[t][0] = F::mma(w, xa[j], acc[t][0]);
+                acc[t][1] = F::mma(w, xb[j], acc[t][1]);
+            } else if constexpr (WQ) {
                 const typename F::f w = F::dq8s(fa[u]);
                 acc[t][0] = F::mma(w, xa[j], acc[t][0]);
                 acc[t][1] = F::mma(w, xb[j], acc[t][1]);
@@ -273,7 +313,10 @@ __global__ __launch_bounds__(512) void bsacc_kernel(BstreamArgs<T> a) {
                 acc[t][0] = F::mma(fa[u], xa[j], acc[t][0]);
                 acc[t][1] = F::mma(fa[u], xb[j], acc[t][1]);
             }
-            if (t + TPR < NTM) issue(t + TPR, j);
+            if (t + TPR < NTM) {
+                if (j == 0) issue_sz(t + TPR);
+                issue(t + TPR, j);
+            }
             __builtin_amdgcn_sched_barrier(0);  // each refill right behind its consumer
             if (t == 0 && j == 0 && a.dbg) ts1 = __builtin_amdgcn_s_memrealtime();
         }
@@ -736,11 +779,15 @@ static void bsacc_attr_all() {
     bsacc_attr<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN>();
     bsacc_attr<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN>();
     bsacc_attr<T, SPW, TPI, NTM, EPI_SLABFIN, PRO_PLAIN>();
-    if constexpr (sizeof(T) == 2) {  // the int8-code forms (bsacc_q8_ok)
+    if constexpr (sizeof(T) == 2) {  // the int8-code and int4-code forms (bsacc_q8_ok / bsacc_q4_ok)
         bsacc_attr<T, SPW, TPI, NTM, EPI_STORE, PRO_PLAIN, 1>();
         bsacc_attr<T, SPW, TPI, NTM, EPI_SWIGLU8, PRO_PLAIN, 1>();
         bsacc_attr<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN, 1>();
         bsacc_attr<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN, 1>();
+        bsacc_attr<T, SPW, TPI, NTM, EPI_STORE, PRO_PLAIN, 2>();
+        bsacc_attr<T, SPW, TPI, NTM, EPI_SWIGLU8, PRO_PLAIN, 2>();
+        bsacc_attr<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN, 2>();
+        bsacc_attr<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN, 2>();
     }
 }
 template <typename T, int SPW, int TPI, int NTM, int EPI, int PRO, int WQ = 0>
@@ -748,15 +795,16 @@ static void bsacc_launch(hipStream_t s, const BstreamArgs<T>& a, int G, int NW) 
     const size_t lds = (size_t)NTM * NW * 2 * 64 * sizeof(f32x4_t);
     bsacc_kernel<T, SPW, TPI, NTM, EPI, PRO, WQ><<<dim3(G), dim3(NW * 64), lds, s>>>(a);
 }
-// the default batched frame's forms on the int8 codes (a.Wq8 set: launch_bstream checked bsacc_q8_ok)
-template <typename T, int SPW, int TPI, int NTM>
-static void bsacc_go_q8(hipStream_t s, const BstreamArgs<T>& a, int epi, int G, int NW) {
+// the default batched frame's forms on the int8 codes (WQ 1; a.Wq8 set: launch_bstream checked
+// bsacc_q8_ok) or the int4 codes (WQ 2; a.Wq4 and a.wsz set, bsacc_q4_ok)
+template <typename T, int SPW, int TPI, int NTM, int WQ>
+static void bsacc_go_q(hipStream_t s, const BstreamArgs<T>& a, int epi, int G, int NW) {
     switch (epi) {
-        case EPI_STORE: bsacc_launch<T, SPW, TPI, NTM, EPI_STORE, PRO_PLAIN, 1>(s, a, G, NW); break;
-        case EPI_SWIGLU8: bsacc_launch<T, SPW, TPI, NTM, EPI_SWIGLU8, PRO_PLAIN, 1>(s, a, G, NW); break;
-        case EPI_F32: bsacc_launch<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN, 1>(s, a, G, NW); break;
-        case EPI_SLAB: bsacc_launch<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN, 1>(s, a, G, NW); break;
-        default: FMCHECK(false, "bsacc: no int8-code form of this epilogue");
+        case EPI_STORE: bsacc_launch<T, SPW, TPI, NTM, EPI_STORE, PRO_PLAIN, WQ>(s, a, G, NW); break;
+        case EPI_SWIGLU8: bsacc_launch<T, SPW, TPI, NTM, EPI_SWIGLU8, PRO_PLAIN, WQ>(s, a, G, NW); break;
+        case EPI_F32: bsacc_launch<T, SPW, TPI, NTM, EPI_F32, PRO_PLAIN, WQ>(s, a, G, NW); break;
+        case EPI_SLAB: bsacc_launch<T, SPW, TPI, NTM, EPI_SLAB, PRO_PLAIN, WQ>(s, a, G, NW); break;
+        default: FMCHECK(false, "bsacc: no code-streaming form of this epilogue");
     }
 }
 template <typename T, int SPW, int TPI, int NTM>
@@ -787,10 +835,15 @@ bool bsacc_q8_ok(const BstreamPlan& p, int epi, int pro, size_t esz) {
            (epi == EPI_STORE || epi == EPI_SWIGLU8 || epi == EPI_F32 || epi == EPI_SLAB);
 }
 
+bool bsacc_q4_ok(const BstreamPlan& p, int epi, int pro, size_t esz, int K) {
+    return bsacc_q8_ok(p, epi, pro, esz) && K % 128 == 0;
+}
+
 template <typename T> bool launch_bstream(hipStream_t s, const BstreamArgs<T>& a0, int epi, const BstreamPlan& p) {
     if (!p.ok) return false;
     BstreamArgs<T> a = a0;
     if (!bsacc_q8_ok(p, epi, a.pro, sizeof(T))) a.Wq8 = nullptr;  // no int8-code form: the bf16 fragments
+    if (!a.wsz || !bsacc_q4_ok(p, epi, a.pro, sizeof(T), a.K)) a.Wq4 = nullptr;  // nor an int4-code form
     a.kparts = p.kparts;
     a.dummy_tail = fm_tuning().bs_dummy;
     a.xfirst = fm_tuning().bs_xfirst;
@@ -800,7 +853,8 @@ template <typename T> bool launch_bstream(hipStream_t s, const BstreamArgs<T>& a
             FMCHECK(epi != EPI_SWIGLU8 || a.N % 16 == 0, "bsacc: SwiGLU8 needs whole interleaved tiles");
 #define BSA(SPW, TPI, NTM)                                               \
     if (p.spw == SPW && p.tpi == TPI && p.ntm == NTM) {                  \
-        if (a.Wq8) bsacc_go_q8<T, SPW, TPI, NTM>(s, a, epi, p.grid, p.nw); \
+        if (a.Wq4) bsacc_go_q<T, SPW, TPI, NTM, 2>(s, a, epi, p.grid, p.nw); \
+        else if (a.Wq8) bsacc_go_q<T, SPW, TPI, NTM, 1>(s, a, epi, p.grid, p.nw); \
         else bsacc_go<T, SPW, TPI, NTM>(s, a, epi, p.grid, p.nw);        \
         return true;                                                     \
     }

@@ -14,6 +14,8 @@
 //                           of k-step 2u + 1) as two exact T fragments (weight-only int8)
 //   dq8s(raw)               8 int8 weights (one k-step of a lane, the step-granular int8 copy of
 //                           the batched stream) as one exact bf16 fragment: dq8's arithmetic
+//   dq4(w, s, z)            8 int4 codes and their group's (scale, zero) as one bf16 fragment
+//   dq4s(w, s, z)           dq4's bits by the batched stream's cheaper arithmetic
 #pragma once
 #include "fm_common.h"
 
@@ -71,6 +73,25 @@ template <> struct Frag<bf16_t> {
             const float v1 = __fmaf_rn((float)((w >> (8 * p + 4)) & 15u) - 8.f, s, z);
             o[p] = (uint32_t)__builtin_bit_cast(uint16_t, static_cast<__bf16>(v0)) |
                    ((uint32_t)__builtin_bit_cast(uint16_t, static_cast<__bf16>(v1)) << 16);
+        }
+        return o;
+    }
+    // dq4's 8 values, bit for bit, without its int -> float conversions (the batched stream's
+    // expansion, bsacc_kernel WQ 2).  Nibble n (0..3) of a half word, kept where it is and ORed into
+    // the mantissa of 2^(23 - 4n), reads as the float 2^(23 - 4n) + q; subtracting 2^(23 - 4n) + 8
+    // (both operands multiples of 1, the difference below 16: exact) leaves (float)q - 8.f, dq4's own
+    // first operand, and the fma and the RNE rounding to bf16 are dq4's.
+    static __device__ __forceinline__ f dq4s(uint32_t w, float s, float z) {
+        f o;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            const uint32_t h = p < 2 ? w : w >> 16;  // nibbles 4..7 as 0..3: bit 23 up is the exponent
+            const int n = 2 * (p & 1);  // the word's two values side by side: packed fp32 add and fma
+            const f32x2_t m = {__uint_as_float((h & (15u << (4 * n))) | ((uint32_t)(150 - 4 * n) << 23)),
+                               __uint_as_float((h & (15u << (4 * n + 4))) | ((uint32_t)(146 - 4 * n) << 23))};
+            const f32x2_t c = {(float)(1 << (23 - 4 * n)) + 8.f, (float)(1 << (19 - 4 * n)) + 8.f};
+            const f32x2_t v = __builtin_elementwise_fma(m - c, (f32x2_t){s, s}, (f32x2_t){z, z});
+            o[p] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));  // RNE, v[0] in the low half
         }
         return o;
     }

@@ -46,6 +46,12 @@ void launch_pack_q4(hipStream_t s, const uint8_t* q, int N, int K, uint8_t* dst)
 // ones in the low half at nibble e / 2, the odd ones in the high half (fm_rowgemv.hip QM 2)
 void launch_pack_q4_rows(hipStream_t s, const uint8_t* q, int N, int K, uint32_t* dst);
 void launch_pack_sz4(hipStream_t s, const uint32_t* sz, int N, int K, int gs, uint32_t* dst);
+// int4 codes row-major [N][K] (one byte per code) -> the batched stream's step-granular layout
+// (fm_bstream.hip, 8 < R <= 32): [ceil(N/16)][K/32] fragments of 256 B, lane l's word (row l & 15)
+// holding its 8 codes of that k-step, k = 8 * (l >> 4) + e in nibble e (Frag::dq4's order) -- the
+// packed bf16 fragments' index order at half a byte per weight.  Rows past N: code 8 (with the
+// (scale, zero) = 0 of launch_pack_sz4 they dequantise to 0)
+void launch_pack_q4s(hipStream_t s, const uint8_t* q, int N, int K, uint32_t* dst);
 
 template <typename T> struct LinearArgs {
     const T* W;      // [N(padded to 16)][K] row-major (nn.Linear layout)
@@ -402,6 +408,11 @@ template <typename T> struct BstreamArgs {
     // weight-only int8 (fm_tune bstream_q8): the step-granular code copy of W, [tiles][K/32][64 lanes][8 B]
     // (launch_pack_q8s).  Set: bsacc_kernel streams it instead of W where bsacc_q8_ok, else W as ever.
     const unsigned char* Wq8 = nullptr;
+    // weight-only int4 (fm_tune bstream_q4): the step-granular code copy of W, [tiles][K/32][64 lanes] words
+    // (launch_pack_q4s), and each (tile, 128-k unit, row)'s (scale, zero) (launch_pack_sz4).  Both set:
+    // bsacc_kernel streams them instead of W where bsacc_q4_ok, else W as ever.
+    const uint32_t* Wq4 = nullptr;
+    const uint32_t* wsz = nullptr;
 };
 struct BstreamPlan {
     bool ok = false;
@@ -411,6 +422,8 @@ struct BstreamPlan {
 BstreamPlan bstream_plan(int N, int K, int R, int epi, size_t esz);
 // whether launch_bstream has an int8-code form (BstreamArgs::Wq8) for this plan, epilogue and prologue
 bool bsacc_q8_ok(const BstreamPlan& p, int epi, int pro, size_t esz);
+// ... and an int4-code form (BstreamArgs::Wq4 / wsz): the same forms, K in whole 128-k units
+bool bsacc_q4_ok(const BstreamPlan& p, int epi, int pro, size_t esz, int K);
 void bsacc_init();  // kernel attributes (> 64 KiB LDS) of every bsacc_kernel, outside any capture
 template <typename T> bool launch_bstream(hipStream_t s, const BstreamArgs<T>& a, int epi, const BstreamPlan& p);
 // x_out = round(res + round(sum of kparts slabs + bias)); if nw: xn_out = RMSNorm(x_out) * nw

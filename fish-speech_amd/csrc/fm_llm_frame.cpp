@@ -196,6 +196,13 @@ template <typename T> struct Run {
         if (q) a.wscale = (const T*)q->scale;
         // weight-only int8 (fm_tune bstream_q8): the accumulating kernel streams the codes where it has the form
         if (q && q->q8s && fm_tuning().bstream_q8 && bsacc_q8_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E)) a.Wq8 = q->q8s;
+        // weight-only int4 (fm_tune bstream_q4; int4_stream 0 keeps the whole model on its dequantised weights):
+        // the 4-bit codes and their (scale, zero) table
+        if (q && q->q4s && q->sz && fm_tuning().bstream_q4 && fm_tuning().int4_stream &&
+            bsacc_q4_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E, K)) {
+            a.Wq4 = q->q4s;
+            a.wsz = q->sz;
+        }
         a.dbg = fm_tuning().dbg;
         if (ex) {
             a.pro = ex->pro;
@@ -209,7 +216,9 @@ template <typename T> struct Run {
             a.ss_out = ex->ss_out;
             a.tickets = m->tickets;
         }
-        const int64_t wbytes = a.Wq8 ? (int64_t)N * K + (int64_t)N * 2 : (int64_t)N * K * E;  // codes + row scales
+        const int64_t wbytes = a.Wq4   ? (int64_t)N * K / 2 + (int64_t)N * (K / 128) * 4  // codes + (scale, zero) words
+                               : a.Wq8 ? (int64_t)N * K + (int64_t)N * 2                  // codes + row scales
+                                       : (int64_t)N * K * E;
         const int64_t bytes = wbytes + (int64_t)R * K * E +
                               (int64_t)R * N * (epi == EPI_SLAB ? 4 * p.kparts : (epi == EPI_F32 ? 4 : E));
         const double flops = 2.0 * R * N * K;

@@ -338,6 +338,26 @@ void launch_pack_q4(hipStream_t s, const uint8_t* q, int N, int K, uint8_t* dst)
     const int64_t n = (int64_t)((N + 15) / 16) * (K / 128) * 64;
     pack_q4_kernel<<<(int)std::min<int64_t>(FM_CEIL(n, 256), 16384), 256, 0, s>>>(q, N, K, dst);
 }
+// one thread per (fragment, lane): one word = the 8 codes of one k-step of row (l & 15), nibble e = k e
+__global__ void pack_q4s_kernel(const uint8_t* __restrict__ q, int N, int K, uint32_t* __restrict__ dst) {
+    const int S = K >> 5;
+    const int64_t n = (int64_t)((N + 15) / 16) * S * 64;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t frag = i >> 6;
+        const int l = (int)(i & 63);
+        const int t = (int)(frag / S), sidx = (int)(frag - (int64_t)t * S);
+        const int row = 16 * t + (l & 15);
+        uint32_t v = 0;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            v |= (uint32_t)(row < N ? q[(size_t)row * K + 32 * sidx + 8 * (l >> 4) + e] & 15 : 8) << (4 * e);
+        dst[i] = v;
+    }
+}
+void launch_pack_q4s(hipStream_t s, const uint8_t* q, int N, int K, uint32_t* dst) {
+    const int64_t n = (int64_t)((N + 15) / 16) * (K / 32) * 64;
+    pack_q4s_kernel<<<(int)std::min<int64_t>(FM_CEIL(n, 256), 16384), 256, 0, s>>>(q, N, K, dst);
+}
 __global__ void pack_sz4_kernel(const uint32_t* __restrict__ sz, int N, int K, int gs, uint32_t* __restrict__ dst) {
     const int U = K >> 7, ng = K / gs;
     const int64_t n = (int64_t)((N + 15) / 16) * U * 16;

@@ -120,6 +120,9 @@ struct fm_llm {
         // int8, bf16, max_slots > 8: the step-granular code copy the batched linears stream
         // (launch_pack_q8s; its own allocation, whatever row_copies frees)
         const unsigned char* q8s = nullptr;
+        // int4 (sz set), bf16, max_slots > 8: the step-granular code copy the batched linears stream with
+        // sz (launch_pack_q4s; its own allocation too)
+        const uint32_t* q4s = nullptr;
     };
     std::map<const void*, QInfo> qmap;
     std::map<const void*, void*> rowmajor;  // packed wo / w2 / wqkv -> row-major bf16 copy (int8 / int4: codes)

@@ -132,7 +132,17 @@ static fm_llm::QInfo pack_q4_dev(fm_llm* m, const void* q, const void* sz, int r
     HIPCHK(hipGetLastError());
     m->allocs.push_back(dq);
     m->allocs.push_back(ds);
-    return fm_llm::QInfo{(const unsigned char*)dq, nullptr, (const uint32_t*)ds};
+    // the batched linears' step-granular copy of the same codes (they stream it with ds): only where
+    // bsacc_kernel can take it -- bf16, a handle with more than GEMV_MAX_ROWS slots; a max_slots <= 8
+    // handle allocates nothing here.  Its own allocation: row_copies 0 frees none of it.
+    void* d4 = nullptr;
+    if (m->prec == FM_PREC_BF16 && m->max_slots > GEMV_MAX_ROWS) {
+        HIPCHK(hipMalloc(&d4, tiles * 16 * cols / 2));
+        launch_pack_q4s(m->stream, (const uint8_t*)q, rows, cols, (uint32_t*)d4);
+        HIPCHK(hipGetLastError());
+        m->allocs.push_back(d4);
+    }
+    return fm_llm::QInfo{(const unsigned char*)dq, nullptr, (const uint32_t*)ds, nullptr, (const uint32_t*)d4};
 }
 
 // int8 mode, before packing: every quantized linear ends with t.p = T(q) row-major (what the

@@ -15,6 +15,8 @@
 //   fm_op_embed     the Dual-AR input embedding (llama.py:399-420)
 //   fm_op_batched_linear_q8  the batched decode linear (bsacc_kernel) on weight-only int8 codes and on
 //                   their bf16 fragment copy (fm_tune bstream_q8)
+//   fm_op_batched_linear_q4  the same on weight-only int4 codes + group (scale, zero) and on the bf16
+//                   fragments of the dequantised weights (fm_tune bstream_q4)
 //   fm_op_linear / fm_op_gemv / fm_op_rowgemv / fm_op_bstream / fm_op_finalize_norm / fm_op_prompt_skinny
 //                   the decode linears, one production launcher each (launch_linear, launch_gemv, launch_rowgemv,
 //                   launch_bstream on bstream_plan's geometry, launch_finalize_norm, launch_prompt_skinny): outputs
@@ -944,6 +946,77 @@ int fm_op_batched_linear_q8(int device, const float* w, int N, int K, const floa
             FMCHECK(launch_bstream<bf16_t>(g.s, a, epi, p), "bstream: no kernel for the plan");
             HIPCHK(hipGetLastError());
             float* out = form ? y_q8 : y_bf16;
+            if (f32) {
+                HIPCHK(hipMemcpyAsync(out, dy, ny * 4, hipMemcpyDeviceToHost, g.s));
+                HIPCHK(hipStreamSynchronize(g.s));
+            } else {
+                download<bf16_t>((const bf16_t*)dy, ny, out, g.s);
+            }
+        }
+        if (kparts) *kparts = p.kparts;
+    });
+}
+
+// weight-only int4 on the batched decode linear: the device quantizer (launch_quant4, group size gs),
+// then the same bstream plan / launch on the packed bf16 fragments of the weights it dequantised to
+// and on the step-granular int4 copy with the (scale, zero) table (BstreamArgs::Wq4 / wsz).  Outputs
+// as fm_op_batched_linear_q8's.
+int fm_op_batched_linear_q4(int device, const float* w, int N, int K, int gs, const float* x, int R, int epi,
+                            float* y_q4, float* y_bf16, int* kparts, uint8_t* q_out, float* scale_out,
+                            float* zero_out, float* w_deq) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y_q4 && y_bf16 && N >= 1 && K >= 128 && R > 8 && R <= 32, "bad arguments");
+        FMCHECK(gs >= 128 && gs % 128 == 0 && K % 128 == 0 && K % gs == 0,
+                "the int4 batched stream needs a group size and K in whole 128-k units, K a multiple of the group size");
+        FMCHECK(epi == EPI_STORE || epi == EPI_F32 || epi == EPI_SLAB || (epi == EPI_SWIGLU8 && N % 16 == 0),
+                "epi must be 0 (store), 3 (fp32), 4 (slabs) or 7 (SwiGLU, whole 16-row tiles)");
+        StreamGuard g(device);
+        DevBufs b(g.s);
+        bsacc_init();
+        const BstreamPlan p = bstream_plan(N, K, R, epi, 2);
+        FMCHECK(bsacc_q4_ok(p, epi, PRO_PLAIN, 2, K), "no int4-code batched kernel for this shape");
+        const int Np = (N + 15) / 16 * 16, ng = K / gs;
+        bf16_t* dw = (bf16_t*)b.alloc((size_t)Np * K * 2);
+        {
+            bf16_t* t = b.upload<bf16_t>(w, (size_t)N * K);
+            HIPCHK(hipMemcpyAsync(dw, t, (size_t)N * K * 2, hipMemcpyDeviceToDevice, g.s));
+        }
+        uint8_t* dq = (uint8_t*)b.alloc((size_t)Np * K);
+        uint32_t* dsz = (uint32_t*)b.alloc((size_t)Np * ng * 4);
+        launch_quant4(g.s, dw, N, K, gs, dq, dsz);  // dw <- bf16(fma(q - 8, scale, zero))
+        bf16_t* pk = (bf16_t*)b.alloc((size_t)Np * K * 2);
+        launch_pack<bf16_t>(g.s, dw, N, K, pk);
+        uint32_t* pq = (uint32_t*)b.alloc((size_t)Np * K / 2);
+        launch_pack_q4s(g.s, dq, N, K, pq);
+        uint32_t* sz4 = (uint32_t*)b.alloc((size_t)(Np / 16) * (K / 128) * 16 * 4);
+        launch_pack_sz4(g.s, dsz, N, K, gs, sz4);
+        HIPCHK(hipGetLastError());
+        if (q_out) HIPCHK(hipMemcpyAsync(q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, g.s));
+        if (w_deq) download<bf16_t>(dw, (size_t)N * K, w_deq, g.s);
+        if (scale_out || zero_out) {
+            std::vector<uint32_t> hs((size_t)N * ng);
+            HIPCHK(hipMemcpyAsync(hs.data(), dsz, hs.size() * 4, hipMemcpyDeviceToHost, g.s));
+            HIPCHK(hipStreamSynchronize(g.s));
+            for (size_t i = 0; i < hs.size(); ++i) {
+                const uint32_t us = hs[i] << 16, uz = hs[i] & 0xffff0000u;
+                if (scale_out) memcpy(&scale_out[i], &us, 4);
+                if (zero_out) memcpy(&zero_out[i], &uz, 4);
+            }
+        }
+        bf16_t* dx = b.upload<bf16_t>(x, (size_t)R * K);
+        const int No = epi == EPI_SWIGLU8 ? N / 2 : N;
+        const bool f32 = epi == EPI_F32 || epi == EPI_SLAB;
+        const size_t ny = (size_t)(epi == EPI_SLAB ? p.kparts : 1) * R * No;
+        for (int form = 0; form < 2; ++form) {
+            void* dy = b.alloc(ny * (f32 ? 4 : 2));
+            BstreamArgs<bf16_t> a{pk, nullptr, dx, K, R, N, K, f32 ? nullptr : (bf16_t*)dy, No, f32 ? (float*)dy : nullptr};
+            if (form) {
+                a.Wq4 = pq;
+                a.wsz = sz4;
+            }
+            FMCHECK(launch_bstream<bf16_t>(g.s, a, epi, p), "bstream: no kernel for the plan");
+            HIPCHK(hipGetLastError());
+            float* out = form ? y_q4 : y_bf16;
             if (f32) {
                 HIPCHK(hipMemcpyAsync(out, dy, ny * 4, hipMemcpyDeviceToHost, g.s));
                 HIPCHK(hipStreamSynchronize(g.s));

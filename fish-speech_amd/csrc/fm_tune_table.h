@@ -86,6 +86,9 @@ FM_KNOB(fin8, 1, FM_BOOL)                  // finalize_norm: all eight K parts' 
 FM_KNOB(fin_split, 0, FM_RANGE(0, 16))     // batched finalize_norm: each row over this many blocks (0 / 1: one block per row)
 FM_KNOB(bstream_q8, 1, FM_BOOL)            // weight-only int8, 8 < R <= 32: 1 bsacc_kernel streams the int8 codes, 0 their bf16 fragment copy
                                            // (bit-identical; int8 B=32 frame 6.441 -> 5.761 ms, the bf16 model's 6.184; profiles/b32_int8.md)
+FM_KNOB(bstream_q4, 1, FM_BOOL)            // weight-only int4 (group size a multiple of 128), 8 < R <= 32: 1 bsacc_kernel streams the 4-bit codes and their
+                                           // (scale, zero) words, 0 the dequantised bf16 fragment copy (bit-identical; int4 B=32 frame 6.343 -> 5.848 ms;
+                                           // profiles/b32_int4.md); int4_stream 0 switches it off too
 FM_KNOB(int4_stream, 1, FM_BOOL)           // weight-only int4: 1 the batch <= 8 GEMVs stream the 4-bit codes, 0 the dequantised bf16 copy
 FM_KNOB(fw_delay, 0, FM_RANGE(0, 1000))    // fattn_wo: FattnWoArgs::delay (10-ns ticks)
 FM_KNOB(fw_cheap, 0, FM_BOOL)              // fattn_wo: FattnWoArgs::cheap

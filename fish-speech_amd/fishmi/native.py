@@ -29,7 +29,7 @@ ABI_SYMBOLS = [
     "fm_codec_stream_open", "fm_codec_stream_decode", "fm_codec_stream_rewind", "fm_codec_stream_close",
     "fm_codec_profile_read", "fm_codec_debug_read", "fm_codec_enable_encoder", "fm_codec_encode",
     "fm_codec_close", "fm_llm_force", "fm_llm_read_logits", "fm_op_rmsnorm", "fm_op_qk_rope", "fm_op_decode_attn", "fm_op_prompt_attn",
-    "fm_op_embed", "fm_op_quant4", "fm_op_batched_linear_q8", "fm_rope_table",
+    "fm_op_embed", "fm_op_quant4", "fm_op_batched_linear_q8", "fm_op_batched_linear_q4", "fm_rope_table",
     "fm_op_linear", "fm_op_gemv", "fm_op_rowgemv", "fm_op_bstream", "fm_op_finalize_norm", "fm_op_prompt_skinny",
     "fm_llm_prefix_save", "fm_llm_prefix_load", "fm_llm_prefix_drop", "fm_llm_prefix_info", "fm_llm_prefill_batch_at",
 ]
@@ -154,6 +154,8 @@ def lib():
                                pf32, pf32]
     L.fm_op_batched_linear_q8.argtypes = [i32, pf32, i32, i32, pf32, i32, i32, pf32, pf32, pi32,
                                           ctypes.POINTER(ctypes.c_int8), pf32]
+    L.fm_op_batched_linear_q4.argtypes = [i32, pf32, i32, i32, i32, pf32, i32, i32, pf32, pf32, pi32,
+                                          ctypes.POINTER(ctypes.c_uint8), pf32, pf32, pf32]
     L.fm_rope_table.argtypes = [i32, i32, f32, pf32]
     L.fm_op_linear.argtypes = [i32, i32, i32, pf32, pf32, pf32, pf32, i32, pf32, i32, i32, i32, i32, i32, pf32, i32,
                                i32, i32, pi32, pi32]

@@ -316,3 +316,34 @@ def prompt_skinny(w, x, out, target, act=False, reps=1, device=0):
     native.check(native.lib().fm_op_prompt_skinny(device, _p(w), _p(x), ldx, R, N, K, int(target), int(act), _p(out),
                                                   out.shape[0], out.shape[1], int(reps), native.i32p(ks)))
     return int(ks[0])
+
+
+def batched_linear_q4(w, x, epi, gs=128, device=0):
+    """fm_op_batched_linear_q4: the batched decode linear (8 < R <= 32 rows of x, bf16) on the device-
+    quantised int4 form of w [N][K] (groups of gs along K; gs and K multiples of 128), once streaming
+    the 4-bit codes + (scale, zero) words and once the bf16 fragments of the dequantised weights.
+    Returns (y_q4, y_bf16, kparts, q [N][K] uint8, scale [N][K/gs], zero [N][K/gs], w_deq [N][K]);
+    the outputs are shaped as batched_linear_q8's."""
+    w = np.ascontiguousarray(w, np.float32)
+    N, K = w.shape
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+    R = x.shape[0]
+    No = N // 2 if epi == EPI_SWIGLU8 else N
+    cap = 8 if epi == EPI_SLAB else 1  # K parts at most (bsacc_plan)
+    y4 = np.zeros((cap, R, No), np.float32)
+    yb = np.zeros((cap, R, No), np.float32)
+    kp = np.zeros(1, np.int32)
+    ng = max(K // gs, 1) if gs > 0 else 1
+    q = np.zeros((N, K), np.uint8)
+    sc = np.zeros((N, ng), np.float32)
+    zr = np.zeros((N, ng), np.float32)
+    wd = np.zeros((N, K), np.float32)
+    native.check(native.lib().fm_op_batched_linear_q4(device, native.f32p(w), N, K, int(gs), native.f32p(x), R, int(epi),
+                                                      native.f32p(y4), native.f32p(yb), native.i32p(kp),
+                                                      q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                      native.f32p(sc), native.f32p(zr), native.f32p(wd)))
+    k = int(kp[0])
+    if epi == EPI_SLAB:
+        return (y4.reshape(-1)[:k * R * No].reshape(k, R, No), yb.reshape(-1)[:k * R * No].reshape(k, R, No), k, q, sc,
+                zr, wd)
+    return y4[0], yb[0], k, q, sc, zr, wd

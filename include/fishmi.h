@@ -222,6 +222,11 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    "bstream_q8" 0|1 (weight-only int8 bf16 models opened with more than 8 slots: 1, the default, the
    batched decode linears stream the int8 codes -- bit-identical outputs, half the weight bytes -- 0
    the bf16 copy of the codes; inert for every other model).
+   "bstream_q4" 0|1 (weight-only int4 bf16 models with a group size that is a multiple of 128, opened
+   with more than 8 slots: 1, the default, the batched decode linears stream the 4-bit codes and their group
+   (scale, zero) words -- bit-identical outputs, 0.28x the weight bytes -- 0 the dequantised bf16
+   copy; inert for every other model, under "int4_stream" 0, "bstream_acc" 0 and on the "bstream_chain"
+   forms).
    "rowgemv" / "rowgemv_q4" bits, "row_copies" 0|1 (0: finalize keeps only the row-major weight
    copies those bits select).  "rowgemv" 0..127, default 123: bits 0-4 put wo / w2, wqkv, w1 || w3,
    the codebook head and the first layers' wqkv on the row-block GEMV; bit 5 (32): the first fast
@@ -349,6 +354,17 @@ int fm_op_finalize_norm(int device, int precision, const float* slab, int kparts
    SwiGLU of the row-interleaved w straight to out [R][ldo >= N / 2]. */
 int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int R, int N, int K, int target, int act,
                         float* out, int out_rows, int ldo, int reps, int* ks);
+/* Weight-only int4 on the batched decode linear (8 < R <= 32, bf16; fm_tune "bstream_q4"): quantises
+   the bf16-valued w [N][K] on the device with the int4 group rule (quantize.py:57-160, groups of gs
+   along K), packs the dequantised bf16 weights, the step-granular codes and the (scale, zero) table,
+   and runs the batched linear's plan once per form: y_q4 from the streamed 4-bit codes, y_bf16 from
+   the bf16 fragments.  x, epi, the output shapes and kparts as fm_op_batched_linear_q8 (no scale
+   epilogue).  Optional outputs: q_out [N][K] codes 0..15, scale_out / zero_out [N][K/gs] (bf16-valued),
+   w_deq [N][K] the dequantised bf16 weights.  FM_ERR_ARG unless gs and K are multiples of 128, K a
+   multiple of gs, and the shape has an int4-code kernel. */
+int fm_op_batched_linear_q4(int device, const float* w, int N, int K, int gs, const float* x, int R, int epi,
+                            float* y_q4, float* y_bf16, int* kparts, uint8_t* q_out, float* scale_out,
+                            float* zero_out, float* w_deq);
 /* the RoPE cos/sin table the library builds on the host (precompute_freqs_cis, llama.py:1003-1022):
    out [seq_len][head_dim/2][2], bf16-valued floats.  No device needed. */
 int fm_rope_table(int seq_len, int head_dim, float base, float* out);
