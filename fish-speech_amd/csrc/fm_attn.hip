@@ -1004,7 +1004,9 @@ __global__ __launch_bounds__(256) void fast_attn_fused_kernel(FastFusedArgs<T> a
 // sampler: radix-select top-K
 // =========================================================================================
 __device__ __forceinline__ uint32_t fkey(float v) {
-    const uint32_t u = __float_as_uint(v);
+    // -0.0 keys as +0.0: the reference sorts by float comparison, so the two zeros tie (lower id first)
+    const uint32_t u0 = __float_as_uint(v);
+    const uint32_t u = u0 == 0x80000000u ? 0u : u0;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ bool cbetter(float v, int id, float bv, int bid) {
@@ -1777,7 +1779,7 @@ template <typename T> void launch_sample_radix(hipStream_t s, const SampleArgs& 
     // 160 KiB (sample_init, run at model finalize outside any capture)
     const size_t lds = std::max(sizeof(float) * a.Nl, sizeof(uint64_t) * (size_t)sw_pow2(a.Nl));
     FMCHECK(lds + 8 * 1024 <= 160 * 1024, "sampler: vocabulary too wide for the LDS row");
-    if (a.Nl <= 256 * SF_PER && fm_tuning().sampler_fast) {
+    if (a.Nl <= sample_fast_max_row() && fm_tuning().sampler_fast) {
         SampleArgs b = a;
         b.kth_fast = fm_tuning().sampler_kth;
         sample_fast_kernel<T><<<R, 256, lds, s>>>(b);
@@ -1795,6 +1797,7 @@ template void launch_fast_attn2<bf16_t>(hipStream_t, const FastFusedArgs<bf16_t>
 template void launch_fast_attn2<float>(hipStream_t, const FastFusedArgs<float>&, int);
 template void launch_fast_attn_fused<bf16_t>(hipStream_t, const FastFusedArgs<bf16_t>&, int);
 template void launch_fast_attn_fused<float>(hipStream_t, const FastFusedArgs<float>&, int);
+int sample_fast_max_row() { return 256 * SF_PER; }
 void sample_init() {
     const void* k[] = {reinterpret_cast<const void*>(&sample_fast_kernel<bf16_t>),
                        reinterpret_cast<const void*>(&sample_radix_kernel<bf16_t>),

@@ -523,6 +523,7 @@ template <typename T> void launch_fast_attn_fused(hipStream_t s, const FastFused
 // fast-model attention, one wave per q head (cpos < 16 cached rows, hd <= 256)
 template <typename T> void launch_fast_attn2(hipStream_t s, const FastFusedArgs<T>& a, int R);
 template <typename T> void launch_sample_radix(hipStream_t s, const SampleArgs& a, int R);
+int sample_fast_max_row();  // widest row sample_fast_kernel takes (wider rows: sample_radix_kernel)
 void sample_init();  // sampler kernel attributes (dynamic LDS past 64 KiB), outside any capture
 template <typename T>
 void launch_attn_combine(hipStream_t s, const float* part, const int* row_pos, int R, int nh, int hd,

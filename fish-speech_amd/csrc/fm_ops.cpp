@@ -22,6 +22,9 @@
 //                   launch_bstream on bstream_plan's geometry, launch_finalize_norm, launch_prompt_skinny): outputs
 //                   are in/out arrays with spare rows / columns, the launch can be repeated on the same scratch,
 //                   and the ticket words left non-zero are counted (tests/test_gpu_linear_ops.py)
+//   fm_op_sample    the decode sampler (launch_sample_radix: sample_fast_kernel / sample_radix_kernel and
+//                   their shared wide path) once on caller logits rows, slot table, RAS window and
+//                   forced columns; cols and the tap are in/out (tests/test_gpu_sampler_ops.py)
 //   fm_rope_table   the host-built bf16 cos/sin table (no device needed)
 // Operands are fp32 host arrays, converted to the precision's storage type (bf16 rounding is the
 // caller's business: pass bf16-valued floats for bit-level comparisons).
@@ -1163,6 +1166,77 @@ int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int
         FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
         StreamGuard g(device);
         prompt_skinny_op(g.s, w, x, ldx, R, N, K, *ks, act, out, out_rows, ldo, reps);
+    });
+}
+
+int fm_op_sample(int device, int precision, int slow, const float* logits, int R, int ldl, int Nl,
+                 const int32_t* row_slot, int slots, const float* temperature, const float* top_p, const int32_t* top_k,
+                 const int32_t* mask_im_end, const uint64_t* seed, const int32_t* step, const int32_t* force, int sb,
+                 int se, int im_end, int cb, int draw, int col_idx, const int32_t* ras, int ras_enable,
+                 const int32_t* force_cols, int32_t* cols, int ldc, float* tap, int tap_ld, int* kernel) {
+    return fm_guard([&] {
+        FMCHECK(logits && row_slot && temperature && top_p && top_k && mask_im_end && seed && step && force && ras &&
+                    force_cols && cols && tap && kernel,
+                "null argument");
+        FMCHECK(R >= 1 && R <= 64 && slots >= 1 && slots <= 64 && Nl >= 1 && ldl >= Nl && tap_ld >= Nl,
+                "need 1 <= R, slots <= 64 and rows of ldl, tap_ld >= Nl >= 1");
+        // launch_sample_radix's own LDS condition, refused here before anything is allocated
+        size_t P = 1;  // the wide path's sort length
+        while (P < (size_t)Nl) P <<= 1;
+        FMCHECK(std::max(sizeof(float) * (size_t)Nl, sizeof(uint64_t) * P) + 8 * 1024 <= 160 * 1024,
+                "sampler: vocabulary too wide for the LDS row");
+        FMCHECK(cb >= 1 && draw >= 0 && draw < 64 && (slow ? ldc >= 2 : (col_idx >= 0 && col_idx < ldc)),
+                "cols rows hold [0], [1] (slow) or [col_idx] (fast)");
+        for (int r = 0; r < R; ++r) FMCHECK(row_slot[r] >= 0 && row_slot[r] < slots, "row_slot outside the slot table");
+        for (int i = 0; i < slots; ++i) FMCHECK(step[i] >= 0, "negative step");
+        StreamGuard g(device);
+        DevBufs b(g.s);
+        sample_init();
+        std::vector<SlotParams> sp((size_t)slots);
+        for (int i = 0; i < slots; ++i) {
+            sp[i] = SlotParams{};
+            sp[i].temperature = temperature[i];
+            sp[i].top_p = top_p[i];
+            sp[i].top_k = top_k[i];
+            sp[i].mask_im_end = mask_im_end[i];
+            sp[i].seed = seed[i];
+            sp[i].step = step[i];
+            sp[i].force = force[i];
+        }
+        auto dev = [&](const void* h, size_t bytes) {
+            void* d = b.alloc(bytes);
+            b.put(d, h, bytes);
+            return d;
+        };
+        SampleArgs a{};
+        a.logits = (const float*)dev(logits, (size_t)R * ldl * 4);
+        a.ldl = ldl;
+        a.Nl = Nl;
+        a.row_slot = (const int*)dev(row_slot, (size_t)R * 4);
+        a.sp = (const SlotParams*)dev(sp.data(), sizeof(SlotParams) * slots);
+        a.ras = (const int32_t*)dev(ras, (size_t)slots * 10 * 4);
+        a.ras_stride = 10;
+        a.ras_enable = ras_enable;
+        a.slow = slow != 0;
+        a.sb = sb;
+        a.se = se;
+        a.im_end = im_end;
+        a.cb = cb;
+        a.draw = draw;
+        a.col_idx = col_idx;
+        a.dbg = nullptr;
+        a.cols = (int32_t*)dev(cols, (size_t)R * ldc * 4);
+        a.ldc = ldc;
+        a.force_cols = (const int32_t*)dev(force_cols, (size_t)slots * ldc * 4);
+        a.tap = (float*)dev(tap, (size_t)slots * tap_ld * 4);
+        a.tap_ld = tap_ld;
+        *kernel = (Nl <= sample_fast_max_row() && fm_tuning().sampler_fast) ? 1 : 0;  // the launcher's own choice
+        if (precision == FM_PREC_BF16) launch_sample_radix<bf16_t>(g.s, a, R);
+        else launch_sample_radix<float>(g.s, a, R);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(cols, a.cols, (size_t)R * ldc * 4, hipMemcpyDeviceToHost, g.s));
+        HIPCHK(hipMemcpyAsync(tap, a.tap, (size_t)slots * tap_ld * 4, hipMemcpyDeviceToHost, g.s));
+        HIPCHK(hipStreamSynchronize(g.s));
     });
 }
 

@@ -347,3 +347,40 @@ def batched_linear_q4(w, x, epi, gs=128, device=0):
         return (y4.reshape(-1)[:k * R * No].reshape(k, R, No), yb.reshape(-1)[:k * R * No].reshape(k, R, No), k, q, sc,
                 zr, wd)
     return y4[0], yb[0], k, q, sc, zr, wd
+
+
+def sample(logits, Nl, row_slot, slots, cols, tap, slow, sb, se, im_end, cb, draw=0, col_idx=0, ras=None,
+           ras_enable=False, force_cols=None, precision="bf16", device=0):
+    """fm_op_sample: launch_sample_radix once on logits [R][ldl >= Nl] (fp32), row r with the parameters of
+    slot row_slot[r].  slots: one dict per slot with temperature, top_p, top_k, mask_im_end, seed, step,
+    force.  cols [R][ldc] int32 and tap [len(slots)][tap_ld >= Nl] float32 are in/out arrays, written in
+    place; ras [len(slots)][10] and force_cols [len(slots)][ldc] int32 default to -1 / 0.  Returns the
+    kernel that ran: 1 sample_fast_kernel, 0 sample_radix_kernel."""
+    logits = _f(logits)
+    R, ldl = logits.shape
+    n = len(slots)
+    row_slot = np.ascontiguousarray(row_slot, np.int32)
+    assert row_slot.shape == (R,)
+    for a, dt in ((cols, np.int32), (tap, np.float32)):
+        assert isinstance(a, np.ndarray) and a.dtype == dt and a.ndim == 2 and a.flags.c_contiguous and a.flags.writeable
+    assert cols.shape[0] == R and tap.shape[0] == n
+    ldc = cols.shape[1]
+    ras = np.full((n, 10), -1, np.int32) if ras is None else np.ascontiguousarray(ras, np.int32)
+    force_cols = np.zeros((n, ldc), np.int32) if force_cols is None else np.ascontiguousarray(force_cols, np.int32)
+    assert ras.shape == (n, 10) and force_cols.shape == (n, ldc)
+
+    def col(key, dt):
+        return np.ascontiguousarray([s[key] for s in slots], dt)
+
+    t, p = col("temperature", np.float32), col("top_p", np.float32)
+    k, m, st, fo = (col(key, np.int32) for key in ("top_k", "mask_im_end", "step", "force"))
+    seed = col("seed", np.uint64)
+    kernel = np.full(1, -1, np.int32)
+    i32p = native.i32p
+    native.check(native.lib().fm_op_sample(device, _prec(precision), int(bool(slow)), _p(logits), R, ldl, int(Nl),
+                                           i32p(row_slot), n, _p(t), _p(p), i32p(k), i32p(m),
+                                           seed.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), i32p(st), i32p(fo),
+                                           int(sb), int(se), int(im_end), int(cb), int(draw), int(col_idx), i32p(ras),
+                                           int(bool(ras_enable)), i32p(force_cols), i32p(cols), ldc, _p(tap),
+                                           tap.shape[1], i32p(kernel)))
+    return int(kernel[0])

@@ -354,6 +354,21 @@ int fm_op_finalize_norm(int device, int precision, const float* slab, int kparts
    SwiGLU of the row-interleaved w straight to out [R][ldo >= N / 2]. */
 int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int R, int N, int K, int target, int act,
                         float* out, int out_rows, int ldo, int reps, int* ks);
+/* launch_sample_radix once on caller operands (tests/test_gpu_sampler_ops.py): logits [R][ldl >= Nl]
+   fp32, row r sampled with the parameters of slot row_slot[r] (the per-slot arrays have `slots`
+   entries; seed is 64-bit).  slow != 0: column i < Nl - 1 is token sb + i and column Nl - 1 is im_end,
+   the row writes cols[r][0] (token) and [1] (code), with the RAS redraw from ras [slots][10] when
+   ras_enable; slow == 0: column i is code i and the row writes cols[r][col_idx] with RNG stream
+   `draw`.  A slot with force != 0 emits force_cols [slots][ldc] and copies its logits row to
+   tap [slots][tap_ld >= Nl].  cols [R][ldc] and tap are in/out: what the kernel leaves alone comes
+   back as the caller filled it.  kernel: 1 sample_fast_kernel, 0 sample_radix_kernel, chosen as in
+   production (fm_tune "sampler_fast" and the row width; "sampler_kth" is passed through).  FM_ERR_ARG
+   for a row too wide for the sampler's LDS. */
+int fm_op_sample(int device, int precision, int slow, const float* logits, int R, int ldl, int Nl,
+                 const int32_t* row_slot, int slots, const float* temperature, const float* top_p, const int32_t* top_k,
+                 const int32_t* mask_im_end, const uint64_t* seed, const int32_t* step, const int32_t* force, int sb,
+                 int se, int im_end, int cb, int draw, int col_idx, const int32_t* ras, int ras_enable,
+                 const int32_t* force_cols, int32_t* cols, int ldc, float* tap, int tap_ld, int* kernel);
 /* Weight-only int4 on the batched decode linear (8 < R <= 32, bf16; fm_tune "bstream_q4"): quantises
    the bf16-valued w [N][K] on the device with the int4 group rule (quantize.py:57-160, groups of gs
    along K), packs the dequantised bf16 weights, the step-granular codes and the (scale, zero) table,
