@@ -136,7 +136,11 @@ template <typename T> __device__ __forceinline__ void st_sc1_run(T* p, size_t i,
 // The GEMV body for block (bxi, ks) of a grid with nks K slices.  CH (chain stage, R == 1, whole
 // K per block): the weight ring goes out first, then the wait for the producing stage, then the
 // prologue's loads (sc1); outputs a later stage reads are stored sc1 (the caller arrives).
-template <typename T, int PRO, int EPI, bool NT, int U, int WPB, int QM, bool CH>
+// PR2 (fm_tune fast_pair: bf16 PRO_PRENORM + EPI_SWIGLU8, R == 2, whole K, ss_gran 1): the ss_gran 1 prologue at two
+// rows.  A thread holds, of EACH row, the chunks the one-row form gives it (threadIdx.x and threadIdx.x + NTH), so
+// each row's sum of squares is taken over the same values in the same order; the norm weight chunks serve both rows,
+// which keeps the preload at the one-row form's 24 registers.
+template <typename T, int PRO, int EPI, bool NT, int U, int WPB, int QM, bool CH, bool PR2 = false>
 __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, const int ks, const int nks,
                                           const ChainWait& cw) {
     constexpr bool Q8 = QM == 1, Q4 = QM == 2, QQ = QM != 0;
@@ -149,6 +153,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
     // row per stream (2 items per thread at R = 1), and its register budget is what lets the
     // 1216-block W1||W3 grid stay resident (5 waves per SIMD)
     constexpr int PRE_N = PRO == PRO_PRENORM ? 3 : GEMV_PRE;
+    static_assert(!PR2 || (PRO == PRO_PRENORM && EPI == EPI_SWIGLU8 && QM == 0 && !CH && sizeof(T) == 2), "two-row ss_gran 1 form");
     using G = Frag<T>;
     constexpr int NACC = (EPI == EPI_SWIGLU) ? 2 : 1;
     constexpr int NTH = WPB * 64;
@@ -384,7 +389,16 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
             if (cw.done) chain_wait(cw);
             if constexpr (EPI == EPI_SLABFIN) load_res();
         }
-        C8<T> xc[PRE_N], wc[PRO == PRO_PRENORM ? PRE_N : 1];
+        C8<T> xc[PR2 ? 4 : PRE_N], wc[PRO == PRO_PRENORM ? (PR2 ? 2 : PRE_N) : 1];
+        if constexpr (PR2) {  // slot 2 rr + j: chunk threadIdx.x + NTH j of row rr (nch <= 2 NTH, host-checked)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {  // (unconditional, clamped: a thread without a second chunk re-loads the last)
+                const int c0 = threadIdx.x + NTH * j, cc = c0 < nch ? c0 : nch - 1;
+                xc[j] = ldx8(0, cc);
+                xc[2 + j] = ldx8(1, cc);
+                wc[j] = load_c8(a.nw + kbeg + 8 * cc);
+            }
+        } else {
 #pragma unroll
         for (int q = 0; q < PRE_N; ++q) {
             const int it = threadIdx.x + NTH * q;
@@ -394,6 +408,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
                 if constexpr (PRO == PRO_PRENORM) wc[q] = load_c8(a.nw + kbeg + 8 * cc);
             }
         }
+        }
         // PRO_PRENORM: the [K/16][R] tile sums of squares, flattened over the block's threads,
         // GEMV_SSQ loads each, unconditional (clamped) and issued before the weight ring so their
         // wait does not queue behind weight bytes (a load under a branch makes the compiler drain
@@ -401,7 +416,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
         constexpr int GEMV_SSQ = 2;
         const int nss = (a.K >> 4) * R;
         float ssv[PRO == PRO_PRENORM ? GEMV_SSQ : 1];
-        if constexpr (PRO == PRO_PRENORM) {
+        if constexpr (PRO == PRO_PRENORM && !PR2) {
 #pragma unroll
             for (int q = 0; q < GEMV_SSQ; ++q) {
                 const int e = threadIdx.x + NTH * q;
@@ -418,7 +433,32 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
         }
         if constexpr (PRO == PRO_PRENORM) {
             float* rsw = rsl + wave * GEMV_RMAX;
-            if (!CH && a.ss_gran == 1) {
+            if constexpr (PR2) {
+                float sl[2] = {0.f, 0.f};
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr) {
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        if ((int)threadIdx.x + NTH * j < nch) {
+                            float xv[8];
+                            c8_to_f(xc[2 * rr + j], xv);
+#pragma unroll
+                            for (int u = 0; u < 8; ++u) sl[rr] += xv[u] * xv[u];
+                        }
+                    }
+                    sl[rr] = wave_sum(sl[rr]);
+                    if (lane == 0) red[rr * WPB + wave] = sl[rr];
+                }
+                lds_barrier();
+                if (a.dbg) tsA = __builtin_amdgcn_s_memrealtime();
+#pragma unroll
+                for (int rr = 0; rr < 2; ++rr) {
+                    float tot = 0.f;
+#pragma unroll
+                    for (int w = 0; w < WPB; ++w) tot += red[rr * WPB + w];
+                    if (lane == 0) rsw[rr] = 1.0f / sqrtf(tot / (float)a.K + a.eps);
+                }
+            } else if (!CH && a.ss_gran == 1) {
                 // one row, whole K staged in xc (host-checked): the statistic from the row itself,
                 // sum of x^2 per thread, per wave, then over the block's waves in a fixed order
                 // (the producer -- fm_rowgemv.hip -- wrote no tile sums)
@@ -478,6 +518,16 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
                 *reinterpret_cast<C8<T>*>(xs + (size_t)rr * xstride + 8 * cc) = o;  // one 16/32-B store
                 if (writer) *reinterpret_cast<C8<T>*>(a.xn_out + (size_t)rr * a.ldxo + kbeg + 8 * cc) = o;
             };
+            if constexpr (PR2) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int cc = threadIdx.x + NTH * j;
+                    if (cc < nch) {
+                        put(0, cc, xc[j], wc[j]);
+                        put(1, cc, xc[2 + j], wc[j]);
+                    }
+                }
+            } else {
 #pragma unroll
             for (int q = 0; q < PRE_N; ++q) {
                 const int it = threadIdx.x + NTH * q;
@@ -486,6 +536,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
             for (int it = threadIdx.x + NTH * PRE_N; it < nitem; it += NTH) {
                 const int rr = it / nch, cc = it - rr * nch;
                 put(rr, cc, ldx8(rr, cc), load_c8(a.nw + kbeg + 8 * cc));
+            }
             }
             if (a.dbg) tsB = __builtin_amdgcn_s_memrealtime();
         } else {
@@ -713,6 +764,13 @@ void gemv_kernel(GemvArgs<T> a) {
     gemv_body<T, PRO, EPI, NT, U, WPB, QM, false>(a, blockIdx.x, blockIdx.y, gridDim.y, ChainWait{});
 }
 
+// w1 || w3 at two rows under ss_gran 1 (gemv_body PR2)
+template <bool NT, int U, int WPB>
+__global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(gemv_wpe(PRO_PRENORM, EPI_SWIGLU8))))
+void gemv_pair_kernel(GemvArgs<bf16_t> a) {
+    gemv_body<bf16_t, PRO_PRENORM, EPI_SWIGLU8, NT, U, WPB, 0, false, true>(a, blockIdx.x, 0, 1, ChainWait{});
+}
+
 // One launch running up to GEMV_CHAIN_MAX dependent batch-1 GEMVs (fm_llm.cpp: a layer's wo, w1||w3,
 // w2 and the next layer's qkv).  Stage s owns blocks [off[s], off[s+1]) (dispatch is in block
 // order, so a waiting block only waits on blocks already resident or done); a stage's blocks
@@ -839,11 +897,42 @@ static void gemv_go_q4(hipStream_t s, const GemvArgs<T>& a, int ksb) {
     }
 }
 
+// the two-row ss_gran 1 form of w1 || w3 (gemv_pair_kernel), under the one-row form's knobs
+template <bool NT, int U> static void gemv_pair_w(hipStream_t s, const GemvArgs<bf16_t>& a, dim3 grid, size_t lds) {
+    if (fm_tuning().gemv_wpb == 8) gemv_pair_kernel<NT, U, 8><<<grid, 512, lds, s>>>(a);
+    else gemv_pair_kernel<NT, U, 4><<<grid, 256, lds, s>>>(a);
+}
+template <bool NT> static void gemv_pair_u(hipStream_t s, const GemvArgs<bf16_t>& a, dim3 grid, size_t lds) {
+    switch (fm_tuning().gemv_u) {
+        case 8: gemv_pair_w<NT, 8>(s, a, grid, lds); break;
+        case 2: gemv_pair_w<NT, 2>(s, a, grid, lds); break;
+        default: gemv_pair_w<NT, 4>(s, a, grid, lds); break;
+    }
+}
+static void gemv_pair_go(hipStream_t s, const GemvArgs<bf16_t>& a0) {
+    GemvArgs<bf16_t> a = a0;
+    a.dbg = fm_tuning().dbg;
+    const dim3 grid(FM_CEIL(a.N, 16), 1);
+    const size_t lds = gemv_lds_bytes(2, a.K, sizeof(bf16_t));
+    if (fm_tuning().gemv_nt) gemv_pair_u<true>(s, a, grid, lds);
+    else gemv_pair_u<false>(s, a, grid, lds);
+}
+
 template <typename T> void launch_gemv(hipStream_t s, const GemvArgs<T>& a, int pro, int epi, int ksb) {
     // PRO_PRENORM stages the [K/16][R] tile sums in the 256 * R floats of the reduction buffer
     FMCHECK(pro != PRO_PRENORM || (a.K <= 4096 && a.R <= GEMV_RMAX), "PRO_PRENORM needs K <= 4096, R <= 8");
-    FMCHECK(pro != PRO_PRENORM || (a.ss_in && (a.ss_gran != 1 || (a.R == 1 && ksb == 1 && a.K <= 3 * 8 * 256))),
-            "PRO_PRENORM: ss_in set (also with ss_gran 1: one row, whole K staged)");
+    // ss_gran 1 at two rows: bf16 w1 || w3 only (K <= 4096: two 8-element chunks per thread and row)
+    const bool pair = pro == PRO_PRENORM && a.ss_gran == 1 && a.R == 2;
+    FMCHECK(pro != PRO_PRENORM ||
+                (a.ss_in && (a.ss_gran != 1 || (a.R == 1 && ksb == 1 && a.K <= 3 * 8 * 256) ||
+                             (pair && sizeof(T) == 2 && epi == EPI_SWIGLU8 && ksb == 1 && !a.Wq))),
+            "PRO_PRENORM: ss_in set (also with ss_gran 1: one row, or two for bf16 w1 || w3; whole K staged)");
+    if constexpr (sizeof(T) == 2) {
+        if (pair) {
+            gemv_pair_go(s, a);
+            return;
+        }
+    }
     FMCHECK(pro != PRO_FATT || (a.R == 1 && a.att.cpos < FAST_ATTN_MAXJ && a.att.cpos < a.att.S &&
                                 (a.K / ksb) % a.att.hd == 0 && a.att.hd % 16 == 0 && a.att.hd <= 16 * FATT_MAXPP &&
                                 a.att.ldqkv % 8 == 0),

@@ -695,8 +695,9 @@ template <typename T> struct Run {
     // input row itself (a table row gathered by xidx[xcol] when xidx), else the residual row xb.  a: the tile
     // form's arguments, whose KV prefetch fields carry over.  kv_rows (fm_tune rowgemv bit 6): rows [nq, nqkv)
     // only -- the same prologue and the same per-row sums, the Q rows of Y left as they were
+    // two (fm_tune fast_pair): x and Y hold two rows; one launch, row 0's Q rows left out (RowGemvArgs::skip0)
     void qkv_row(const StackDims& d, const LayerW& L, const GemvArgs<T>& a, bool first, const void* x, int ldx,
-                 const int32_t* xidx, int xcol, void* Y, bool kv_rows) {
+                 const int32_t* xidx, int xcol, void* Y, bool kv_rows, bool two = false) {
         RowGemvArgs r{};
         row_weight(r, L.wqkv_rm, L.wqkv);  // (bf16 or int4: row_qkv excludes int8 models)
         r.X = (const bf16_t*)x;
@@ -712,6 +713,12 @@ template <typename T> struct Run {
         r.Y = (bf16_t*)Y;
         r.N = d.nqkv();
         r.K = d.dim;
+        if (two) {
+            r.xr = 2;
+            r.X1 = r.X + d.dim;
+            r.Y1 = r.Y + d.nqkv();
+            r.skip0 = d.nq();
+        }
         if (kv_rows) {
             r.W += (size_t)d.nq() * d.dim;
             if (r.bias) r.bias += d.nq();
@@ -777,7 +784,18 @@ template <typename T> struct Run {
         int cpos, layer;
         KsbPlan kp;
         void* xo;
+        // fm_tune fast_pair: codebook positions 0 and 1 as one two-row pass.  Row 0's input is x_in (the plain hidden
+        // row), row 1's the row of x_in1 gathered by xidx[xcol]; cpos is row 1's position; row 1 of every activation
+        // buffer follows row 0.  1: both rows run the layer; 2 (the last layer): row 0 ends at its K / V cache write
+        // inside the fused launch, and wo, w1 || w3 and w2 run on row 1 alone
+        int pair = 0;
+        const void* x_in1 = nullptr;
     };
+    // row 1 of a pair's buffer (w elements per row); the buffer itself outside the pair's last layer
+    static const void* row1(const Small& c, const void* p, int w) {
+        return (const char*)p + (c.pair == 2 ? (size_t)w * sizeof(T) : 0);
+    }
+    static void* row1(const Small& c, void* p, int w) { return (char*)p + (c.pair == 2 ? (size_t)w * sizeof(T) : 0); }
     // ... and the kernel path of each of its stages, chosen once (small_path)
     struct SmallPath {
         bool rf;        // wo / w2 on the row-block GEMV; their RMSNorm consumers take the statistic from the row they stage
@@ -820,7 +838,7 @@ template <typename T> struct Run {
     }
     // QKV (+ attention_norm)
     void small_qkv(const Small& c, const SmallPath& p) {
-        if (p.tab) return;
+        if (p.tab && !c.pair) return;
         const StackDims& d = c.d;
         GemvArgs<T> a = qkv_args(d, c.L, c.n);
         if (!c.is_fast && c.n == 1 && fm_tuning().kv_prefetch)  // the attention's K / V rows into L2
@@ -831,9 +849,11 @@ template <typename T> struct Run {
             kv_prefetch(a, (const T*)m->fkc, (const T*)m->fvc, m->frame_slot, m->fiota + c.cpos, m->fslot_stride,
                         (size_t)c.layer * m->flayer_stride, m->C, d.nkv, d.hd);
         if (c.first) {  // the layer's input row itself (a table row gathered by xidx[xcol] at codebook > 0)
-            qkv_first(d, c.L, a, c.n, c.x_in, c.ldx_in, c.xidx, c.xcol, m->qkv, p.kv0);
+            // (a pair: row 0's K / V rows, codebook 0's launch as it stands; row 1's row is the table's)
+            qkv_first(d, c.L, a, c.n, c.x_in, c.ldx_in, c.pair ? nullptr : c.xidx, c.pair ? 0 : c.xcol, m->qkv,
+                      p.kv0 || c.pair);
         } else if (p.row_here) {
-            qkv_row(d, c.L, a, false, c.xb, 0, nullptr, 0, m->qkv, p.kv0);
+            qkv_row(d, c.L, a, false, c.xb, 0, nullptr, 0, m->qkv, p.kv0, c.pair != 0);
         } else {
             a.X = (const T*)c.xb;
             a.ldx = d.dim;
@@ -882,8 +902,27 @@ template <typename T> struct Run {
             row_weight(r, L.wo_rm, L.wo);
             r.X = (const bf16_t*)m->att;  // (fw: unused, x comes from the tagged words)
             r.bias = (const bf16_t*)L.bo;
-            row_residual(r, c.first, c.x_in, c.ldx_in, c.xidx, c.xcol, c.xb, d.dim);
-            r.res_out = (bf16_t*)c.hb;
+            if (!c.pair) {
+                row_residual(r, c.first, c.x_in, c.ldx_in, c.xidx, c.xcol, c.xb, d.dim);
+                r.res_out = (bf16_t*)c.hb;
+            } else {  // row 1's residual: its gathered input row at the first layer, else row 1 of xb
+                RowGemvArgs r1{};
+                row_residual(r1, c.first, c.x_in1, c.ldx_in, c.xidx, c.xcol, (const bf16_t*)c.xb + d.dim, d.dim);
+                r.ldr = r1.ldr;
+                r.residx = r1.residx;
+                r.res_col = r1.res_col;
+                r.res_rows = r1.res_rows;
+                if (c.pair == 2) {
+                    r.res = r1.res;
+                    r.res_out = (bf16_t*)c.hb + d.dim;
+                } else {
+                    r.xr = 2;
+                    r.res = (const bf16_t*)(c.first ? c.x_in : c.xb);
+                    r.res1 = r1.res;
+                    r.res_out = (bf16_t*)c.hb;
+                    r.res_out1 = (bf16_t*)c.hb + d.dim;
+                }
+            }
             r.N = d.dim;
             r.K = d.nq();
             if (!p.fw) {
@@ -908,6 +947,7 @@ template <typename T> struct Run {
                 A.qrows = m->cb;
             }
             A.kv0 = p.kv0;
+            A.pair = c.pair;
             hipStream_t st = s;
             auto go = [st, A] { launch_fattn_wo(st, A); };
             // (recorded as "attn_wo", not "linear": attention + GEMV, reported apart)
@@ -948,10 +988,10 @@ template <typename T> struct Run {
         if (row_w13(c.n)) {
             RowGemvArgs r{};
             row_weight(r, c.L.w13_rm, c.L.w13);
-            r.X = (const bf16_t*)c.hb;
+            r.X = (const bf16_t*)row1(c, c.hb, d.dim);
             r.nw = (const bf16_t*)c.L.fn;
             r.eps = m->c.norm_eps;
-            r.Y = (bf16_t*)m->act;
+            r.Y = (bf16_t*)row1(c, m->act, d.inter);
             r.N = 2 * d.inter;
             r.K = d.dim;
             rowgemv(r, ROWGEMV_NORM_SWIGLU);
@@ -960,14 +1000,14 @@ template <typename T> struct Run {
         GemvArgs<T> a = ga();
         a.W = (const T*)c.L.w13;
         a.nw = (const T*)c.L.fn;
-        a.R = c.n;
+        a.R = c.pair == 1 ? 2 : c.n;  // (a pair's two rows: the ss_gran 1 prologue's two-row instantiation)
         a.N = 2 * d.inter;
         a.K = d.dim;
-        a.X = (const T*)c.hb;
+        a.X = (const T*)row1(c, c.hb, d.dim);
         a.ldx = d.dim;
         a.ss_in = m->ssH;
         a.ss_gran = p.rf ? 1 : 0;
-        a.Y = (T*)m->act;
+        a.Y = (T*)row1(c, m->act, d.inter);
         a.ldy = d.inter;
         gemv(a, PRO_PRENORM, EPI_SWIGLU8, 1, "linear");
     }
@@ -977,10 +1017,16 @@ template <typename T> struct Run {
         if (p.rf) {
             RowGemvArgs r{};
             row_weight(r, c.L.w2_rm, c.L.w2);
-            r.X = (const bf16_t*)m->act;
-            r.res = (const bf16_t*)c.hb;
+            r.X = (const bf16_t*)row1(c, m->act, d.inter);
+            r.res = (const bf16_t*)row1(c, c.hb, d.dim);
             r.ldr = d.dim;
-            r.res_out = (bf16_t*)c.xo;
+            r.res_out = (bf16_t*)row1(c, c.xo, d.dim);
+            if (c.pair == 1) {
+                r.xr = 2;
+                r.X1 = r.X + d.inter;
+                r.res1 = r.res + d.dim;
+                r.res_out1 = r.res_out + d.dim;
+            }
             r.N = d.dim;
             r.K = d.inter;
             rowgemv(r, ROWGEMV_FIN);
@@ -1008,8 +1054,8 @@ template <typename T> struct Run {
     // squares ssX / ssH), so every RMSNorm consumer is PRO_PRENORM.
     void block_small(const StackDims& d, const LayerW& L, int n, bool first, const void* x_in, int ldx_in,
                      const int32_t* xidx, int xcol, void* xb, void* hb, bool is_fast, int cpos, int layer,
-                     const KsbPlan& kp, void* xo, bool kv_only = false) {
-        const Small c{d, L, n, first, x_in, ldx_in, xidx, xcol, xb, hb, is_fast, cpos, layer, kp, xo};
+                     const KsbPlan& kp, void* xo, bool kv_only = false, int pair = 0, const void* x_in1 = nullptr) {
+        const Small c{d, L, n, first, x_in, ldx_in, xidx, xcol, xb, hb, is_fast, cpos, layer, kp, xo, pair, x_in1};
         const SmallPath p = small_path(c, kv_only);
         small_qkv(c, p);
         small_attn(c, p);
@@ -1086,18 +1132,23 @@ template <typename T> struct Run {
             block_small(m->fdm, m->fast[l], n, first, xin, c.fast_dim, xidx, cc, xbuf(m->fx, m->fx2, l), m->fh, true,
                         cc, l, kp, xbuf(m->fx, m->fx2, l + 1), kv_only);
         }
-        if (with_head && sizeof(T) == 2 && n == 1 && m->fout_rm && (row_bits() & 8) && !fm_tuning().gemv_chain &&
+        if (with_head) fast_head(n, xbuf(m->fx, m->fx2, m->fdm.n_layer));
+    }
+    // the codebook head on the fast stack's output row(s) x
+    void fast_head(int n, const void* x) {
+        const fm_model_config& c = m->c;
+        if (sizeof(T) == 2 && n == 1 && m->fout_rm && (row_bits() & 8) && !fm_tuning().gemv_chain &&
             (m->quant != FM_QUANT_INT4 || fm_tuning().int4_stream)) {
             RowGemvArgs r{};  // the codebook head on the row-block GEMV (norm prologue, fp32 logits)
             row_weight(r, m->fout_rm, m->fout);
-            r.X = (const bf16_t*)xbuf(m->fx, m->fx2, m->fdm.n_layer);
+            r.X = (const bf16_t*)x;
             r.nw = (const bf16_t*)m->fnorm;
             r.eps = c.norm_eps;
             r.Yf = m->flogits;
             r.N = m->cb;
             r.K = c.fast_dim;
             rowgemv(r, ROWGEMV_NORM_F32);
-        } else if (with_head) {
+        } else {
             GemvArgs<T> a = ga();
             a.W = (const T*)m->fout;
             a.nw = (const T*)m->fnorm;
@@ -1106,7 +1157,7 @@ template <typename T> struct Run {
             a.K = c.fast_dim;
             a.Yf = m->flogits;
             a.ldy = m->cb;
-            a.X = (const T*)xbuf(m->fx, m->fx2, m->fdm.n_layer);
+            a.X = (const T*)x;
             a.ldx = c.fast_dim;
             a.ss_in = m->ssX;
             a.ss_gran = row_fin(n) ? 1 : 0;
@@ -1114,13 +1165,61 @@ template <typename T> struct Run {
         }
     }
 
+    // fm_tune fast_pair: whether codebook positions 0 and 1 run as one two-row pass.  Both input rows are known when
+    // the fast passes start (the slow model's hidden row; fast_embeddings[cols[1]], drawn by the slow sampler) and row 1
+    // needs of row 0 only its K / V per layer, so the pair is a causal two-token pass that reads every weight once.
+    // It stands on bf16 unquantised weights at one row, fast_tail, the fused attention + wo of every layer at position
+    // 1, the QKV table (rowgemv bit 5) and codebook 0's K / V-only form (bit 6) -- so bits 0 and 1 too -- w1 || w3 on
+    // the tile kernel, and two-row kernel forms that exist at these depths; anywhere else the one-row passes run
+    bool fast_pair_live(int n) const {
+        const FmTuning& t = fm_tuning();
+        const StackDims& d = m->fdm;
+        // (two fast layers at least: consecutive writers of the pair's row-1 tagged words then always differ in tag)
+        if (!(sizeof(T) == 2 && !m->quant && n == 1 && m->C >= 2 && d.n_layer >= 2 && t.fast_pair && t.fast_tail && !t.gemv_chain &&
+              !row_w13(n) && d.dim <= 4096 && rowgemv_pair_ok(-1, d.nq(), false) && rowgemv_pair_ok(ROWGEMV_FIN, d.nq(), true) &&
+              rowgemv_pair_ok(ROWGEMV_FIN, d.inter, false) && rowgemv_pair_ok(ROWGEMV_NORM_STORE, d.dim, false)))
+            return false;
+        const KsbPlan kp{1, 1};
+        for (int l = 0; l < d.n_layer; ++l) {
+            const Small c0{d, m->fast[l], n, l == 0, nullptr, 0, nullptr, 0, nullptr, nullptr, true, 0, l, kp, nullptr};
+            const Small c1{d, m->fast[l], n, l == 0, nullptr, 0, m->cols, 1, nullptr, nullptr, true, 1, l, kp, nullptr};
+            const SmallPath p0 = small_path(c0, false), p1 = small_path(c1, false);
+            if (!(p0.kv0 && p1.fw && p1.rf && !p1.att_wo && (l == 0 ? p1.tab : p1.row_here))) return false;
+        }
+        return true;
+    }
+    // codebook positions 0 and 1 as one pass, and codebook 1's head (on row 1 of the stack's output)
+    void fast_pair(const void* hidden) {
+        const fm_model_config& c = m->c;
+        const KsbPlan kp = plan(m->fdm, 1);
+        const int nl = m->fdm.n_layer;
+        for (int l = 0; l < nl; ++l)
+            block_small(m->fdm, m->fast[l], 1, l == 0, hidden, c.fast_dim, m->cols, 1, m->fx, m->fh, true, 1, l, kp, m->fx,
+                        false, l == nl - 1 ? 2 : 1, m->femb);
+        fast_head(1, (const char*)m->fx + (size_t)c.fast_dim * sizeof(T));
+    }
+    // codebook 0's pass (it only fills the fast KV cache; logits discarded) and, where the pair engages, codebook 1's
+    // with its head in the same pass: returns the next codebook to run
+    int fast_open(int n, const void* hidden) {
+        if (fast_pair_live(n)) {
+            fast_pair(hidden);
+            return 2;
+        }
+        fast_small(n, 0, false, hidden);
+        return 1;
+    }
+
     void frame_tail_small(int n, bool ras_enable, bool sample, const void* hidden) {
         if (sample) {
             SampleArgs a = sargs(true, ras_enable, 0);
             run_("sample", 0, 0, [&] { launch_sample_radix<T>(s, a, n); });
         }
-        fast_small(n, 0, false, hidden);  // position 0 fills the fast KV cache; logits discarded
-        for (int cc = 1; cc < m->C; ++cc) {
+        int cc = fast_open(n, hidden);
+        if (cc == 2 && sample) {
+            SampleArgs a = sargs(false, 0, 1);
+            run_("sample", 0, 0, [&] { launch_sample_radix<T>(s, a, n); });
+        }
+        for (; cc < m->C; ++cc) {
             fast_small(n, cc, true, hidden);
             if (sample) {
                 SampleArgs a = sargs(false, 0, cc);
@@ -1459,8 +1558,10 @@ void teacher_frame(fm_llm* m, int slot, const int32_t* x, int S, int pos0, const
         }
         if (next_col) {
             HIPCHK(hipMemcpyAsync(m->cols, next_col, (size_t)m->C1 * 4, hipMemcpyHostToDevice, m->stream));
-            r.fast_small(1, 0, false, hid);
-            for (int cc = 1; cc < m->C; ++cc) {
+            const int c0 = r.fast_open(1, hid);
+            if (c0 == 2 && fast_logits)
+                HIPCHK(hipMemcpyAsync(fast_logits, m->flogits, (size_t)m->cb * 4, hipMemcpyDeviceToHost, m->stream));
+            for (int cc = c0; cc < m->C; ++cc) {
                 r.fast_small(1, cc, true, hid);
                 if (fast_logits)
                     HIPCHK(hipMemcpyAsync(fast_logits + (size_t)(cc - 1) * m->cb, m->flogits, (size_t)m->cb * 4,

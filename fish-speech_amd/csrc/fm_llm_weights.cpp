@@ -415,7 +415,8 @@ void finalize(fm_llm* m) {
         HIPCHK(hipMemcpy(m->fiota, io, sizeof(io), hipMemcpyHostToDevice));
     }
     if (m->prec == FM_PREC_BF16)
-        m->fxt = (uint32_t*)m->dalloc((size_t)m->fdm.nh * m->fdm.hd * sizeof(uint32_t));  // tags 0: never current
+        // (two rows: fm_tune fast_pair publishes codebook positions 0 and 1 in one launch)
+        m->fxt = (uint32_t*)m->dalloc(2 * (size_t)m->fdm.nh * m->fdm.hd * sizeof(uint32_t));  // tags 0: never current
     m->row_ok = m->row_qkv_ok = m->row_w13_ok = true;
     for (auto* st : {&m->slow, &m->fast})
         for (const LayerW& L : *st) {
@@ -527,11 +528,12 @@ void finalize(fm_llm* m) {
     m->xl = m->dalloc((size_t)n * dmax * E);
     m->plast = m->dalloc((size_t)n * dmax * E);
     m->xnl = m->dalloc((size_t)n * dmax * E);
-    m->fx = m->dalloc((size_t)n * dmax * E);
-    m->fh = m->dalloc((size_t)n * dmax * E);
+    // (the fast residual rows hold two rows on a one-slot handle too: fm_tune fast_pair's paired pass)
+    m->fx = m->dalloc((size_t)std::max(n, 2) * dmax * E);
+    m->fh = m->dalloc((size_t)std::max(n, 2) * dmax * E);
     m->fxn = m->dalloc((size_t)n * dmax * E);
     m->x2 = m->dalloc((size_t)std::min(n, GEMV_MAX_ROWS) * dmax * E);
-    m->fx2 = m->dalloc((size_t)std::min(n, GEMV_MAX_ROWS) * dmax * E);
+    m->fx2 = m->dalloc((size_t)std::max(std::min(n, GEMV_MAX_ROWS), 2) * dmax * E);
     m->chain_cnt = (unsigned*)m->dalloc(GEMV_CHAIN_WORDS * sizeof(unsigned));
     m->chain_err = (int*)m->dalloc(16 * sizeof(int));
     HIPCHK(hipHostMalloc((void**)&m->h_chain_err, 16 * sizeof(int), hipHostMallocDefault));

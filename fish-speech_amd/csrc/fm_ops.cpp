@@ -713,6 +713,58 @@ void rowgemv_op(hipStream_t s, const RowGemvOp& o) {
     else yt.get(s);
 }
 
+// the two-row forms of launch_rowgemv (RowGemvArgs::xr = 2): x [2][K]; fin: row 0's residual res0 [N], row 1's
+// row idx[idx_col] of res1 [res_rows][ldr] (row 0 of it without idx); y [2][y_ld] in/out
+struct RowGemvPairOp {
+    int kind;
+    const float *w, *bias, *nw;
+    float eps;
+    const float *x, *res0, *res1;
+    int res_rows, ldr;
+    const int32_t* idx;
+    int idx_n, idx_col, skip0, N, K;
+    float* y;
+    int y_ld;
+};
+
+void rowgemv_pair_op(hipStream_t s, const RowGemvPairOp& o) {
+    DevBufs b(s);
+    const int N = o.N, K = o.K;
+    RowGemvArgs a{};
+    a.W = b.upload<bf16_t>(o.w, (size_t)N * K);
+    a.X = b.upload<bf16_t>(o.x, (size_t)2 * K);
+    a.X1 = a.X + K;
+    a.ldx = K;
+    if (o.bias) a.bias = b.upload<bf16_t>(o.bias, (size_t)N);
+    if (o.nw) a.nw = b.upload<bf16_t>(o.nw, (size_t)K);
+    a.eps = o.eps;
+    a.N = N;
+    a.K = K;
+    a.xr = 2;
+    InOut<bf16_t> yt(b, o.y, (size_t)2 * o.y_ld);
+    if (o.kind == ROWGEMV_FIN) {
+        a.res = b.upload<bf16_t>(o.res0, (size_t)N);
+        a.res1 = b.upload<bf16_t>(o.res1, (size_t)o.res_rows * o.ldr);
+        a.ldr = o.ldr;
+        if (o.idx) {
+            int32_t* id = (int32_t*)b.alloc((size_t)o.idx_n * 4);
+            b.put(id, o.idx, (size_t)o.idx_n * 4);
+            a.residx = id;
+            a.res_col = o.idx_col;
+            a.res_rows = o.res_rows;
+        }
+        a.res_out = yt.d;
+        a.res_out1 = yt.d + o.y_ld;
+    } else {
+        a.Y = yt.d;
+        a.Y1 = yt.d + o.y_ld;
+        a.skip0 = o.skip0;
+    }
+    launch_rowgemv(s, a, o.kind);
+    HIPCHK(hipGetLastError());
+    yt.get(s);
+}
+
 void prompt_skinny_op(hipStream_t s, const float* w, const float* x, int ldx, int R, int N, int K, int ks, int act,
                       float* out, int out_rows, int ldo, int reps) {
     DevBufs b(s);
@@ -1071,8 +1123,9 @@ int fm_op_gemv(int device, int precision, int pro, int epi, int ksb, const float
         FMCHECK((epi != EPI_SLABFIN && epi != EPI_SWIGLU8) || N % 16 == 0, "EPI_SLABFIN / EPI_SWIGLU8 need whole 16-row tiles");
         FMCHECK(epi != EPI_SLABFIN || (res && ss_out && ldr >= N), "EPI_SLABFIN needs res and ss_out");
         FMCHECK(!norm || K <= 8192, "PRO_NORM stages at most 8192 columns");
-        FMCHECK(!pre || (K <= 4096 && (ss_gran == 0 || (ss_gran == 1 && R == 1 && K <= 3 * 8 * 256))),
-                "PRO_PRENORM: K <= 4096; ss_gran 1 needs one row and K <= 6144");
+        FMCHECK(!pre || (K <= 4096 && (ss_gran == 0 || (ss_gran == 1 && R == 1 && K <= 3 * 8 * 256) ||
+                                       (ss_gran == 1 && R == 2 && epi == EPI_SWIGLU8 && precision == FM_PREC_BF16))),
+                "PRO_PRENORM: K <= 4096; ss_gran 1 needs one row and K <= 6144 (bf16 epi 7: two rows too)");
         FMCHECK(!idx || ((norm || epi == EPI_SLABFIN) && idx_rows >= 1 && idx_ld >= 1 && idx_col >= 0 && idx_col < idx_ld),
                 "a row gather needs PRO_NORM (x) or EPI_SLABFIN (res), its table's row count and a column of idx");
         FMCHECK(ldx >= K && ldx % 8 == 0 && ldy >= (epi == EPI_SWIGLU8 ? N / 2 : N), "bad row strides");
@@ -1108,6 +1161,27 @@ int fm_op_rowgemv(int device, int kind, int q8, const float* w, const float* bia
                     q_out, scale_out};
         StreamGuard g(device);
         rowgemv_op(g.s, o);
+    });
+}
+
+int fm_op_rowgemv_pair(int device, int kind, const float* w, const float* bias, const float* nw, float eps, const float* x,
+                       const float* res0, const float* res1, int res_rows, int ldr, const int32_t* idx, int idx_n,
+                       int idx_col, int skip0, int N, int K, float* y, int y_ld) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y, "null argument");
+        FMCHECK(kind == ROWGEMV_FIN || kind == ROWGEMV_NORM_STORE, "kind must be 0 (fin) or 1 (norm, store)");
+        const bool fin = kind == ROWGEMV_FIN;
+        FMCHECK(rowgemv_pair_ok(kind, K, fin && idx != nullptr), "no two-row form at this depth (K: whole chunks of 256)");
+        const int rp = fin ? 2 : 8;
+        FMCHECK(N >= rp && N % rp == 0 && y_ld >= N, "N must be whole row blocks (fin 2, else 8), y rows at least N wide");
+        FMCHECK(fin == (nw == nullptr) && fin == (res0 != nullptr) && fin == (res1 != nullptr),
+                "fin takes both residual rows, norm + store a norm weight");
+        FMCHECK(!fin || (res_rows >= 1 && ldr >= N && (idx || res_rows == 1)), "bad residual table / stride");
+        FMCHECK(!idx || (fin && idx_n >= 1 && idx_col >= 0 && idx_col < idx_n), "bad gather (fin only)");
+        FMCHECK(fin || (skip0 >= 0 && skip0 <= N), "skip0 outside 0..N");
+        RowGemvPairOp o{kind, w, bias, nw, eps, x, res0, res1, res_rows, ldr, idx, idx_n, idx_col, skip0, N, K, y, y_ld};
+        StreamGuard g(device);
+        rowgemv_pair_op(g.s, o);
     });
 }
 

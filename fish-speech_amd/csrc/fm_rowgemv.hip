@@ -89,15 +89,24 @@ template <int QM> struct RowT {
 // TX (tagged x, fattn_wo_kernel): x is read after the weights, from 32-bit words (bf16 << 16 | gen)
 // that a producer in the same launch stores write-through; the wave re-reads its words (sc1) until
 // every tag equals gen (bounded; *err set on timeout).  blk: the row block's index.
-template <int U, int RP, bool PRENORM, int EPI, bool G, int QM, bool TX>
+// XR 2 (fm_tune fast_pair; bf16, STORE / FIN): two activation rows against one pass over the weights.  Row 1's
+// operands are RowGemvArgs::X1 / res1 / res_out1 / Y1 (TX: the second K words of xt); G gathers row 1's residual
+// only.  One accumulator set, one RMSNorm statistic and one epilogue thread per (x row, weight row): every output
+// is the one-row form's operations on the same inputs in the same order.
+template <int U, int RP, bool PRENORM, int EPI, bool G, int QM, bool TX, int XR = 1>
 __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk, const uint32_t* xt, const uint32_t gen,
                                              int* err) {
     static_assert(!TX || (!PRENORM && EPI == 1), "tagged x: the residual form only");
+    static_assert(XR == 1 || (XR == 2 && QM == 0 && EPI <= 1 && (!G || EPI == 1)), "two x rows: bf16 STORE / FIN");
     constexpr bool FIN = EPI == 1;
     using R = RowT<QM>;
     using XV = typename R::XV;
     constexpr int EPL = R::EPL, NW = EPL / 2;  // NW: 32-bit words of x per lane per chunk
-    __shared__ float red[4 * RP + 8];
+    constexpr int SB = XR * 4 * RP;            // red: [XR][4 waves][RP] partials, then the statistics
+    // deep runs (w2): row 1's x chunk is loaded into the registers row 0's chunk leaves, after its dot products, so
+    // the two-row form keeps the one-row form's register budget (no scratch under waves_per_eu 5)
+    constexpr bool LATE = XR == 2 && !TX && !PRENORM && U >= 10;
+    __shared__ float red[XR * (4 * RP + 8)];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n0 = blk * RP;
     const int nch = a.K / R::CE;
@@ -107,6 +116,7 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     // first round trip, unconditional (a load under a branch drains vmcnt): the epilogue's residual,
     // bias and (int8) scale elements of row n0 + (thread % RP), then x (and the norm weight)
     const int er = n0 + (int)(threadIdx.x % RP);
+    const int ex = XR == 2 ? (int)((threadIdx.x / RP) & 1) : 0;  // the x row this thread finishes
     int ri = 0, xi = 0;
     if constexpr (G && FIN) {
         const int32_t iv = a.residx[a.res_col];
@@ -116,18 +126,20 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         xi = iv < 0 ? 0 : (iv >= a.xrows ? a.xrows - 1 : iv);
     }
     bf16_t rv = 0;
-    if constexpr (FIN) rv = a.res[(size_t)ri * a.ldr + er];
+    if constexpr (FIN && XR == 2) rv = ex ? a.res1[(size_t)ri * a.ldr + er] : a.res[er];
+    else if constexpr (FIN) rv = a.res[(size_t)ri * a.ldr + er];
     const bf16_t bv = *(a.bias ? a.bias + er : a.X);
     bf16_t sv = 0;
     if constexpr (QM == 1) sv = a.wscale[er];
     const XV* xp = reinterpret_cast<const XV*>(a.X + (size_t)xi * a.ldx) + (size_t)wa * 64 + lane;
     const XV* gp = reinterpret_cast<const XV*>(PRENORM ? a.nw : a.X) + (size_t)wa * 64 + lane;
-    XV xv[U], gv[PRENORM ? U : 1];
+    XV xv[XR][U], gv[PRENORM ? U : 1];
     if constexpr (!TX) {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = (u < last ? u : last) * 64;
-            xv[u] = xp[j];
+            xv[0][u] = xp[j];
+            if constexpr (XR == 2 && !LATE) xv[1][u] = (reinterpret_cast<const XV*>(a.X1) + (size_t)wa * 64 + lane)[j];
             if constexpr (PRENORM) gv[u] = gp[j];
         }
     }
@@ -177,24 +189,29 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     if constexpr (TX) {
         if (a.dbg) tsw = __builtin_amdgcn_s_memrealtime();
         // EPL tagged words per lane per chunk (sc1 loads, 16 B each), re-read until all are current
-        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xt, (short)0, a.K * 4, 0x00020000);
-        u32x4_t xw[U][EPL / 4];
+        const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xt, (short)0, XR * a.K * 4, 0x00020000);
+        u32x4_t xw[XR][U][EPL / 4];
         for (unsigned it = 0;; ++it) {
             polls = it + 1;
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int jc = u < last ? u : last;
+            for (int x = 0; x < XR; ++x)
 #pragma unroll
-                for (int q = 0; q < EPL / 4; ++q)
-                    xw[u][q] = __builtin_amdgcn_raw_buffer_load_b128(xr, ((wa + jc) * R::CE + EPL * lane + 4 * q) * 4, 0, 16);
-            }
+                for (int u = 0; u < U; ++u) {
+                    const int jc = u < last ? u : last;
+#pragma unroll
+                    for (int q = 0; q < EPL / 4; ++q)
+                        xw[x][u][q] = __builtin_amdgcn_raw_buffer_load_b128(
+                            xr, (x * a.K + (wa + jc) * R::CE + EPL * lane + 4 * q) * 4, 0, 16);
+                }
             bool ok = true;
 #pragma unroll
-            for (int u = 0; u < U; ++u)
+            for (int x = 0; x < XR; ++x)
 #pragma unroll
-                for (int q = 0; q < EPL / 4; ++q)
+                for (int u = 0; u < U; ++u)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) ok = ok && ((xw[u][q][e] & 0xffffu) == gen);
+                    for (int q = 0; q < EPL / 4; ++q)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) ok = ok && ((xw[x][u][q][e] & 0xffffu) == gen);
             if (__all(ok)) break;
             if (it >= (1u << 14)) {  // bounded: the host sees err and fails the frame
                 if (lane == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -204,12 +221,14 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         }
         if (a.dbg) tsx = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int x = 0; x < XR; ++x)
 #pragma unroll
-            for (int h = 0; h < NW; ++h) {
-                const uint32_t w0 = xw[u][(2 * h) >> 2][(2 * h) & 3], w1 = xw[u][(2 * h + 1) >> 2][(2 * h + 1) & 3];
-                xv[u][h] = (w0 >> 16) | (w1 & 0xffff0000u);
-            }
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int h = 0; h < NW; ++h) {
+                    const uint32_t w0 = xw[x][u][(2 * h) >> 2][(2 * h) & 3], w1 = xw[x][u][(2 * h + 1) >> 2][(2 * h + 1) & 3];
+                    xv[x][u][h] = (w0 >> 16) | (w1 & 0xffff0000u);
+                }
     }
     float pfw[PF];
     if constexpr (EPI == 0) {  // GemvArgs::pf_kc: one 4-byte load per 64-B sector, after the weights
@@ -235,14 +254,14 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         }
     }
     // PRENORM: the row statistic (every block the same sums in the same order), then x'
-    if constexpr (PRENORM) {
+    if constexpr (PRENORM && XR == 1) {  // (kept apart from the two-row form below: the one-row code stays as it compiled)
         float sl = 0.f;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (u < nmy) {
 #pragma unroll
                 for (int h = 0; h < NW; ++h) {
-                    const float e0 = lo16(xv[u][h]), e1 = hi16(xv[u][h]);
+                    const float e0 = lo16(xv[0][u][h]), e1 = hi16(xv[0][u][h]);
                     sl += e0 * e0 + e1 * e1;
                 }
             }
@@ -257,55 +276,109 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
             XV o;
 #pragma unroll
             for (int h = 0; h < NW; ++h) {
-                const float y0 = bfround(bfround(lo16(xv[u][h]) * rs) * lo16(gv[u][h]));
-                const float y1 = bfround(bfround(hi16(xv[u][h]) * rs) * hi16(gv[u][h]));
+                const float y0 = bfround(bfround(lo16(xv[0][u][h]) * rs) * lo16(gv[u][h]));
+                const float y1 = bfround(bfround(hi16(xv[0][u][h]) * rs) * hi16(gv[u][h]));
                 o[h] = (uint32_t)f2bf(y0) | ((uint32_t)f2bf(y1) << 16);
             }
-            xv[u] = o;
+            xv[0][u] = o;
         }
     }
-    float acc[RP];
+    if constexpr (PRENORM && XR == 2) {  // one statistic per x row, each the one-row form's sums in its order
 #pragma unroll
-    for (int r = 0; r < RP; ++r) acc[r] = 0.f;
+        for (int x = 0; x < XR; ++x) {
+            float sl = 0.f;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (u < nmy) {
+#pragma unroll
+                    for (int h = 0; h < NW; ++h) {
+                        const float e0 = lo16(xv[x][u][h]), e1 = hi16(xv[x][u][h]);
+                        sl += e0 * e0 + e1 * e1;
+                    }
+                }
+            }
+            sl = wave_sum(sl);
+            if (lane == 0) red[SB + 4 * x + wave] = sl;
+        }
+        lds_barrier();
+#pragma unroll
+        for (int x = 0; x < XR; ++x) {
+            const float tot = ((red[SB + 4 * x] + red[SB + 4 * x + 1]) + red[SB + 4 * x + 2]) + red[SB + 4 * x + 3];
+            const float rs = 1.0f / sqrtf(tot / (float)a.K + a.eps);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                XV o;
+#pragma unroll
+                for (int h = 0; h < NW; ++h) {
+                    const float y0 = bfround(bfround(lo16(xv[x][u][h]) * rs) * lo16(gv[u][h]));
+                    const float y1 = bfround(bfround(hi16(xv[x][u][h]) * rs) * hi16(gv[u][h]));
+                    o[h] = (uint32_t)f2bf(y0) | ((uint32_t)f2bf(y1) << 16);
+                }
+                xv[x][u] = o;
+            }
+        }
+    }
+    float acc[XR][RP];
+#pragma unroll
+    for (int x = 0; x < XR; ++x)
+#pragma unroll
+        for (int r = 0; r < RP; ++r) acc[x][r] = 0.f;
     float xs = 0.f;  // int8: this lane's sum of x (the 128 offset of the codes)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (u < nmy) {
             if constexpr (QM == 0) {
 #pragma unroll
-                for (int r = 0; r < RP; ++r) acc[r] = dot4(wv[u][r], xv[u], acc[r]);
+                for (int r = 0; r < RP; ++r)
+#pragma unroll
+                    for (int x = 0; x < (LATE ? 1 : XR); ++x) acc[x][r] = dot4(wv[u][r], xv[x][u], acc[x][r]);
             } else if constexpr (QM == 2) {
                 const u32x4_t ones = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
-                const float xl = dot8r(ones, xv[u], 0.f);  // sum of the lane's 8 x
+                const float xl = dot8r(ones, xv[0][u], 0.f);  // sum of the lane's 8 x
 #pragma unroll
                 for (int r = 0; r < RP; ++r) {
                     const uint32_t w = w4[u][r];
                     u32x4_t A;
 #pragma unroll
                     for (int p = 0; p < 4; ++p) A[p] = ((w >> (4 * p)) & 0x000F000Fu) | 0x43004300u;
-                    const float B = dot8r(A, xv[u], 0.f);
+                    const float B = dot8r(A, xv[0][u], 0.f);
                     const float sc = lo16(szv[u][r]), zr = hi16(szv[u][r]);
-                    acc[r] = fmaf(sc, B, acc[r]);
-                    acc[r] = fmaf(zr - 136.f * sc, xl, acc[r]);
+                    acc[0][r] = fmaf(sc, B, acc[0][r]);
+                    acc[0][r] = fmaf(zr - 136.f * sc, xl, acc[0][r]);
                 }
             } else {
                 float xf[8];
 #pragma unroll
                 for (int h = 0; h < 4; ++h) {
-                    xf[2 * h] = lo16(xv[u][h]);
-                    xf[2 * h + 1] = hi16(xv[u][h]);
+                    xf[2 * h] = lo16(xv[0][u][h]);
+                    xf[2 * h + 1] = hi16(xv[0][u][h]);
                 }
                 xs += ((xf[0] + xf[1]) + (xf[2] + xf[3])) + ((xf[4] + xf[5]) + (xf[6] + xf[7]));
 #pragma unroll
                 for (int r = 0; r < RP; ++r) {
                     const uint32_t c0 = wv[u][r][0] ^ 0x80808080u, c1 = wv[u][r][1] ^ 0x80808080u;
-                    float t = acc[r];
+                    float t = acc[0][r];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) t = fmaf((float)((c0 >> (8 * e)) & 0xffu), xf[e], t);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) t = fmaf((float)((c1 >> (8 * e)) & 0xffu), xf[4 + e], t);
-                    acc[r] = t;
+                    acc[0][r] = t;
                 }
+            }
+        }
+    }
+    if constexpr (LATE) {
+        // row 1's loads stay behind row 0's dot products (the accumulators pass through the statement)
+#pragma unroll
+        for (int r = 0; r < RP; ++r) asm volatile("" : "+v"(acc[0][r])::"memory");
+        const XV* xp1 = reinterpret_cast<const XV*>(a.X1) + (size_t)wa * 64 + lane;
+#pragma unroll
+        for (int u = 0; u < U; ++u) xv[1][u] = xp1[(u < last ? u : last) * 64];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (u < nmy) {
+#pragma unroll
+                for (int r = 0; r < RP; ++r) acc[1][r] = dot4(wv[u][r], xv[1][u], acc[1][r]);
             }
         }
     }
@@ -315,25 +388,28 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     }
     const unsigned long long ts1 = a.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
 #pragma unroll
-    for (int r = 0; r < RP; ++r) {
-        const float v = wave_sum(acc[r]);
-        if (lane == 0) red[wave * RP + r] = v;
-    }
+    for (int x = 0; x < XR; ++x)
+#pragma unroll
+        for (int r = 0; r < RP; ++r) {
+            const float v = wave_sum(acc[x][r]);
+            if (lane == 0) red[(4 * x + wave) * RP + r] = v;
+        }
     if constexpr (QM == 1) {
         const float v = wave_sum(xs);
         if (lane == 0) red[4 * RP + 4 + wave] = v;
     }
     __syncthreads();
-    if ((int)threadIdx.x < RP) {
-        const int t = threadIdx.x;
-        float v = ((red[t] + red[RP + t]) + red[2 * RP + t]) + red[3 * RP + t];
+    if ((int)threadIdx.x < XR * RP) {
+        const int t = XR == 2 ? (int)(threadIdx.x % RP) : (int)threadIdx.x;
+        const float* rd = red + 4 * RP * ex;
+        float v = ((rd[t] + rd[RP + t]) + rd[2 * RP + t]) + rd[3 * RP + t];
         if constexpr (QM == 1) {
             const float xt = ((red[4 * RP + 4] + red[4 * RP + 5]) + red[4 * RP + 6]) + red[4 * RP + 7];
             v = bfround(bfround(v - 128.f * xt) * bf2f(sv));
         }
         if (a.bias) v += bf2f(bv);
         if constexpr (FIN) {
-            a.res_out[er] = f2bf(bfround(bf2f(rv) + bfround(v)));
+            (ex ? a.res_out1 : a.res_out)[er] = f2bf(bfround(bf2f(rv) + bfround(v)));
         } else if constexpr (EPI == 3) {
             a.Yf[er] = bfround(v);
         } else if constexpr (EPI == 2) {  // gate rows t < RP / 2, up rows t >= RP / 2 (same wave)
@@ -342,17 +418,22 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
                 const float g = bfround(v);
                 a.Y[blockIdx.x * (RP / 2) + t] = f2bf(bfround(g / (1.0f + expf(-g))) * bfround(up));
             }
+        } else if constexpr (XR == 2) {  // (row 0's outputs below skip0 are not wanted: a block straddling it)
+            if (ex || er >= a.skip0) (ex ? a.Y1 : a.Y)[er] = f2bf(v);
         } else {
             a.Y[er] = f2bf(v);
         }
     }
-    if (a.dbg && threadIdx.x == 0) {
-        if constexpr (TX) {  // (wave 0) start, weights issued, x words current, dot products done, end; aux = reads of x
-            const unsigned long long t[7] = {ts0, tsw, tsx, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0};
-            dbg_record(a.dbg, 0xFFF8u, polls, t);
-        } else {
-            const unsigned long long t[7] = {ts0, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0};
-            dbg_record(a.dbg, 0xFFFAu, (unsigned)blk, t);
+    if (a.dbg && threadIdx.x == 0) {  // one record per x row: a record stands for one block's work on one row
+#pragma unroll
+        for (int x = 0; x < XR; ++x) {
+            if constexpr (TX) {  // (wave 0) start, weights issued, x words current, dot products done, end; aux = reads of x
+                const unsigned long long t[7] = {ts0, tsw, tsx, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0};
+                dbg_record(a.dbg, 0xFFF8u, polls, t);
+            } else {
+                const unsigned long long t[7] = {ts0, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0};
+                dbg_record(a.dbg, 0xFFFAu, (unsigned)blk, t);
+            }
         }
     }
 }
@@ -361,6 +442,24 @@ template <int U, int RP, bool PRENORM, int EPI, bool G, int QM>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RP == 2 ? 5 : 3)))
 void rowgemv_kernel(RowGemvArgs a) {
     rowgemv_body<U, RP, PRENORM, EPI, G, QM, false>(a, blockIdx.x, nullptr, 0u, nullptr);
+}
+
+// Two activation rows (fm_tune fast_pair): the same grid, each block's weights loaded once for both rows.
+// STORE (wqkv): a block whose rows all lie in [0, skip0) -- the Q rows, which row 0 never reads -- runs the
+// one-row body on row 1.
+template <int U, int RP, bool PRENORM, int EPI, bool G>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RP == 2 ? 5 : 3)))
+void rowgemv2_kernel(RowGemvArgs a) {
+    if constexpr (EPI == 0) {
+        if (((int)blockIdx.x + 1) * RP <= a.skip0) {
+            RowGemvArgs b = a;
+            b.X = a.X1;
+            b.Y = a.Y1;
+            rowgemv_body<U, RP, PRENORM, EPI, false, 0, false>(b, blockIdx.x, nullptr, 0u, nullptr);
+            return;
+        }
+    }
+    rowgemv_body<U, RP, PRENORM, EPI, G, 0, false, 2>(a, blockIdx.x, nullptr, 0u, nullptr);
 }
 
 // smallest instantiated depth covering a wave's share of the K chunks (0: not eligible)
@@ -393,6 +492,53 @@ static void rowgemv_go(hipStream_t s, const RowGemvArgs& a, int U) {
 #undef RG
 }
 
+// the two-row forms: FIN (wo / w2, RP 2, row 1's residual gathered or not) and NORM_STORE (wqkv, row_qkv_rp rows)
+template <int RP, bool PRENORM, int EPI>
+static void rowgemv2_go(hipStream_t s, const RowGemvArgs& a, int U) {
+    const dim3 grid(a.N / RP), block(256);
+    const bool g = EPI == 1 && a.residx != nullptr;
+#define RG(u) \
+    case u: (g ? rowgemv2_kernel<u, RP, PRENORM, EPI, EPI == 1> : rowgemv2_kernel<u, RP, PRENORM, EPI, false>)<<<grid, block, 0, s>>>(a); break;
+    switch (U) {
+        RG(2) RG(3) RG(4) RG(5)
+        default:
+            if constexpr (EPI == 1) {
+                if (U == 6) rowgemv2_kernel<6, RP, PRENORM, EPI, false><<<grid, block, 0, s>>>(a);
+                else if (U == 8) rowgemv2_kernel<8, RP, PRENORM, EPI, false><<<grid, block, 0, s>>>(a);
+                else if (U == 10) rowgemv2_kernel<10, RP, PRENORM, EPI, false><<<grid, block, 0, s>>>(a);
+                else rowgemv2_kernel<12, RP, PRENORM, EPI, false><<<grid, block, 0, s>>>(a);
+            }
+            break;
+    }
+#undef RG
+}
+
+// The two-row forms that exist: every one of them fits its launch bounds without scratch (code-object metadata,
+// DESIGN section 3 round 9); a shape outside them runs the one-row passes.  NORM_STORE: 8 rows per block, runs
+// of at most 5 chunks; FIN: any depth, the gathered form (the first layer's wo, K = nq) at most 5; the fused
+// attention + wo pair form (kind -1): at most 5, within its 80 registers.
+bool rowgemv_pair_ok(int kind, int K, bool gathered) {
+    const int U = rowgemv_u(K, 0);
+    if (U <= 0) return false;
+    if (kind == ROWGEMV_FIN) return U <= 5 || !gathered;
+    if (kind == ROWGEMV_NORM_STORE) return U <= 5 && fm_tuning().row_qkv_rp == 8;
+    return kind == -1 && U <= 5;
+}
+
+static void launch_rowgemv2(hipStream_t s, const RowGemvArgs& a, int kind, int U) {
+    FMCHECK(a.W && !a.Wq && !a.Wq4 && !a.xidx, "row GEMV, two rows: bf16, no x gather");
+    if (kind == ROWGEMV_FIN) {
+        FMCHECK(a.N % 2 == 0 && a.res && a.res1 && a.res_out && a.res_out1 && rowgemv_pair_ok(kind, a.K, a.residx != nullptr),
+                "row GEMV (fin, two rows): N even, both residual rows set, an instantiated depth");
+        rowgemv2_go<2, false, 1>(s, a, U);
+    } else {
+        FMCHECK(kind == ROWGEMV_NORM_STORE && a.N % 8 == 0 && a.nw && a.X1 && a.Y && a.Y1 && a.skip0 >= 0 &&
+                    rowgemv_pair_ok(kind, a.K, false),
+                "row GEMV (norm, store, two rows): N a whole number of 8-row blocks, norm weight, both rows set, an instantiated depth");
+        rowgemv2_go<8, true, 0>(s, a, U);
+    }
+}
+
 void launch_rowgemv(hipStream_t s, const RowGemvArgs& a0, int kind) {
     RowGemvArgs a = a0;
     a.dbg = fm_tuning().dbg;
@@ -403,6 +549,10 @@ void launch_rowgemv(hipStream_t s, const RowGemvArgs& a0, int kind) {
                 (qm == 2 ? (a.wsz && a.gs > 0 && a.gs % 8 == 0 && a.K % a.gs == 0 && !a.bias)
                          : (qm == 1 ? (a.Wq && a.wscale && !a.bias) : a.W != nullptr)),
             "row GEMV: K a whole number of chunks (256 k, int8 / int4 512 k), at most 48 per wave; operands set");
+    if (a.xr == 2) {
+        launch_rowgemv2(s, a, kind, U);
+        return;
+    }
     if (kind == ROWGEMV_FIN) {
         FMCHECK(a.N % 2 == 0 && a.res && a.res_out, "row GEMV (fin): N even, residual rows set");
         if (qm == 2) rowgemv_go<2, false, 1, 2>(s, a, U);
@@ -759,6 +909,123 @@ void fattn_wo_kernel(FattnWoArgs A) {
     rowgemv_body<U, 2, false, 1, G, QM, true>(A.wo, (int)blockIdx.x - at.nkv, A.xt, gen, A.err);
 }
 
+// The pair form (fm_tune fast_pair; bf16): codebook positions 0 and 1 of the fast decoder in ONE launch.  Row 0 is
+// the slow model's hidden row at position 0, row 1 the embedding of the code the slow sampler drew, at position 1;
+// both are known before the fast passes start, and row 1 needs of row 0 only its K / V at this layer.  An
+// attention block does both rows of its kv group:
+//   row 0  form 2's arithmetic: k normed, rotated (position 0) and cached with v, output 0 + v (no Q);
+//   row 1  form 0 / 1 at cpos 1: q, k normed and rotated (position 1), k / v cached, then fw_attend<2> with
+//          position 0's K / V row staged in LDS from row 0's registers -- the rounded bf16 values the cache
+//          holds, so no cache load and no other block is waited for.
+// TAB: row 1's raw q|k|v row comes from the table (form 1: the first layer; its residual row is gathered too),
+// else it is row 1 of at.qkv.  XR 2: both rows' outputs are published (K tagged words each) and the wo blocks
+// run the two-row TX body; XR 1 (the last layer): row 0 ends at its K / V write, the wo blocks take row 1 only
+// (A.wo holds row 1's residual and output).  One gen per launch, the tag of position 1's launch index.
+// Each operation on each row is the one-row kernel's, in its order (the second RoPE pair of a lane, masked to
+// zero there because hd <= FW_MAXHD, only adds +0 to sums that are never -0 and is left out).
+template <int U, bool TAB, int XR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
+void fattn_wo_pair_kernel(FattnWoArgs A) {
+    __shared__ __attribute__((aligned(16))) bf16_t kvs[4 * FW_MAXHD];  // K rows 0 .. 1, V rows 0 .. 1 (row 1: read, selected away)
+    const FastFusedArgs<bf16_t>& at = A.at;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t gen = ((uint32_t)A.at.row_pos[0] * 41u + (uint32_t)A.gen) % 65535u + 1u;
+    const unsigned long long ts0 = A.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
+    if ((int)blockIdx.x < at.nkv) {
+        if (A.prio) __builtin_amdgcn_s_setprio(3);
+        const int kvh = blockIdx.x, hd = at.hd, g = at.nh / at.nkv, half = hd >> 1;
+        const bf16_t* r0 = at.qkv;
+        const bf16_t* r1 = at.qkv + at.ldqkv;
+        if constexpr (TAB) {
+            const int32_t iv = A.qidx[A.qcol];
+            const int xi = iv < 0 ? 0 : (iv >= A.qrows ? A.qrows - 1 : iv);
+            r1 = A.qtab + (size_t)xi * at.ldqkv;
+        }
+        const int slot = at.row_slot[0];
+        const bool live = wave < g, in = lane < half;
+        const int h = kvh * g + (live ? wave : 0), pp = in ? lane : 0;
+        const float* tab0 = at.rope;
+        const float* tab1 = at.rope + hd;
+        const size_t base = (size_t)slot * at.slot_stride + at.layer_off + (size_t)kvh * at.S * hd;
+        const size_t ko = (size_t)(at.nh + kvh) * hd + 2 * pp, vo = (size_t)(at.nh + at.nkv + kvh) * hd + 2 * pp;
+        float ka0, ka1, va0, va1, q0, q1, k0, k1, v0, v1, qw0 = 1.f, qw1 = 1.f, kw0 = 1.f, kw1 = 1.f;
+        ld_pair_bf(r0 + ko, ka0, ka1);
+        ld_pair_bf(r0 + vo, va0, va1);
+        ld_pair_bf(r1 + (size_t)h * hd + 2 * pp, q0, q1);
+        ld_pair_bf(r1 + ko, k0, k1);
+        ld_pair_bf(r1 + vo, v0, v1);
+        if (at.qk_norm) {
+            ld_pair_bf(at.qn + 2 * pp, qw0, qw1);
+            ld_pair_bf(at.kn + 2 * pp, kw0, kw1);
+        }
+        const float ca = tab0[2 * pp], sa = tab0[2 * pp + 1], cb = tab1[2 * pp], sb = tab1[2 * pp + 1];
+        if (!in) ka0 = ka1 = va0 = va1 = q0 = q1 = k0 = k1 = v0 = v1 = 0.f;
+        // the three chains (row 0's k, row 1's q and k) side by side, each with prep's operations
+        if (at.qk_norm) {
+            float sa_ = 0.f, sq = 0.f, sk = 0.f;
+            sa_ += ka0 * ka0 + ka1 * ka1;
+            sq += q0 * q0 + q1 * q1;
+            sk += k0 * k0 + k1 * k1;
+            sa_ = wave_sum(sa_);
+            sq = wave_sum(sq);
+            sk = wave_sum(sk);
+            const float ra = 1.0f / sqrtf(sa_ / (float)hd + at.eps), rq = 1.0f / sqrtf(sq / (float)hd + at.eps),
+                        rk = 1.0f / sqrtf(sk / (float)hd + at.eps);
+            ka0 = bfround((ka0 * ra) * kw0);
+            ka1 = bfround((ka1 * ra) * kw1);
+            q0 = bfround((q0 * rq) * qw0);
+            q1 = bfround((q1 * rq) * qw1);
+            k0 = bfround((k0 * rk) * kw0);
+            k1 = bfround((k1 * rk) * kw1);
+        }
+        {
+            const float a0 = bfround(ka0 * ca - ka1 * sa), a1 = bfround(ka1 * ca + ka0 * sa);
+            const float b0 = bfround(q0 * cb - q1 * sb), b1 = bfround(q1 * cb + q0 * sb);
+            const float c0 = bfround(k0 * cb - k1 * sb), c1 = bfround(k1 * cb + k0 * sb);
+            ka0 = a0;
+            ka1 = a1;
+            q0 = b0;
+            q1 = b1;
+            k0 = c0;
+            k1 = c1;
+        }
+        if (wave == 0 && in) {  // both positions into the fast cache; position 0's row staged for row 1's scores
+            const uint32_t kw = (uint32_t)f2bf(ka0) | ((uint32_t)f2bf(ka1) << 16);
+            const uint32_t vw = (uint32_t)f2bf(va0) | ((uint32_t)f2bf(va1) << 16);
+            *reinterpret_cast<uint32_t*>(at.kc + base + 2 * lane) = kw;
+            *reinterpret_cast<uint32_t*>(at.vc + base + 2 * lane) = vw;
+            *reinterpret_cast<uint32_t*>(at.kc + base + hd + 2 * lane) = (uint32_t)f2bf(k0) | ((uint32_t)f2bf(k1) << 16);
+            *reinterpret_cast<uint32_t*>(at.vc + base + hd + 2 * lane) = (uint32_t)f2bf(v0) | ((uint32_t)f2bf(v1) << 16);
+            *reinterpret_cast<uint32_t*>(kvs + 2 * lane) = kw;
+            *reinterpret_cast<uint32_t*>(kvs + 2 * FW_MAXHD + 2 * lane) = vw;
+        }
+        __syncthreads();
+        const unsigned long long ts1 = A.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
+        if (!live) return;
+        float o0 = 0.f, o1 = 0.f;
+        fw_attend<2>(kvs, kvs + 2 * FW_MAXHD, hd, half, 1, lane, at.scale, q0, q1, k0, k1, v0, v1, o0, o1);
+        const int K = at.nh * hd;
+        if (in) {
+            if constexpr (XR == 2) {  // row 0: one position, softmax = {1}, output 0 + v
+                const float p0 = 0.f + va0, p1 = 0.f + va1;
+                const uint64_t w = (uint64_t)(((uint32_t)f2bf(p0) << 16) | gen) | ((uint64_t)(((uint32_t)f2bf(p1) << 16) | gen) << 32);
+                __hip_atomic_store(reinterpret_cast<uint64_t*>(A.xt + (size_t)h * hd + 2 * lane), w, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            }
+            const uint64_t w = (uint64_t)(((uint32_t)f2bf(o0) << 16) | gen) | ((uint64_t)(((uint32_t)f2bf(o1) << 16) | gen) << 32);
+            __hip_atomic_store(reinterpret_cast<uint64_t*>(A.xt + K + (size_t)h * hd + 2 * lane), w, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (A.dbg && lane == 0) {  // one attention-wave record per row whose output this wave produced
+            const unsigned long long t[7] = {ts0, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0};
+#pragma unroll
+            for (int x = 0; x < XR; ++x) dbg_record(A.dbg, 0xFFF9, (unsigned)h, t);
+        }
+        return;
+    }
+    rowgemv_body<U, 2, false, 1, TAB, 0, true, XR>(A.wo, (int)blockIdx.x - at.nkv, XR == 2 ? A.xt : A.xt + A.wo.K, gen, A.err);
+}
+
 bool fattn_wo_ok(int nh, int nkv, int hd, int cpos, int N, int K, int qm) {
     const int U = rowgemv_u(K, qm);
     return nkv > 0 && nh % nkv == 0 && nh / nkv <= 4 && hd % 2 == 0 && hd <= FW_MAXHD && cpos >= 0 &&
@@ -782,6 +1049,25 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
                         A.qrows == A.wo.res_rows),
             "fused fast attention + wo: the QKV table form is bf16, gathered by the residual's index");
     FMCHECK(!A.kv0 || (qm == 0 && !G && at.cpos == 0), "fused fast attention + wo: the K / V-only form is bf16 at codebook 0");
+    if (A.pair) {
+        FMCHECK(qm == 0 && !A.kv0 && at.cpos == 1 && at.S >= 2 && rowgemv_pair_ok(-1, A.wo.K, false) && (A.qtab != nullptr) == G && (A.pair == 2 || (A.wo.res1 && A.wo.res_out1)),
+                "fused fast attention + wo, pair form: bf16, positions 0 and 1, both rows' residuals set");
+        const bool two = A.pair != 2;
+        // (a one-layer stack would pair the table form with the last-layer form; its row-1 words would also be
+        // written by one launch index only, so two slots at one position could not tell each other's words apart)
+        FMCHECK(two || !A.qtab, "fused fast attention + wo, pair form: the first layer is not the last");
+        switch (rowgemv_u(A.wo.K, 0)) {
+#define FW(u)                                                                                                            \
+    case u:                                                                                                              \
+        (A.qtab ? fattn_wo_pair_kernel<u, true, 2>                                                                       \
+                : (two ? fattn_wo_pair_kernel<u, false, 2> : fattn_wo_pair_kernel<u, false, 1>))<<<grid, block, 0, s>>>(A); \
+        break;
+            FW(2) FW(3) FW(4)
+            default: FW(5)
+#undef FW
+        }
+        return;
+    }
     if (A.qtab || A.kv0) {
         switch (rowgemv_u(A.wo.K, 0)) {
 #define FW(u) \

@@ -107,4 +107,8 @@ FM_KNOB(row_copies, 1, FM_BOOL)            // 1: fm_llm_finalize keeps a row-maj
                                            // rowgemv bits work later (bf16 S2-Pro: ~3.7 GB beside the packed tiles); 0: only the copies the
                                            // rowgemv / rowgemv_q4 bits in force at finalize select (w1 || w3 bf16 / int8: ~3.6 GB saved)
 FM_KNOB(prefix_vec, 1, FM_BOOL)            // voice prefix copy (fm_prefix.hip): 1 16-byte accesses where the runs allow, 0 the scalar path
+FM_KNOB(fast_pair, 1, FM_BOOL)             // 1: batch-1 bf16 frames run the fast decoder's codebook positions 0 and 1 as ONE two-row pass (both input
+                                           // rows are known once the slow sampler has run; every fast weight is then read once for the two, not twice):
+                                           // needs fast_tail, fattn_wo, rowgemv bits 0, 1, 5, 6 and not 2, gemv_chain off; elsewhere, and at 0, the one-row
+                                           // passes (bit-identical)
 #endif

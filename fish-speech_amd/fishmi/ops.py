@@ -258,6 +258,26 @@ def rowgemv(w, x, y, kind, q8=False, bias=None, nw=None, eps=1e-6, res=None, idx
     return (q, sc) if q8 else None
 
 
+def rowgemv_pair(w, x, y, kind, bias=None, nw=None, eps=1e-6, res0=None, res1=None, idx=None, idx_col=0, skip0=0,
+                 device=0):
+    """fm_op_rowgemv_pair: launch_rowgemv's two-row forms.  x [2][K]; kind 0: res0 [N] (row 0's residual), res1
+    [res_rows][ldr] (row 1's, row idx[idx_col] of it); kind 1: skip0 rows of row 0 left out.  y (in/out) [2][ld]."""
+    w, bias, nw, x, res0, res1 = _f(w), _f(bias), _f(nw), _f(x), _f(res0), _f(res1)
+    N, K = w.shape
+    assert x.shape == (2, K)
+    if res1 is not None:
+        res1 = res1.reshape(-1, res1.shape[-1])
+    y = _out(y)
+    assert y.ndim == 2 and y.shape[0] == 2
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, np.int32).ravel()
+    native.check(native.lib().fm_op_rowgemv_pair(device, int(kind), _p(w), _p(bias), _p(nw), float(eps), _p(x), _p(res0),
+                                                 _p(res1), 0 if res1 is None else res1.shape[0],
+                                                 0 if res1 is None else res1.shape[1],
+                                                 None if idx is None else native.i32p(idx), 0 if idx is None else idx.size,
+                                                 int(idx_col), int(skip0), N, K, _p(y), y.shape[1]))
+
+
 PLAN_FIELDS = ("acc", "kparts", "nw", "spw", "tpi", "ntm", "grid")
 
 

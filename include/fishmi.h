@@ -240,7 +240,14 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    recorded after the call (graphs captured earlier keep theirs; fm_llm_use_graph drops them).
    "fattn_ilp" 0|1 (default 1: the fused fast attention + wo launch runs its q / k preparation and
    score / softmax / PV over a compile-time position count in one basic block) changes no output
-   bit either. */
+   bit either.
+   "fast_pair" 0|1 (default 1): a batch-1 bf16 frame runs the fast decoder's codebook positions 0
+   and 1 -- whose input rows, the slow model's hidden row and the embedding of the code the slow
+   sampler drew, are both known when the fast passes start -- as one causal two-row pass, so every
+   fast weight is read once for the two and not twice (13 launches fewer per frame at 4 fast
+   layers).  It engages on bf16 unquantised models at one row with "fast_tail" and "fattn_wo" on,
+   "gemv_chain" off and "rowgemv" bits 0, 1, 5 and 6 set and bit 2 clear, at shapes whose two-row
+   kernel forms exist; anywhere else, and at 0, the one-row passes run.  It changes no output bit. */
 int fm_tune(const char* key, int value);
 int fm_tune_get(const char* key, int* value);
 /* developer hook ("debug_ts" armed): per-block records of 8 words {tag = N<<32 | blockIdx.y<<16 |
@@ -320,7 +327,7 @@ int fm_op_linear(int device, int precision, int epi, const float* w, const float
 /* launch_gemv (R <= 8) on ksb K slices (> 1 only with epi 4 / 5).  idx [R][idx_ld] (optional): column
    idx_col gathers the x rows (pro 1) or the residual rows (epi 5) from a table of idx_rows rows, indices
    clamped into it.  pro 3: x is first finalised by a zero-weight epi-5 launch, which leaves the sums of
-   squares the prologue reads (ss_gran 1: R == 1, the statistic from the staged row instead).  Outputs:
+   squares the prologue reads (ss_gran 1: the statistic from the staged row instead; R == 1, or R == 2 for bf16 epi 7).  Outputs:
    y [R][N] (epi 7: [R][N / 2]; epi 4: fp32 slabs [ksb][R][ldy], bias in slice 0; epi 5: the finalised
    rows round(res + round(x . w^T + bias)), and ss_out [N / 16][R] their per-tile sums of squares). */
 int fm_op_gemv(int device, int precision, int pro, int epi, int ksb, const float* w, const float* w2, const float* bias,
@@ -334,6 +341,13 @@ int fm_op_gemv(int device, int precision, int pro, int epi, int ksb, const float
 int fm_op_rowgemv(int device, int kind, int q8, const float* w, const float* bias, const float* nw, float eps,
                   const float* x, int x_rows, int ldx, const float* res, int res_rows, int ldr, const int32_t* idx,
                   int idx_n, int idx_col, int N, int K, float* y, int y_len, int reps, int8_t* q_out, float* scale_out);
+/* launch_rowgemv's two-row forms (fm_tune "fast_pair"; bf16): x [2][K] against one pass over w.  kind 0 fin:
+   row 0's residual res0 [N], row 1's the row idx[idx_col] of res1 [res_rows][ldr] (its row 0 without idx);
+   kind 1 norm + store: blocks whose 8 rows all lie below skip0 compute row 1 only, and row 0's outputs below
+   skip0 are never stored.  y [2][y_ld] in/out. */
+int fm_op_rowgemv_pair(int device, int kind, const float* w, const float* bias, const float* nw, float eps, const float* x,
+                       const float* res0, const float* res1, int res_rows, int ldr, const int32_t* idx, int idx_n,
+                       int idx_col, int skip0, int N, int K, float* y, int y_ld);
 /* launch_bstream (8 < R <= 32) on bstream_plan's geometry, returned in plan[7] = {acc, kparts, nw, spw,
    tpi, ntm, grid} (acc 1: bsacc_kernel; fm_tune "bstream_acc" 0 or fp32: bstream_kernel).  pro 3 (bsacc,
    epi 0 / 7): the sums of squares come from a zero-weight epi-5 launch over x.  Outputs as fm_op_gemv's,
