@@ -356,12 +356,12 @@ struct FattnWoArgs {
     int prio;                 // 1: attention waves at s_setprio 3 (fm_tune fw_prio)
     int ilp;                  // 1: the attention chain without serial per-position blocks (fm_tune fattn_ilp)
     unsigned long long* dbg;  // developer records (launcher: fm_tune debug_ts)
-    // fm_tune rowgemv bit 5 (the first fast layer at codebook > 0, bf16): the attention blocks take the raw q|k|v
+    // fm_tune rowgemv bit 5 / fast_dead_q bit 0 (the first fast layer at codebook > 0): the attention blocks take the raw q|k|v
     // row from qtab [qrows][at.ldqkv], row qidx[qcol] clamped into it, instead of at.qkv (no QKV launch ran)
     const bf16_t* qtab;
     const int32_t* qidx;
     int qcol, qrows;
-    // fm_tune rowgemv bit 6 (at.cpos == 0, bf16): Q was not computed; the attention output is 0 + v
+    // fm_tune rowgemv bit 6 / fast_dead_q bit 1 (at.cpos == 0): Q was not computed; the attention output is 0 + v
     int kv0;
     // fm_tune fast_pair (bf16, at.cpos == 1): codebook positions 0 and 1 in one launch; at.qkv holds two rows
     // (row 0: the K / V part only), qtab set: row 1's row comes from the table instead.  1: both rows' outputs
@@ -370,6 +370,8 @@ struct FattnWoArgs {
     int pair;
 };
 bool fattn_wo_ok(int nh, int nkv, int hd, int cpos, int N, int K, int qm);
+// ... and whether its table / K-V-only forms (qtab, kv0) exist and stay resident at depth K (fm_tune fast_dead_q)
+bool fattn_wo_dead_ok(int K, int qm);
 void launch_fattn_wo(hipStream_t s, const FattnWoArgs& a);
 // batch-1 GEMV chain (fm_gemv.hip gemv_chain_kernel): 2..GEMV_CHAIN_MAX dependent GEMVs in one launch,
 // whole K per block, one row.  Stage kinds: wo / w2 (PRO_PLAIN, EPI_SLABFIN; the residual may be a

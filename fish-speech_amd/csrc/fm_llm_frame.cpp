@@ -550,11 +550,11 @@ template <typename T> struct Run {
         auto go = [st, g] { launch_gemv_chain<T>(st, g); };
         launch("linear", bytes, flops, go);
     }
-    void gemv(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls) {
+    void gemv(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls, int tile0 = 0) {
         const int kind = chain_kind(a, pro, epi, ksb);
-        if (kind < 0) {
+        if (kind < 0 || tile0) {
             chain_flush();
-            gemv_now(a, pro, epi, ksb, cls);
+            gemv_now(a, pro, epi, ksb, cls, tile0);
             return;
         }
         const size_t E = sizeof(T);
@@ -563,10 +563,22 @@ template <typename T> struct Run {
         if ((int)chain.size() >= std::min(GEMV_CHAIN_MAX, fm_tuning().chain_max) || kind == GEMV_CHAIN_HEAD)
             chain_flush();
     }
-    void gemv_now(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls) {
-        int64_t wbytes = (int64_t)a.N * a.K * E * (epi == EPI_SWIGLU ? 2 : 1);
+    // tile0 (fm_tune fast_dead_q bit 1; weight-only int8, whole K, STORE): the launch covers the 16-row tiles from
+    // tile0 on -- rows [16 tile0, N) of the same packed weight, found by its base a.W: the kernel's tile b is the
+    // weight's tile tile0 + b (a tile's codes are contiguous), so the codes, the row scales, the bias and Y move
+    // by the same rows and N shrinks; the tiles are independent, every output row is the full launch's
+    void gemv_now(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls, int tile0 = 0) {
         const auto* q = m->qinfo(a.W);
         if (q && q->sz && !fm_tuning().int4_stream) q = nullptr;  // int4 model on its dequantised bf16 weights
+        if (tile0) {
+            const int r0 = 16 * tile0;
+            FMCHECK(q && !q->sz && ksb == 1 && epi == EPI_STORE && a.R == 1 && a.Y && tile0 > 0 && r0 < a.N && a.N % 16 == 0,
+                    "GEMV from a tile offset: weight-only int8, whole K, one stored row");
+            a.Y += r0;
+            if (a.bias) a.bias += r0;
+            a.N -= r0;
+        }
+        int64_t wbytes = (int64_t)a.N * a.K * E * (epi == EPI_SWIGLU ? 2 : 1);
         if (q) {
             a.Wq = q->q8;
             if (q->sz) {  // weight-only int4: 4-bit codes + group (scale, zero), whole 128-k units per slice
@@ -578,6 +590,10 @@ template <typename T> struct Run {
                 a.wscale = (const T*)q->scale;
                 while (ksb > 1 && (a.K / ksb) % 64) ksb /= 2;
                 wbytes = (int64_t)a.N * a.K;
+                if (tile0) {
+                    a.Wq += (size_t)tile0 * 16 * a.K;
+                    a.wscale += 16 * tile0;
+                }
             }
         }
         const int64_t bytes = wbytes + (int64_t)a.R * a.K * E;
@@ -627,6 +643,19 @@ template <typename T> struct Run {
             r.wscale = (const bf16_t*)(it != m->rowscale.end() ? it->second : m->qinfo(packed)->scale);
         } else {
             r.W = (const bf16_t*)rm;
+        }
+    }
+    // ... from its row row0 on (K columns): the rows, and with them the int4 code words and (scale, zero) rows or the
+    // int8 codes and row scales, start row0 rows in; the caller moves bias, Y and N
+    static void row_weight_from(RowGemvArgs& r, int row0, int K) {
+        if (r.Wq4) {
+            r.Wq4 += (size_t)row0 * (K / 8);
+            r.wsz += (size_t)row0 * (K / r.gs);
+        } else if (r.Wq) {
+            r.Wq += (size_t)row0 * K;
+            r.wscale += row0;
+        } else {
+            r.W += (size_t)row0 * K;
         }
     }
     // weight bytes a row-block GEMV streams (int4: codes + group words; int8: codes + row scales)
@@ -720,7 +749,7 @@ template <typename T> struct Run {
             r.skip0 = d.nq();
         }
         if (kv_rows) {
-            r.W += (size_t)d.nq() * d.dim;
+            row_weight_from(r, d.nq(), d.dim);
             if (r.bias) r.bias += d.nq();
             r.Y += d.nq();
             r.N -= d.nq();
@@ -746,7 +775,8 @@ template <typename T> struct Run {
         a.xidx_ld = m->C1;
         a.xidx_col = xcol;
         a.xidx_rows = xidx ? m->cb : 0;
-        gemv(a, PRO_NORM, EPI_STORE, 1, "linear");
+        // (kv_rows on the tile form: weight-only int8 only, small_path; the tiles from nq / 16 on)
+        gemv(a, PRO_NORM, EPI_STORE, 1, "linear", kv_rows ? d.nq() / 16 : 0);
     }
     // the tile form's arguments of a fast layer's QKV at one row, no prefetch (the table build)
     GemvArgs<T> qkv_args(const StackDims& d, const LayerW& L, int n) {
@@ -761,9 +791,13 @@ template <typename T> struct Run {
         a.ldy = d.nqkv();
         return a;
     }
-    // whether block_small may read the first fast layer's QKV from the table (bit 5; bf16, unquantised)
+    // fm_tune fast_dead_q's bits in force: weight-only int8 / int4 handles whose fast stack has no o-bias (the
+    // quantised linears carry no bias, finalize; a model configured with one stays on the launches it has)
+    static int dead_q_bits(const fm_llm* m) { return m->quant && !m->fdm.o_bias ? fm_tuning().fast_dead_q : 0; }
+    // whether block_small may read the first fast layer's QKV from the table (bf16 compute: rowgemv bit 5 on
+    // unquantised weights, fast_dead_q bit 0 on quantised ones)
     bool qkv0_live() const {
-        return sizeof(T) == 2 && !m->quant && (row_bits() & 32) && m->qkv0 && m->qkv0_built &&
+        return sizeof(T) == 2 && (m->quant ? (dead_q_bits(m) & 1) : (row_bits() & 32)) && m->qkv0 && m->qkv0_built &&
                m->qkv0_epoch == fm_tuning().epoch;
     }
 
@@ -802,8 +836,8 @@ template <typename T> struct Run {
         bool fw;        // fast model: attention + wo as one launch (fattn_wo_kernel), no attention launch
         bool att_wo;    // fast model: attention recomputed in the wo tile GEMV's prologue (PRO_FATT), no attention launch
         bool row_here;  // this layer's QKV on the row-block GEMV (a stack's first layer: only with rowgemv bit 4)
-        bool tab;       // rowgemv bit 5: the first fast layer at codebook > 0 inside fw: its q|k|v row comes from the table, no QKV launch
-        bool kv0;       // rowgemv bit 6: codebook 0 on the row path: only K / V are projected and the attention reads no Q (one position: output = v)
+        bool tab;       // rowgemv bit 5 / fast_dead_q bit 0: the first fast layer at codebook > 0 inside fw: its q|k|v row comes from the table, no QKV launch
+        bool kv0;       // rowgemv bit 6 / fast_dead_q bit 1: codebook 0: only K / V are projected (row path; int8: the tile path) and the attention reads no Q (one position: output = v)
         bool kv_only;   // the layer ends after its K / V cache write (fm_tune fast_tail: its output would be discarded)
     };
     SmallPath small_path(const Small& c, bool kv_only) const {
@@ -812,17 +846,27 @@ template <typename T> struct Run {
         p.kv_only = kv_only;
         p.rf = row_fin(c.n);
         const int fq = m->quant == FM_QUANT_INT8 ? 1 : (m->quant == FM_QUANT_INT4 ? 2 : 0);
-        p.fw = c.is_fast && !kv_only && p.rf && fm_tuning().fattn_wo && m->fxt && m->fdm.n_layer * m->C >= 2 &&
-               m->fdm.n_layer * m->C <= 40 && fattn_wo_ok(d.nh, d.nkv, d.hd, c.cpos, d.dim, d.nq(), fq);
+        // (fw_any: the fused launch is this layer's form, whether or not this pass ends before it)
+        const bool fw_any = c.is_fast && p.rf && fm_tuning().fattn_wo && m->fxt && m->fdm.n_layer * m->C >= 2 &&
+                            m->fdm.n_layer * m->C <= 40 && fattn_wo_ok(d.nh, d.nkv, d.hd, c.cpos, d.dim, d.nq(), fq);
+        p.fw = fw_any && !kv_only;
         // (fm_tune attn_wo; measured slower, kept under test)
         p.att_wo = c.is_fast && !kv_only && fm_tuning().attn_wo && !m->quant && c.n == 1 && c.cpos < 16 && d.hd % 16 == 0 &&
                    d.hd <= 128 && d.nh % d.nkv == 0 && (d.nq() / c.kp.wo) % d.hd == 0 && d.nqkv() % 8 == 0;
         p.row_here = row_qkv(c.n) && (!c.first || (row_bits() & 16));
         // bits 5 / 6: bf16, unquantised, batch 1; inert elsewhere (with kv0 the Q part of m->qkv is stale)
         const bool bits56 = sizeof(T) == 2 && !m->quant && c.is_fast && c.n == 1;
-        p.tab = bits56 && c.first && c.xidx && p.fw && qkv0_live();
+        // fm_tune fast_dead_q: the same two forms on weight-only int8 / int4 handles, only where the fused launch is
+        // the layer's form and its table / K-V-only instantiation is one that stays resident (fattn_wo_dead_ok).
+        // K / V only: int4 on the row form as bf16 (8 rows per block), int8 on the tile form from tile nq / 16
+        const int dq = sizeof(T) == 2 && c.is_fast && c.n == 1 && fw_any && fattn_wo_dead_ok(d.nq(), fq) ? dead_q_bits(m) : 0;
+        p.tab = (bits56 || (dq & 1)) && c.first && c.xidx && p.fw && qkv0_live();
         p.kv0 = bits56 && c.cpos == 0 && (row_bits() & 64) && p.row_here && !p.att_wo && d.hd <= 256 &&
                 (d.nqkv() - d.nq()) % fm_tuning().row_qkv_rp == 0;
+        if ((dq & 2) && c.cpos == 0 && !p.att_wo && d.hd <= 256)
+            p.kv0 = m->quant == FM_QUANT_INT4
+                        ? p.row_here && (d.nqkv() - d.nq()) % fm_tuning().row_qkv_rp == 0 && (d.nqkv() - d.nq()) % 8 == 0
+                        : !p.row_here && d.nq() % 16 == 0 && d.nqkv() % 16 == 0;
         return p;
     }
     // the fast model's attention operands at this layer (the attention launch, fattn_wo, PRO_FATT)
@@ -859,7 +903,7 @@ template <typename T> struct Run {
             a.ldx = d.dim;
             a.ss_in = m->ssX;
             a.ss_gran = p.rf ? 1 : 0;
-            gemv(a, PRO_PRENORM, EPI_STORE, 1, "linear");
+            gemv(a, PRO_PRENORM, EPI_STORE, 1, "linear", p.kv0 ? d.nq() / 16 : 0);  // (kv0 here: weight-only int8)
         }
     }
     // attention launch (none where wo does it: fw, att_wo)
@@ -1444,11 +1488,15 @@ template <typename F> static int with_prec(fm_llm* m, F&& f) {
 // block_small's own first-layer QKV helper per code (Run::qkv_first: the kernel the frame would run, on
 // the row fast_embeddings[code]), so the table holds the bytes that launch would have written.  Built at
 // load time and again whenever an fm_tune call since could have changed the helper's kernel (the tuning
-// epoch); never inside a capture.  bf16 unquantised models only: bits 5 / 6 are inert for int8 / int4.
+// epoch); never inside a capture.  Weight-only int8 / int4 handles build it the same way under fm_tune fast_dead_q
+// bit 0 (int8: the PRO_NORM tile kernel on the int8 stream; int4: the row form with the gather), where the fused
+// launch can run at all (row-major wo / w2 copies; int4: int4_stream).
 void ensure_qkv0(fm_llm* m) {
     FmTuning& t = fm_tuning();
-    if (!m->finalized || m->prec != FM_PREC_BF16 || m->quant || !(t.rowgemv & 32) || !m->fxt || m->C < 2 ||
-        !t.fattn_wo || t.gemv_chain || m->fast.empty())
+    const bool want = m->quant ? (Run<bf16_t>::dead_q_bits(m) & 1) && m->row_ok && (m->quant != FM_QUANT_INT4 || t.int4_stream)
+                               : (t.rowgemv & 32) != 0;
+    if (!m->finalized || m->prec != FM_PREC_BF16 || !want || !m->fxt || m->C < 2 || !t.fattn_wo || t.gemv_chain ||
+        m->fast.empty())
         return;
     if (m->qkv0_built && m->qkv0_epoch == t.epoch) return;
     const StackDims& d = m->fdm;

@@ -660,7 +660,8 @@ __device__ __forceinline__ void fw_attend(const bf16_t* Ks, const bf16_t* Vs, co
 }
 
 //
-// M (bf16 only): 0 the attention reads the raw q|k|v row the QKV launch left in at.qkv.
+// M (the attention half is bf16 whatever QM the wo half streams; forms 1 and 2 on int8 / int4 weights: fm_tune
+// fast_dead_q): 0 the attention reads the raw q|k|v row the QKV launch left in at.qkv.
 // 1 (fm_tune rowgemv bit 5, the first layer at codebook > 0): that row is a pure function of the
 //   sampled code -- round(Wqkv rmsnorm(fast_embeddings[code]) + b) -- so it is read from the table
 //   of all codebook_size rows built at load time (A.qtab) and no QKV launch runs.  The index goes
@@ -674,7 +675,6 @@ __device__ __forceinline__ void fw_attend(const bf16_t* Ks, const bf16_t* Vs, co
 template <int U, bool G, int QM, int M>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
 void fattn_wo_kernel(FattnWoArgs A) {
-    static_assert(M == 0 || QM == 0, "table / K-V-only forms: bf16 only");
     static_assert(2 * FW_MAXJ * FW_MAXHD / 8 <= 512, "cached rows: at most two 16-B chunks per thread");
     __shared__ __attribute__((aligned(16))) bf16_t kvs[2 * FW_MAXJ * FW_MAXHD];
     __shared__ float red[8];
@@ -1032,6 +1032,16 @@ bool fattn_wo_ok(int nh, int nkv, int hd, int cpos, int N, int K, int qm) {
            cpos < FW_MAXJ + 1 && K == nh * hd && N % 2 == 0 && U > 0 && U <= 8;
 }
 
+// Whether the table (M 1) and K / V-only (M 2) forms at depth K of int8 (qm 1) / int4 (qm 2) weights may be
+// dispatched: the launch is deadlock-free only while its whole grid is resident -- at most 80 VGPRs, no scratch,
+// under 26 KiB LDS (code-object metadata).  Elsewhere the frame keeps its launches.
+bool fattn_wo_dead_ok(int K, int qm) {
+    const int U = rowgemv_u(K, qm);
+    // int8 / int4: depths 2 .. 5 hold 36 .. 79 VGPRs without scratch; 6 and 8 spill (20 .. 136 B per lane at 80 VGPRs,
+    // as their M 0 forms do) and are not instantiated
+    return U > 0 && U <= (qm ? 5 : 8);
+}
+
 void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
     FattnWoArgs A = A0;
     A.dbg = fm_tuning().dbg;
@@ -1045,10 +1055,12 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
     const dim3 grid(at.nkv + A.wo.N / 2), block(256);
     const bool G = A.wo.residx != nullptr;
     // the table form gathers its residual row by the same index; the K / V-only form runs at codebook 0 (no gather)
-    FMCHECK(!A.qtab || (qm == 0 && G && !A.kv0 && A.qidx == A.wo.residx && A.qcol == A.wo.res_col && A.qrows > 0 &&
+    FMCHECK(!A.qtab || (G && !A.kv0 && A.qidx == A.wo.residx && A.qcol == A.wo.res_col && A.qrows > 0 &&
                         A.qrows == A.wo.res_rows),
-            "fused fast attention + wo: the QKV table form is bf16, gathered by the residual's index");
-    FMCHECK(!A.kv0 || (qm == 0 && !G && at.cpos == 0), "fused fast attention + wo: the K / V-only form is bf16 at codebook 0");
+            "fused fast attention + wo: the QKV table form is gathered by the residual's index");
+    FMCHECK(!A.kv0 || (!G && at.cpos == 0), "fused fast attention + wo: the K / V-only form runs at codebook 0");
+    FMCHECK(!(A.qtab || A.kv0) || fattn_wo_dead_ok(A.wo.K, qm),
+            "fused fast attention + wo: no resident table / K-V-only form at this depth of int8 / int4 weights");
     if (A.pair) {
         FMCHECK(qm == 0 && !A.kv0 && at.cpos == 1 && at.S >= 2 && rowgemv_pair_ok(-1, A.wo.K, false) && (A.qtab != nullptr) == G && (A.pair == 2 || (A.wo.res1 && A.wo.res_out1)),
                 "fused fast attention + wo, pair form: bf16, positions 0 and 1, both rows' residuals set");
@@ -1066,6 +1078,21 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
             default: FW(5)
 #undef FW
         }
+        return;
+    }
+    if ((A.qtab || A.kv0) && qm) {  // fm_tune fast_dead_q: the depths fattn_wo_dead_ok admits
+        auto dead = [&](auto q) {
+            constexpr int Q = decltype(q)::value;
+            switch (rowgemv_u(A.wo.K, Q)) {
+#define FW(u) \
+    case u: (A.qtab ? fattn_wo_kernel<u, true, Q, 1> : fattn_wo_kernel<u, false, Q, 2>)<<<grid, block, 0, s>>>(A); break;
+                FW(2) FW(3) FW(4)
+                default: FW(5)
+#undef FW
+            }
+        };
+        if (qm == 2) dead(std::integral_constant<int, 2>{});
+        else dead(std::integral_constant<int, 1>{});
         return;
     }
     if (A.qtab || A.kv0) {

@@ -111,4 +111,8 @@ FM_KNOB(fast_pair, 1, FM_BOOL)             // 1: batch-1 bf16 frames run the fas
                                            // rows are known once the slow sampler has run; every fast weight is then read once for the two, not twice):
                                            // needs fast_tail, fattn_wo, rowgemv bits 0, 1, 5, 6 and not 2, gemv_chain off; elsewhere, and at 0, the one-row
                                            // passes (bit-identical)
+FM_KNOB(fast_dead_q, 1, FM_RANGE(0, 3))    // weight-only int8 / int4 handles only (rowgemv bits 5 / 6 govern unquantised bf16): bit 0 the first fast layer's
+                                           // QKV at codebooks >= 1 read from the table, bit 1 K / V only at codebook 0 -- batch 1, inside the fused fast
+                                           // attention + wo, models without an o-bias (bit-identical).  S2-Pro frame, int8 /
+                                           // int4: bit 0 -69 / -59 us (2.3 / 2.0 %); bit 1 -1.2 / -8.0 us, inside three times the baseline's spread: off
 #endif

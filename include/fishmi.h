@@ -247,7 +247,12 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    fast weight is read once for the two and not twice (13 launches fewer per frame at 4 fast
    layers).  It engages on bf16 unquantised models at one row with "fast_tail" and "fattn_wo" on,
    "gemv_chain" off and "rowgemv" bits 0, 1, 5 and 6 set and bit 2 clear, at shapes whose two-row
-   kernel forms exist; anywhere else, and at 0, the one-row passes run.  It changes no output bit. */
+   kernel forms exist; anywhere else, and at 0, the one-row passes run.  It changes no output bit.
+   "fast_dead_q" 0..3 (default 1): the two removals of "rowgemv" bits 5 and 6 for weight-only int8 /
+   int4 handles, which those bits leave alone -- bit 0 (1) the first fast layer's QKV table (built the
+   same way, by the quantised model's own launch), bit 1 (2) K / V only at codebook 0.  They act at batch
+   1 in bf16 compute where the fused fast attention + wo launch runs, on models configured without an
+   o-bias, and change no output bit; inert on unquantised models and everywhere else. */
 int fm_tune(const char* key, int value);
 int fm_tune_get(const char* key, int* value);
 /* developer hook ("debug_ts" armed): per-block records of 8 words {tag = N<<32 | blockIdx.y<<16 |
