@@ -725,10 +725,10 @@ static BstreamPlan bsacc_plan(int N, int K, int R, int epi, size_t esz) {
     return p;
 }
 
-BstreamPlan bstream_plan(int N, int K, int R, int epi, size_t esz) {
+BstreamPlan bstream_plan(int N, int K, int R, int epi, size_t esz, bool acc_default) {
     BstreamPlan p{};
     const FmTuning& tu = fm_tuning();
-    if (tu.bstream_acc) {
+    if (tu.bstream_acc || acc_default) {
         p = bsacc_plan(N, K, R, epi, esz);
         if (p.ok) return p;
     }

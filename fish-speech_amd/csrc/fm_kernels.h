@@ -71,6 +71,12 @@ template <typename T> struct LinearArgs {
     // weight-only int8 (tools/llama/quantize.py WeightOnlyInt8Linear): W holds the int8 values
     // exactly and every output is round(round(acc) * wscale[n]) (not with EPI_SWIGLU)
     const T* wscale = nullptr;
+    // the code-reading forms (bf16; EPI_STORE / EPI_RESID / EPI_F32): W is null and the kernel rebuilds every
+    // bf16 weight fragment, bit for bit, from the step-granular code copy right before its MFMAs --
+    // Wq8s (launch_pack_q8s, Frag::dq8s), or Wq4s with wsz (launch_pack_q4s / launch_pack_sz4, Frag::dq4s)
+    const unsigned char* Wq8s = nullptr;
+    const uint32_t* Wq4s = nullptr;
+    const uint32_t* wsz = nullptr;
 };
 
 template <typename T> struct QkArgs {
@@ -438,7 +444,8 @@ struct BstreamPlan {
     int kparts = 1, nw = 0, spw = 0, tpi = 1, grid = 0;
     int acc = 0, ntm = 0;  // bsacc_kernel: tiles per block at most (register accumulators)
 };
-BstreamPlan bstream_plan(int N, int K, int R, int epi, size_t esz);
+// (acc_default: plan as under fm_tune bstream_acc 1 whatever the knob says -- a compact handle, fm_llm_model.h)
+BstreamPlan bstream_plan(int N, int K, int R, int epi, size_t esz, bool acc_default = false);
 // whether launch_bstream has an int8-code form (BstreamArgs::Wq8) for this plan, epilogue and prologue
 bool bsacc_q8_ok(const BstreamPlan& p, int epi, int pro, size_t esz);
 // ... and an int4-code form (BstreamArgs::Wq4 / wsz): the same forms, K in whole 128-k units

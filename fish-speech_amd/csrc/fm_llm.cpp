@@ -177,6 +177,30 @@ int fm_llm_set_quant(fm_llm* m, int mode) {
     });
 }
 
+int fm_llm_set_quant_compact(fm_llm* m, int enable) {
+    return fm_guard([&] {
+        FMCHECK(m, "null handle");
+        auto state = [](bool ok, const char* msg) {
+            if (!ok) throw FmError{FM_ERR_STATE, msg};
+        };
+        state(!m->finalized, "weights are frozen after finalize");
+        FMCHECK(m->prec == FM_PREC_BF16, "compact: bf16 precision only (the code-reading kernel forms are bf16)");
+        state(m->quant != FM_QUANT_NONE, "compact: set the quantization mode first (fm_llm_set_quant / fm_llm_set_quant_int4)");
+        for (auto& kv : m->w) state(!kv.second.set, "compact: set it before any tensor");
+        m->compact = enable != 0;
+    });
+}
+
+int fm_llm_memory_info(fm_llm* m, int64_t out[8]) {
+    return fm_guard([&] {
+        FMCHECK(m && out, "null argument");
+        if (!m->finalized) throw FmError{FM_ERR_STATE, "memory_info: finalize the handle first"};
+        int64_t sum = 0;
+        for (int i = 0; i < 7; ++i) sum += out[i] = m->mem[i];
+        out[7] = sum;
+    });
+}
+
 int fm_llm_set_tensor(fm_llm* m, const char* name, const void* data, int dtype, int64_t numel) {
     return fm_guard([&] {
         FMCHECK(m && name && data, "null argument");

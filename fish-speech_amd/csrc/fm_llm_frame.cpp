@@ -134,15 +134,32 @@ template <typename T> struct Run {
             bs_linear(W, bias, X, ldx, R, N, K, Y, ldy, Yf, epi))
             return;  // heads / fast_project_in of a batched frame
         if (prompt_gemm(W, W2, bias, X, ldx, R, N, K, Y, ldy, res, ldr, epi, cls)) return;
-        LinearArgs<T> a{(const T*)W, (const T*)W2, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y,
+        LinearArgs<T> a{(const T*)m->wdev(W), (const T*)W2, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y,
                         ldy, (const T*)res, ldr, Yf};
-        if (const auto* q = m->qinfo(W)) a.wscale = (const T*)q->scale;
+        const auto* q = m->qinfo(W);
+        if (q) a.wscale = (const T*)q->scale;
+        const bool codes = q && q->compact;  // no bf16 copy: linear_kernel's code-reading form
+        if (codes) {
+            FMCHECK(sizeof(T) == 2 && !W2 && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_F32),
+                    "compact linear: linear_kernel has no code-reading form of this launch");
+            if (q->sz) {
+                FMCHECK(q->q4s && K % 128 == 0, "compact int4 linear without its step-granular codes");
+                a.Wq4s = q->q4s;
+                a.wsz = q->sz;
+            } else {
+                FMCHECK(q->q8s && K % 32 == 0, "compact int8 linear without its step-granular codes");
+                a.Wq8s = q->q8s;
+            }
+        }
         if (R > GEMV_MAX_ROWS && R <= 64) {  // batched decode: split-K over the idle CUs
             FMCHECK(m->skpart_cap >= (long long)LINEAR_PART_CAP, "split-K partial buffer too small");
             a.part = m->skpart;
             a.tickets = m->tickets;
         }
-        const int64_t wbytes = (int64_t)N * K * E * (epi == EPI_SWIGLU ? 2 : 1);
+        // (a code form's bytes: bs_linear's formulas)
+        const int64_t wbytes = a.Wq4s   ? (int64_t)N * K / 2 + (int64_t)N * (K / 128) * 4
+                               : a.Wq8s ? (int64_t)N * K + (int64_t)N * 2
+                                        : (int64_t)N * K * E * (epi == EPI_SWIGLU ? 2 : 1);
         const int64_t bytes = wbytes + (int64_t)R * K * E + (int64_t)R * N * (epi == EPI_F32 ? 4 : E);
         const double flops = 2.0 * R * N * K * (epi == EPI_SWIGLU ? 2 : 1);
         hipStream_t st = s;
@@ -174,8 +191,10 @@ template <typename T> struct Run {
         else
             launch_attn_decode2<T>(s, aa, R);
     }
+    // (a compact handle runs its default routing whatever the process-wide knobs that would pick a reader of the
+    // bf16 copy say -- bstream, bstream_acc, bstream_chain, bstream_q8, bstream_q4, int4_stream: fm_tune's comment)
     bool bs_use(int R, bool) const {
-        return fm_tuning().bstream && bs_frame && R > GEMV_MAX_ROWS && R <= 32 && m->bsA;
+        return (fm_tuning().bstream || m->compact) && bs_frame && R > GEMV_MAX_ROWS && R <= 32 && m->bsA;
     }
     // one bstream linear; returns false (nothing launched) when the shape is not eligible
     // bsacc_kernel's fused prologue / epilogue operands (the batched SLABFIN / PRENORM chain)
@@ -189,20 +208,24 @@ template <typename T> struct Run {
     };
     bool bs_linear(const void* W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
                    float* Yf, int epi, int* kparts_out = nullptr, const BsExtra* ex = nullptr) {
-        const BstreamPlan p = bstream_plan(N, K, R, epi, E);
+        const BstreamPlan p = bstream_plan(N, K, R, epi, E, m->compact);
         if (!p.ok || ((epi == EPI_SLABFIN || (ex && ex->pro == PRO_PRENORM)) && !p.acc)) return false;
-        BstreamArgs<T> a{(const T*)W, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y, ldy, Yf};
+        BstreamArgs<T> a{(const T*)m->wdev(W), (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y, ldy, Yf};
         const auto* q = m->qinfo(W);
+        const bool codes = q && q->compact;  // no bf16 copy: only a code-streaming form will do
         if (q) a.wscale = (const T*)q->scale;
         // weight-only int8 (fm_tune bstream_q8): the accumulating kernel streams the codes where it has the form
-        if (q && q->q8s && fm_tuning().bstream_q8 && bsacc_q8_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E)) a.Wq8 = q->q8s;
+        if (q && q->q8s && (fm_tuning().bstream_q8 || codes) && bsacc_q8_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E)) a.Wq8 = q->q8s;
         // weight-only int4 (fm_tune bstream_q4; int4_stream 0 keeps the whole model on its dequantised weights):
         // the 4-bit codes and their (scale, zero) table
-        if (q && q->q4s && q->sz && fm_tuning().bstream_q4 && fm_tuning().int4_stream &&
+        if (q && q->q4s && q->sz && ((fm_tuning().bstream_q4 && fm_tuning().int4_stream) || codes) &&
             bsacc_q4_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E, K)) {
             a.Wq4 = q->q4s;
             a.wsz = q->sz;
         }
+        // the plan's kernel has no code instantiation: nothing launched, the caller's else branch reaches linear()
+        if (codes && !a.Wq8 && !a.Wq4) return false;
+        FMCHECK(a.W || a.Wq8 || (a.Wq4 && a.wsz), "bstream: no weight for the selected form");
         a.dbg = fm_tuning().dbg;
         if (ex) {
             a.pro = ex->pro;
@@ -238,7 +261,7 @@ template <typename T> struct Run {
     // prologue's X rows and tile sums arrive ~7 us into the launch (scripts/b32_ts.py "xready"),
     // 3-4 us later than a plain prologue's, and the last K part's finalise adds 3-5 us to Wo / W2.
     bool bs_chain(const StackDims& d, int R) const {
-        if (!fm_tuning().bstream_chain || E != 2 || R > 32) return false;
+        if (!fm_tuning().bstream_chain || m->compact || E != 2 || R > 32) return false;  // (the chain forms read bf16 tiles)
         auto ok = [&](int N, int K, int epi) { return bstream_plan(N, K, R, epi, E).acc; };
         return ok(d.nqkv(), d.dim, EPI_STORE) && ok(d.dim, d.nq(), EPI_SLABFIN) && ok(2 * d.inter, d.dim, EPI_SWIGLU8) &&
                ok(d.dim, d.inter, EPI_SLABFIN);
@@ -569,7 +592,12 @@ template <typename T> struct Run {
     // by the same rows and N shrinks; the tiles are independent, every output row is the full launch's
     void gemv_now(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls, int tile0 = 0) {
         const auto* q = m->qinfo(a.W);
-        if (q && q->sz && !fm_tuning().int4_stream) q = nullptr;  // int4 model on its dequantised bf16 weights
+        const bool codes = q && q->compact;  // a.W is the linear's key, not an address: the kernel gets the codes alone
+        if (q && q->sz && !fm_tuning().int4_stream && !codes) q = nullptr;  // int4 model on its dequantised bf16 weights
+        if (codes) {
+            FMCHECK(q->q8 && (q->sz || q->scale) && epi != EPI_SWIGLU, "compact linear without its decode-GEMV codes");
+            a.W = nullptr;
+        }
         if (tile0) {
             const int r0 = 16 * tile0;
             FMCHECK(q && !q->sz && ksb == 1 && epi == EPI_STORE && a.R == 1 && a.Y && tile0 > 0 && r0 < a.N && a.N % 16 == 0,
@@ -613,26 +641,27 @@ template <typename T> struct Run {
     bool row_fin(int n) const {
         const FmTuning& t = fm_tuning();
         return sizeof(T) == 2 && n == 1 && m->row_ok && (row_bits() & 1) && !t.gemv_chain && !t.attn_wo &&
-               (m->quant != FM_QUANT_INT4 || t.int4_stream);
+               (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact);
     }
     // ... and wqkv (norm prologue, 8 rows per block)
     bool row_qkv(int n) const {
         const FmTuning& t = fm_tuning();
         // (int8: the tile kernel's wqkv measured as fast, 3.12 vs 3.14 ms per frame)
         return sizeof(T) == 2 && n == 1 && m->row_qkv_ok && m->quant != FM_QUANT_INT8 && (row_bits() & 2) &&
-               !t.gemv_chain && (m->quant != FM_QUANT_INT4 || t.int4_stream);
+               !t.gemv_chain && (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact);
     }
     // ... and w1 || w3 (norm prologue, SwiGLU epilogue, 4 + 4 rows per block)
     bool row_w13(int n) const {
         const FmTuning& t = fm_tuning();
         return sizeof(T) == 2 && n == 1 && m->row_w13_ok && (row_bits() & 4) && !t.gemv_chain &&
-               (m->quant != FM_QUANT_INT4 || t.int4_stream);
+               (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact);
     }
     // the row-block GEMV's weight: bf16 row-major, or the int8 codes + row scales, or the int4 code words + group
     // (scale, zero) rows.  rowscale holds only w1 || w3's row-block interleaved scales (pack_w13 is its one
     // writer), so for every other linear -- the codebook head included -- the lookup misses and the packed
     // weight's own row scales apply.
     void row_weight(RowGemvArgs& r, const void* rm, const void* packed) {
+        FMCHECK(rm, "row GEMV: the linear has no row-major copy");  // (packed may be a compact linear's key: never read)
         if (m->quant == FM_QUANT_INT4) {
             r.Wq4 = (const uint32_t*)rm;
             r.wsz = (const uint32_t*)m->rowsz.at(packed);
@@ -1182,7 +1211,7 @@ template <typename T> struct Run {
     void fast_head(int n, const void* x) {
         const fm_model_config& c = m->c;
         if (sizeof(T) == 2 && n == 1 && m->fout_rm && (row_bits() & 8) && !fm_tuning().gemv_chain &&
-            (m->quant != FM_QUANT_INT4 || fm_tuning().int4_stream)) {
+            (m->quant != FM_QUANT_INT4 || fm_tuning().int4_stream || m->compact)) {
             RowGemvArgs r{};  // the codebook head on the row-block GEMV (norm prologue, fp32 logits)
             row_weight(r, m->fout_rm, m->fout);
             r.X = (const bf16_t*)x;
@@ -1493,7 +1522,7 @@ template <typename F> static int with_prec(fm_llm* m, F&& f) {
 // launch can run at all (row-major wo / w2 copies; int4: int4_stream).
 void ensure_qkv0(fm_llm* m) {
     FmTuning& t = fm_tuning();
-    const bool want = m->quant ? (Run<bf16_t>::dead_q_bits(m) & 1) && m->row_ok && (m->quant != FM_QUANT_INT4 || t.int4_stream)
+    const bool want = m->quant ? (Run<bf16_t>::dead_q_bits(m) & 1) && m->row_ok && (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact)
                                : (t.rowgemv & 32) != 0;
     if (!m->finalized || m->prec != FM_PREC_BF16 || !want || !m->fxt || m->C < 2 || !t.fattn_wo || t.gemv_chain ||
         m->fast.empty())
@@ -1501,7 +1530,9 @@ void ensure_qkv0(fm_llm* m) {
     if (m->qkv0_built && m->qkv0_epoch == t.epoch) return;
     const StackDims& d = m->fdm;
     if (!m->qkv0) {
+        m->mem_cat = 4;  // fm_llm_memory_info: the table is a weight
         m->qkv0 = m->dalloc((size_t)m->cb * d.nqkv() * sizeof(bf16_t), false);
+        m->mem_cat = 6;
         std::vector<int32_t> io((size_t)m->cb);
         for (size_t i = 0; i < io.size(); ++i) io[i] = (int32_t)i;
         m->qkv0_iota = (int32_t*)m->dalloc(io.size() * sizeof(int32_t), false);

@@ -14,6 +14,7 @@
 //   sample_kernel ............ inference.py:43-93, 117-144 (top-k / top-p / temperature /
 //                              RAS with the reference's rounding; no full-vocab sort)
 #include "fm_kernels.h"
+#include "fm_runtime.h"
 #include "fm_frag.h"
 
 // =========================================================================================
@@ -421,10 +422,21 @@ __device__ __forceinline__ void linear_epi(const LinearArgs<T>& a, int n, int co
 // ticket; the tile's last-arriving block sums the ksb partials in slice order (deterministic)
 // with sc1 loads and runs the epilogue (cdna_hip_programming.md split-K recipe, the same hand-off
 // as gemv_kernel's EPI_SLABFIN).
-template <typename T, int NCG, int EPI, int U>
+//
+// WM, the weight mode: 0 the packed T fragments of a.W.  1 / 2 (bf16, one weight matrix): a.W is null and the
+// fragment of (tile, step) is rebuilt from the step-granular code copy -- the lane's 8 int8 bytes (a.Wq8s,
+// Frag::dq8s), or its 4-byte word of 4-bit codes (a.Wq4s) with the (scale, zero) word of (tile, 128-k unit
+// step >> 2, row lane & 15) from a.wsz, loaded once per unit (Frag::dq4s) -- right before that step's MFMAs.
+// Both rebuild the bits the bf16 copy holds, and the steps, their order and every reduction are mode 0's,
+// so every fp32 sum has the same operands in the same order: the three modes give the same bytes.
+template <typename T, int NCG, int EPI, int U, int WM = 0>
 __global__ __launch_bounds__(512) void linear_kernel(LinearArgs<T> a) {
     using M = Frag<T>;
     constexpr int NACC = (EPI == EPI_SWIGLU) ? 2 : 1;
+    static_assert(WM == 0 || (sizeof(T) == 2 && NACC == 1), "code-reading forms: bf16, one weight matrix");
+    // one step's raw weight operand in the ring: the fragment itself, 8 code bytes, or one word of 8 nibbles
+    typedef typename std::conditional<WM == 2, uint32_t, typename std::conditional<WM == 1, u32x2_t, typename M::f>::type>::type raw_t;
+    constexpr int NZ = WM == 2 ? U / 4 + 1 : 1;  // 128-k units a run of U steps can touch
     __shared__ f32x4_t red[8][NACC * NCG][64];
     __shared__ int last_flag;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -437,6 +449,24 @@ __global__ __launch_bounds__(512) void linear_kernel(LinearArgs<T> a) {
     // packed weights: block (tile, step) = 512 elements
     const T* wp = a.W + (size_t)blockIdx.x * nsteps * 512;
     const T* wp2 = (EPI == EPI_SWIGLU) ? a.W2 + (size_t)blockIdx.x * nsteps * 512 : nullptr;
+    // the tile's codes, [step][64 lanes] of 8 bytes (int8) or 4 (int4), and its (scale, zero) words [unit][16 rows]
+    const u32x2_t* q8p = nullptr;
+    const uint32_t *q4p = nullptr, *szp = nullptr;
+    if constexpr (WM == 1) q8p = reinterpret_cast<const u32x2_t*>(a.Wq8s + (size_t)blockIdx.x * nsteps * 512) + lane;
+    if constexpr (WM == 2) {
+        q4p = a.Wq4s + (size_t)blockIdx.x * nsteps * 64 + lane;
+        szp = a.wsz + (size_t)blockIdx.x * (a.K >> 7) * 16 + r;
+    }
+    auto load_raw = [&](int st) -> raw_t {
+        if constexpr (WM == 1) return q8p[(size_t)st * 64];
+        else if constexpr (WM == 2) return q4p[(size_t)st * 64];
+        else return M::load_w(wp + (size_t)st * 512, lane);
+    };
+    auto expand = [&](raw_t v, uint32_t z) -> typename M::f {
+        if constexpr (WM == 1) return M::dq8s(v);
+        else if constexpr (WM == 2) return M::dq4s(v, __uint_as_float(z << 16), __uint_as_float(z & 0xffff0000u));
+        else return v;
+    };
 
     for (int c0 = 0; c0 < a.R; c0 += 16 * NCG) {
         f32x4_t acc[NACC][NCG];
@@ -451,27 +481,47 @@ __global__ __launch_bounds__(512) void linear_kernel(LinearArgs<T> a) {
         }
         int s = s0;
         for (; s + U <= s1; s += U) {
-            typename M::f fa[NACC][U], fb[NCG][U];
+            raw_t fa[U];
+            typename M::f fa2[NACC == 2 ? U : 1], fb[NCG][U];
+            uint32_t fz[NZ];
+            if constexpr (WM == 2) {  // units (s >> 2) + i; one past the run's last re-reads the last (never selected)
+                const int ub = s >> 2, ul = (s + U - 1) >> 2;
+#pragma unroll
+                for (int i = 0; i < NZ; ++i) fz[i] = szp[(size_t)(ub + i < ul ? ub + i : ul) * 16];
+            }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                fa[0][u] = M::load_w(wp + (size_t)(s + u) * 512, lane);
-                if constexpr (NACC == 2) fa[1][u] = M::load_w(wp2 + (size_t)(s + u) * 512, lane);
+                fa[u] = load_raw(s + u);
+                if constexpr (NACC == 2) fa2[u] = M::load_w(wp2 + (size_t)(s + u) * 512, lane);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
                 for (int c = 0; c < NCG; ++c) fb[c][u] = M::load(xp[c] + (size_t)(s + u) * 32);
 #pragma unroll
-            for (int u = 0; u < U; ++u)
+            for (int u = 0; u < U; ++u) {
+                uint32_t z = 0;
+                if constexpr (WM == 2) {  // step s + u is in unit (s >> 2) + ((s & 3) + u >> 2)
+                    const int zi = ((s & 3) + u) >> 2;
+                    z = fz[0];
 #pragma unroll
-                for (int c = 0; c < NCG; ++c)
+                    for (int i = 1; i < NZ; ++i) z = zi >= i ? fz[i] : z;
+                }
+                const typename M::f w = expand(fa[u], z);
 #pragma unroll
-                    for (int q = 0; q < NACC; ++q) acc[q][c] = M::mma(fa[q][u], fb[c][u], acc[q][c]);
+                for (int c = 0; c < NCG; ++c) {
+                    acc[0][c] = M::mma(w, fb[c][u], acc[0][c]);
+                    if constexpr (NACC == 2) acc[1][c] = M::mma(fa2[u], fb[c][u], acc[1][c]);
+                }
+            }
         }
         for (; s < s1; ++s) {
-            typename M::f fa0 = M::load_w(wp + (size_t)s * 512, lane);
+            uint32_t z = 0;
+            if constexpr (WM == 2) z = szp[(size_t)(s >> 2) * 16];
+            const raw_t fr = load_raw(s);
             typename M::f fa1;
             if constexpr (NACC == 2) fa1 = M::load_w(wp2 + (size_t)s * 512, lane);
+            const typename M::f fa0 = expand(fr, z);
 #pragma unroll
             for (int c = 0; c < NCG; ++c) {
                 typename M::f fb = M::load(xp[c] + (size_t)s * 32);
@@ -941,21 +991,43 @@ int linear_ksb(int N, int K, int R, int nacc, bool can_split) {
     return ksb;
 }
 
-template <typename T, int EPI>
+template <typename T, int EPI, int WM = 0>
 static void linear_dispatch(hipStream_t s, const LinearArgs<T>& a) {
     const int tiles = FM_CEIL(a.N, 16);
     dim3 grid(tiles, linear_ksb(a.N, a.K, a.R, EPI == EPI_SWIGLU ? 2 : 1, a.part != nullptr && a.tickets != nullptr));
     if (a.R <= 16)
-        linear_kernel<T, 1, EPI, 8><<<grid, 512, 0, s>>>(a);
+        linear_kernel<T, 1, EPI, 8, WM><<<grid, 512, 0, s>>>(a);
     else if (a.R <= 32) {
         if (fm_tuning().linear_u32 == 8)
-            linear_kernel<T, 2, EPI, 8><<<grid, 512, 0, s>>>(a);
+            linear_kernel<T, 2, EPI, 8, WM><<<grid, 512, 0, s>>>(a);
         else
-            linear_kernel<T, 2, EPI, 4><<<grid, 512, 0, s>>>(a);
+            linear_kernel<T, 2, EPI, 4, WM><<<grid, 512, 0, s>>>(a);
     } else
-        linear_kernel<T, 4, EPI, 4><<<grid, 512, 0, s>>>(a);
+        linear_kernel<T, 4, EPI, 4, WM><<<grid, 512, 0, s>>>(a);
+}
+// the code-reading forms (LinearArgs::Wq8s / Wq4s): bf16, one weight matrix, no packed T weight beside the codes
+template <typename T, int WM> static void linear_dispatch_q(hipStream_t s, const LinearArgs<T>& a, int epi) {
+    if constexpr (sizeof(T) == 2) {
+        FMCHECK(!a.W && !a.W2 && a.K % 32 == 0, "linear: a code-reading form takes the codes alone");
+        FMCHECK(WM == 1 ? (a.Wq8s && !a.Wq4s) : (a.Wq4s && a.wsz && !a.Wq8s && a.K % 128 == 0),
+                "linear: the code pointer of the selected form is not set");
+        switch (epi) {
+            case EPI_STORE: linear_dispatch<T, EPI_STORE, WM>(s, a); break;
+            case EPI_RESID: linear_dispatch<T, EPI_RESID, WM>(s, a); break;
+            case EPI_F32: linear_dispatch<T, EPI_F32, WM>(s, a); break;
+            default: FMCHECK(false, "linear: no code-reading form of this epilogue");
+        }
+    } else {
+        FMCHECK(false, "linear: the code-reading forms are bf16 only");
+    }
 }
 template <typename T> void launch_linear(hipStream_t s, const LinearArgs<T>& a, int epi) {
+    if (a.Wq8s || a.Wq4s) {
+        if (a.Wq4s) linear_dispatch_q<T, 2>(s, a, epi);
+        else linear_dispatch_q<T, 1>(s, a, epi);
+        return;
+    }
+    FMCHECK(a.W, "linear: no weight");
     switch (epi) {
         case EPI_STORE: linear_dispatch<T, EPI_STORE>(s, a); break;
         case EPI_RESID: linear_dispatch<T, EPI_RESID>(s, a); break;

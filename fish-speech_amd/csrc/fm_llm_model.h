@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <deque>
+
 #include "fm_kernels.h"
 #include "fm_runtime.h"
 
@@ -123,8 +125,27 @@ struct fm_llm {
         // int4 (sz set), bf16, max_slots > 8: the step-granular code copy the batched linears stream with
         // sz (launch_pack_q4s; its own allocation too)
         const uint32_t* q4s = nullptr;
+        // fm_llm_set_quant_compact: the linear has no bf16 fragment copy -- its key is no device address
+        // (compact_key) and every launcher reads the codes above
+        bool compact = false;
     };
     std::map<const void*, QInfo> qmap;
+    // compact weight-only handles (fm_llm_set_quant_compact): finalize keeps the codes of every quantised
+    // linear and frees (int8 checkpoints: never makes) its bf16 copy.  A compact linear's key -- what LayerW,
+    // head_c, fout and fproj_w hold and qinfo() / rowmajor / rowsz / rowscale are looked up by -- is the
+    // address of one byte of ckeys: a host address no kernel may be handed (wdev() is null for it).
+    bool compact = false;
+    std::deque<char> ckeys;
+    const void* compact_key() {
+        ckeys.push_back(0);
+        return &ckeys.back();
+    }
+    // fm_llm_memory_info: steady-state device bytes, booked where they are allocated
+    // (finalize; ensure_qkv0's table): [0] fragment copies of quantised linears, [1] decode-GEMV code units
+    // and their scale tables, [2] step-granular codes, [3] row-major copies and their tables, [4] every
+    // other weight, [5] KV caches, [6] activations and scratch
+    int64_t mem[7] = {0, 0, 0, 0, 0, 0, 0};
+    int mem_cat = 6;  // the class dalloc books under
     std::map<const void*, void*> rowmajor;  // packed wo / w2 / wqkv -> row-major bf16 copy (int8 / int4: codes)
     std::map<const void*, const void*> rowsz;  // int4: packed -> its row-major (scale, zero) table
     std::map<const void*, const void*> rowscale;  // int8 w1 || w3: packed -> its row-block interleaved scales
@@ -154,12 +175,17 @@ struct fm_llm {
         auto it = qmap.find(W);
         return it == qmap.end() ? nullptr : &it->second;
     }
+    // the packed T weight a kernel may read: null for a compact linear (its key is a host address)
+    const void* wdev(const void* W) const {
+        const QInfo* q = qinfo(W);
+        return q && q->compact ? nullptr : W;
+    }
 
     ~fm_llm() {
         if (device >= 0) (void)hipSetDevice(device);
         for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
         for (auto& kv : w) {
-            if (kv.second.p) (void)hipFree(kv.second.p);
+            if (kv.second.p && wdev(kv.second.p)) (void)hipFree(kv.second.p);  // (not a compact linear's key)
             if (kv.second.q) (void)hipFree(kv.second.q);
         }
         for (void* p : allocs) (void)hipFree(p);
@@ -177,6 +203,7 @@ struct fm_llm {
             throw FmError{FM_ERR_OOM, "hipMalloc(" + std::to_string(bytes) + ") failed: " + hipGetErrorString(e)};
         if (zero) HIPCHK(hipMemsetAsync(p, 0, bytes, stream));
         allocs.push_back(p);
+        mem[mem_cat] += (int64_t)bytes;
         return p;
     }
 };

@@ -102,18 +102,22 @@ static void* pack_q8_dev(fm_llm* m, const void* q, int rows, int cols) {
     launch_pack_q8(m->stream, (const int8_t*)q, rows, cols, (int8_t*)dst);
     HIPCHK(hipGetLastError());
     m->allocs.push_back(dst);
+    m->mem[1] += (int64_t)(rows + 15) / 16 * 16 * cols;
     return dst;
 }
 
 // the batched linears' step-granular copy of the same codes: only where bsacc_kernel can take it (int8,
-// bf16, a handle with more than GEMV_MAX_ROWS slots); a max_slots <= 8 handle allocates nothing here
+// bf16, a handle with more than GEMV_MAX_ROWS slots); a max_slots <= 8 handle allocates nothing here -- unless it is
+// compact: there the copy is what linear_kernel's code form reads, whatever max_slots is
 static const unsigned char* pack_q8s_dev(fm_llm* m, const void* q, int rows, int cols) {
-    if (m->quant != FM_QUANT_INT8 || m->prec != FM_PREC_BF16 || m->max_slots <= GEMV_MAX_ROWS || cols % 32) return nullptr;
+    if (m->quant != FM_QUANT_INT8 || m->prec != FM_PREC_BF16 || (m->max_slots <= GEMV_MAX_ROWS && !m->compact) || cols % 32)
+        return nullptr;
     void* dst = nullptr;
     HIPCHK(hipMalloc(&dst, (size_t)(rows + 15) / 16 * 16 * cols));
     launch_pack_q8s(m->stream, (const int8_t*)q, rows, cols, (int8_t*)dst);
     HIPCHK(hipGetLastError());
     m->allocs.push_back(dst);
+    m->mem[2] += (int64_t)(rows + 15) / 16 * 16 * cols;
     return (const unsigned char*)dst;
 }
 
@@ -132,15 +136,18 @@ static fm_llm::QInfo pack_q4_dev(fm_llm* m, const void* q, const void* sz, int r
     HIPCHK(hipGetLastError());
     m->allocs.push_back(dq);
     m->allocs.push_back(ds);
+    m->mem[1] += (int64_t)(tiles * 16 * cols / 2 + tiles * (cols / 128) * 16 * 4);
     // the batched linears' step-granular copy of the same codes (they stream it with ds): only where
     // bsacc_kernel can take it -- bf16, a handle with more than GEMV_MAX_ROWS slots; a max_slots <= 8
-    // handle allocates nothing here.  Its own allocation: row_copies 0 frees none of it.
+    // handle allocates nothing here (a compact one does: linear_kernel's code form reads it).  Its own allocation:
+    // row_copies 0 frees none of it.
     void* d4 = nullptr;
-    if (m->prec == FM_PREC_BF16 && m->max_slots > GEMV_MAX_ROWS) {
+    if (m->prec == FM_PREC_BF16 && (m->max_slots > GEMV_MAX_ROWS || m->compact)) {
         HIPCHK(hipMalloc(&d4, tiles * 16 * cols / 2));
         launch_pack_q4s(m->stream, (const uint8_t*)q, rows, cols, (uint32_t*)d4);
         HIPCHK(hipGetLastError());
         m->allocs.push_back(d4);
+        m->mem[2] += (int64_t)(tiles * 16 * cols / 2);
     }
     return fm_llm::QInfo{(const unsigned char*)dq, nullptr, (const uint32_t*)ds, nullptr, (const uint32_t*)d4};
 }
@@ -149,6 +156,7 @@ static fm_llm::QInfo pack_q4_dev(fm_llm* m, const void* q, const void* sz, int r
 // T-fragment kernels read), t.q = int8 row-major, t.s = row scales.  int8 checkpoints supply q and
 // "<name>.scales"; float weights are quantized here with quantize.py's per-channel rule.
 static void quantize_linears(fm_llm* m) {
+    m->mem_cat = 1;  // (the int8 row scales allocated below belong to the decode-GEMV units)
     if (m->quant == FM_QUANT_INT4) {  // every linear: codes, group (scale, zero), dequantised bf16 in place
         for (auto& kv : m->w) {
             if (!is_quant_linear(kv.first)) continue;
@@ -164,6 +172,7 @@ static void quantize_linears(fm_llm* m) {
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipStreamSynchronize(m->stream));
+        m->mem_cat = 6;
         return;
     }
     for (auto& kv : m->w) {
@@ -174,11 +183,13 @@ static void quantize_linears(fm_llm* m) {
         if (t.q) {
             FMCHECK(sc.set, "int8 weight without scales: " + kv.first);
             FMCHECK(!t.p, "tensor set twice: " + kv.first);
-            HIPCHK(hipMalloc(&t.p, rp * t.cols * m->esz));
-            if (m->prec == FM_PREC_BF16)
-                launch_i8_to<bf16_t>(m->stream, (const int8_t*)t.q, (int64_t)rp * t.cols, (bf16_t*)t.p);
-            else
-                launch_i8_to<float>(m->stream, (const int8_t*)t.q, (int64_t)rp * t.cols, (float*)t.p);
+            if (!m->compact) {  // (a compact handle serves the linear from its codes: no T expansion at all)
+                HIPCHK(hipMalloc(&t.p, rp * t.cols * m->esz));
+                if (m->prec == FM_PREC_BF16)
+                    launch_i8_to<bf16_t>(m->stream, (const int8_t*)t.q, (int64_t)rp * t.cols, (bf16_t*)t.p);
+                else
+                    launch_i8_to<float>(m->stream, (const int8_t*)t.q, (int64_t)rp * t.cols, (float*)t.p);
+            }
             t.s = sc.p;
         } else {
             FMCHECK(!sc.set, "scales given with a float weight: " + kv.first);
@@ -193,13 +204,16 @@ static void quantize_linears(fm_llm* m) {
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(m->stream));
+    m->mem_cat = 6;
 }
 
 // row-major [rows][cols] device tensor -> packed fragment layout (fm_kernels.h)
-static void* pack_dev(fm_llm* m, const void* src, int rows, int cols) {
+// (booked as the fragment copy of a quantised linear, qlin, or as any other weight)
+static void* pack_dev(fm_llm* m, const void* src, int rows, int cols, bool qlin) {
     const size_t n = (size_t)(rows + 15) / 16 * 16 * cols;
     void* dst = nullptr;
     HIPCHK(hipMalloc(&dst, n * m->esz));
+    m->mem[qlin ? 0 : 4] += (int64_t)(n * m->esz);
     if (m->prec == FM_PREC_BF16)
         launch_pack<bf16_t>(m->stream, (const bf16_t*)src, rows, cols, (bf16_t*)dst);
     else
@@ -247,11 +261,17 @@ static void* pack_w13(fm_llm* m, const std::string& p, int inter, int dim) {
     DTensor& t3 = m->w.at(p + "feed_forward.w3.weight");
     const size_t E = m->esz, rb = (size_t)dim * E;
     void* tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, 2 * (size_t)inter * rb));
-    HIPCHK(hipMemcpy2DAsync(tmp, 16 * rb, t1.p, 8 * rb, 8 * rb, inter / 8, hipMemcpyDeviceToDevice, m->stream));
-    HIPCHK(hipMemcpy2DAsync((char*)tmp + 8 * rb, 16 * rb, t3.p, 8 * rb, 8 * rb, inter / 8, hipMemcpyDeviceToDevice,
-                            m->stream));
-    void* pk = pack_dev(m, tmp, 2 * inter, dim);
+    void* pk = nullptr;
+    if (m->compact) {  // no T tiles: the key of the codes packed below
+        pk = const_cast<void*>(m->compact_key());
+    } else {
+        HIPCHK(hipMalloc(&tmp, 2 * (size_t)inter * rb));
+        HIPCHK(hipMemcpy2DAsync(tmp, 16 * rb, t1.p, 8 * rb, 8 * rb, inter / 8, hipMemcpyDeviceToDevice, m->stream));
+        HIPCHK(hipMemcpy2DAsync((char*)tmp + 8 * rb, 16 * rb, t3.p, 8 * rb, 8 * rb, inter / 8, hipMemcpyDeviceToDevice,
+                                m->stream));
+        pk = pack_dev(m, tmp, 2 * inter, dim, m->quant != FM_QUANT_NONE);
+    }
+    m->mem_cat = 3;  // the row-block GEMV's copies and their tables
     // the row-block GEMV's copy (fm_rowgemv.hip ROWGEMV_NORM_SWIGLU): row-major, rows 4b .. 4b+3 of W1
     // then the same rows of W3, per 8-row block (bf16 rows, or int8 codes + scales, or int4 packed
     // code words + (scale, zero) rows)
@@ -298,7 +318,9 @@ static void* pack_w13(fm_llm* m, const std::string& p, int inter, int dim) {
         HIPCHK(hipMemcpy2DAsync(st, 16 * gb, t1.s, 8 * gb, 8 * gb, inter / 8, hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipMemcpy2DAsync((char*)st + 8 * gb, 16 * gb, t3.s, 8 * gb, 8 * gb, inter / 8, hipMemcpyDeviceToDevice,
                                 m->stream));
-        const fm_llm::QInfo qi = pack_q4_dev(m, qt, st, 2 * inter, dim);
+        fm_llm::QInfo qi = pack_q4_dev(m, qt, st, 2 * inter, dim);
+        qi.compact = m->compact;
+        FMCHECK(qi.q8 || !m->compact, "compact: no int4 code layout for " + p + "feed_forward.w1.weight");
         if (qi.q8) m->qmap[pk] = qi;
         HIPCHK(hipStreamSynchronize(m->stream));
         for (void* p : {qt, st, t1.q, t3.q, t1.s, t3.s}) HIPCHK(hipFree(p));
@@ -311,12 +333,14 @@ static void* pack_w13(fm_llm* m, const std::string& p, int inter, int dim) {
                                 hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipMemcpy2DAsync((char*)qt + 8 * (size_t)dim, 16 * (size_t)dim, t3.q, 8 * (size_t)dim,
                                 8 * (size_t)dim, inter / 8, hipMemcpyDeviceToDevice, m->stream));
+        m->mem_cat = 1;
         void* s13 = m->dalloc(2 * (size_t)inter * E);
+        m->mem_cat = 3;
         HIPCHK(hipMemcpy2DAsync(s13, 16 * E, t1.s, 8 * E, 8 * E, inter / 8, hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipMemcpy2DAsync((char*)s13 + 8 * E, 16 * E, t3.s, 8 * E, 8 * E, inter / 8, hipMemcpyDeviceToDevice,
                                 m->stream));
         m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, qt, 2 * inter, dim), s13, nullptr,
-                                    pack_q8s_dev(m, qt, 2 * inter, dim)};
+                                    pack_q8s_dev(m, qt, 2 * inter, dim), nullptr, m->compact};
         HIPCHK(hipStreamSynchronize(m->stream));
         HIPCHK(hipFree(qt));
         HIPCHK(hipFree(t1.q));
@@ -324,9 +348,10 @@ static void* pack_w13(fm_llm* m, const std::string& p, int inter, int dim) {
         t1.q = t3.q = nullptr;
     }
     HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipFree(tmp));
-    HIPCHK(hipFree(t1.p));
-    HIPCHK(hipFree(t3.p));
+    m->mem_cat = 6;
+    if (tmp) HIPCHK(hipFree(tmp));
+    if (t1.p) HIPCHK(hipFree(t1.p));  // (null: a compact handle's int8 checkpoint tensor was never expanded)
+    if (t3.p) HIPCHK(hipFree(t3.p));
     t1.p = pk;
     t3.p = nullptr;
     return pk;
@@ -338,22 +363,44 @@ void finalize(fm_llm* m) {
     bsacc_init();
     sample_init();
     for (auto& kv : m->w) FMCHECK(kv.second.set || kv.second.optional, "tensor not set: " + kv.first);
+    if (m->compact) {
+        // before anything is freed or packed: every quantised linear must have a code layout all its kernels read
+        // (int8: whole 64-k units; int4: pack_q4_dev's condition -- group size and K whole 128-k units, K whole groups)
+        FMCHECK(m->quant && m->prec == FM_PREC_BF16, "compact: a weight-only bf16 handle only");
+        for (auto& kv : m->w) {
+            if (!is_quant_linear(kv.first)) continue;
+            const int64_t K = kv.second.cols;
+            if (m->quant == FM_QUANT_INT4)
+                FMCHECK(m->q4_gs % 128 == 0 && K % 128 == 0 && K % m->q4_gs == 0,
+                        "compact int4 needs a group size and in_features that are multiples of 128: " + kv.first +
+                            " (group size " + std::to_string(m->q4_gs) + ", in_features " + std::to_string(K) + ")");
+            else
+                FMCHECK(K % 64 == 0, "compact int8 needs in_features % 64 == 0: " + kv.first);
+        }
+    }
     if (m->quant) quantize_linears(m);
     for (auto& kv : m->w) {
         if (!is_linear_weight(kv.first) || is_ffn_w13(kv.first)) continue;  // W1/W3: pack_w13 below
         DTensor& t = kv.second;
-        void* pk = pack_dev(m, t.p, (int)t.rows, (int)t.cols);
+        // (a compact handle packs no T tiles: the linear's key stands where the packed pointer would)
+        void* pk = m->compact ? const_cast<void*>(m->compact_key())
+                              : pack_dev(m, t.p, (int)t.rows, (int)t.cols, m->quant != FM_QUANT_NONE);
         if (m->quant == FM_QUANT_INT4) {
-            const fm_llm::QInfo qi = pack_q4_dev(m, t.q, t.s, (int)t.rows, (int)t.cols);
+            fm_llm::QInfo qi = pack_q4_dev(m, t.q, t.s, (int)t.rows, (int)t.cols);
+            qi.compact = m->compact;
+            FMCHECK(qi.q8 || !m->compact, "compact: no int4 code layout for " + kv.first);
             if (qi.q8) m->qmap[pk] = qi;
             const bool keep = row_keep(m, kv.first, (int)t.rows, (int)t.cols);
             if (keep) {  // the codes as packed row-major words + the row-major (scale, zero) table
+                m->mem_cat = 3;
                 void* rw = m->dalloc((size_t)t.rows * t.cols / 2, false);
+                m->mem_cat = 6;
                 launch_pack_q4_rows(m->stream, (const uint8_t*)t.q, (int)t.rows, (int)t.cols, (uint32_t*)rw);
                 HIPCHK(hipGetLastError());
                 m->rowmajor[pk] = rw;
                 m->rowsz[pk] = t.s;
                 m->allocs.push_back(const_cast<void*>(t.s));
+                m->mem[3] += (int64_t)((t.rows + 15) / 16 * 16 * (t.cols / m->q4_gs) * 4);
             }
             HIPCHK(hipStreamSynchronize(m->stream));
             HIPCHK(hipFree(t.q));
@@ -362,11 +409,12 @@ void finalize(fm_llm* m) {
             t.s = nullptr;
         } else if (m->quant) {
             m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, t.q, (int)t.rows, (int)t.cols), t.s, nullptr,
-                                        pack_q8s_dev(m, t.q, (int)t.rows, (int)t.cols)};
+                                        pack_q8s_dev(m, t.q, (int)t.rows, (int)t.cols), nullptr, m->compact};
             HIPCHK(hipStreamSynchronize(m->stream));
             if (row_keep(m, kv.first, (int)t.rows, (int)t.cols)) {
                 m->rowmajor[pk] = t.q;  // the int8 codes, row-major, for the row-block GEMV
                 m->allocs.push_back(t.q);
+                m->mem[3] += (int64_t)((t.rows + 15) / 16 * 16 * t.cols);
             } else {
                 HIPCHK(hipFree(t.q));
             }
@@ -376,7 +424,8 @@ void finalize(fm_llm* m) {
         if (!m->quant && row_keep(m, kv.first, (int)t.rows, (int)t.cols)) {
             m->rowmajor[pk] = t.p;  // kept for the batch-1 row-pair GEMV
             m->allocs.push_back(t.p);
-        } else {
+            m->mem[3] += (int64_t)((t.rows + 15) / 16 * 16 * t.cols * m->esz);
+        } else if (t.p) {  // (null: a compact handle's int8 checkpoint tensor was never expanded)
             HIPCHK(hipFree(t.p));
         }
         t.p = pk;
@@ -447,14 +496,21 @@ void finalize(fm_llm* m) {
     m->Nhead = m->nsem + 1;
     FMCHECK(m->Nhead <= 8192, "constrained head wider than 8192 rows is not supported");
     const size_t rowb = (size_t)c.dim * m->esz;
-    void* head_rm = m->dalloc((size_t)(m->Nhead + 15) / 16 * 16 * rowb);
-    HIPCHK(hipMemcpyAsync(head_rm, (const char*)outw + (size_t)c.semantic_begin_id * rowb,
-                          (size_t)m->nsem * rowb, hipMemcpyDeviceToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync((char*)head_rm + (size_t)m->nsem * rowb,
-                          (const char*)outw + (size_t)c.im_end_id * rowb, rowb, hipMemcpyDeviceToDevice,
-                          m->stream));
-    m->head_c = pack_dev(m, head_rm, m->Nhead, c.dim);
-    m->allocs.push_back(m->head_c);
+    const bool head_q = m->quant && !c.tie_word_embeddings;  // output.weight is a quantised linear; a tied head is not
+    if (m->compact && head_q) {
+        m->head_c = const_cast<void*>(m->compact_key());  // served from the compact rows of the codes packed below
+    } else {
+        m->mem_cat = 4;
+        void* head_rm = m->dalloc((size_t)(m->Nhead + 15) / 16 * 16 * rowb);
+        m->mem_cat = 6;
+        HIPCHK(hipMemcpyAsync(head_rm, (const char*)outw + (size_t)c.semantic_begin_id * rowb,
+                              (size_t)m->nsem * rowb, hipMemcpyDeviceToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync((char*)head_rm + (size_t)m->nsem * rowb,
+                              (const char*)outw + (size_t)c.im_end_id * rowb, rowb, hipMemcpyDeviceToDevice,
+                              m->stream));
+        m->head_c = pack_dev(m, head_rm, m->Nhead, c.dim, head_q);
+        m->allocs.push_back(m->head_c);
+    }
     if (m->quant == FM_QUANT_INT4 && !c.tie_word_embeddings) {  // the compact rows of the codes and groups
         DTensor& o = m->w.at("output.weight");
         const size_t gb = (size_t)(c.dim / m->q4_gs) * 4;
@@ -470,13 +526,16 @@ void finalize(fm_llm* m) {
                               hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipMemcpyAsync((char*)hs + (size_t)m->nsem * gb, (const char*)o.s + (size_t)c.im_end_id * gb, gb,
                               hipMemcpyDeviceToDevice, m->stream));
-        const fm_llm::QInfo qi = pack_q4_dev(m, hq, hs, m->Nhead, c.dim);
+        fm_llm::QInfo qi = pack_q4_dev(m, hq, hs, m->Nhead, c.dim);
+        qi.compact = m->compact;
+        FMCHECK(qi.q8 || !m->compact, "compact: no int4 code layout for output.weight");
         if (qi.q8) m->qmap[m->head_c] = qi;
         HIPCHK(hipStreamSynchronize(m->stream));
         for (void* p : {hq, hs, o.q, o.s}) HIPCHK(hipFree(p));
         o.q = o.s = nullptr;
     } else if (m->quant && !c.tie_word_embeddings) {  // the same compact rows of the int8 head and its scales
         DTensor& o = m->w.at("output.weight");
+        m->mem_cat = 1;
         void* hq = m->dalloc((size_t)(m->Nhead + 15) / 16 * 16 * c.dim);
         HIPCHK(hipMemcpyAsync(hq, (const char*)o.q + (size_t)c.semantic_begin_id * c.dim, (size_t)m->nsem * c.dim,
                               hipMemcpyDeviceToDevice, m->stream));
@@ -487,16 +546,32 @@ void finalize(fm_llm* m) {
                               hipMemcpyDeviceToDevice, m->stream));
         HIPCHK(hipMemcpyAsync((char*)hs + (size_t)m->nsem * m->esz, (const char*)o.s + (size_t)c.im_end_id * m->esz,
                               m->esz, hipMemcpyDeviceToDevice, m->stream));
+        m->mem_cat = 6;
         m->qmap[m->head_c] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, hq, m->Nhead, c.dim), hs, nullptr,
-                                           pack_q8s_dev(m, hq, m->Nhead, c.dim)};
+                                           pack_q8s_dev(m, hq, m->Nhead, c.dim), nullptr, m->compact};
         HIPCHK(hipStreamSynchronize(m->stream));
         HIPCHK(hipFree(o.q));
         o.q = nullptr;
+    }
+    if (m->compact && head_q) {  // the whole table's T copy served only the head rows above
+        DTensor& o = m->w.at("output.weight");
+        if (o.p) HIPCHK(hipFree(o.p));
+        o.p = nullptr;
+    }
+    // every tensor still held as uploaded: embeddings, norms, biases, an untied head's table (int8: the row scales)
+    for (auto& kv : m->w) {
+        const DTensor& t = kv.second;
+        if (!t.p || is_linear_weight(kv.first)) continue;
+        const int64_t rows = t.rows > 1 ? (t.rows + 15) / 16 * 16 : 1;
+        const std::string& n = kv.first;
+        const bool scales = n.size() > 7 && n.compare(n.size() - 7, 7, ".scales") == 0;
+        m->mem[scales ? 1 : 4] += rows * t.cols * (int64_t)m->esz;
     }
     // caches [slot][layer][kv][S][hd]
     const StackDims& d = m->sd;
     m->layer_stride = (size_t)d.nkv * m->S * d.hd;
     m->slot_stride = m->layer_stride * d.n_layer;
+    m->mem_cat = 5;
     m->kc = m->dalloc(m->slot_stride * m->max_slots * m->esz);
     m->vc = m->dalloc(m->slot_stride * m->max_slots * m->esz);
     const StackDims& f = m->fdm;
@@ -504,6 +579,7 @@ void finalize(fm_llm* m) {
     m->fslot_stride = m->flayer_stride * f.n_layer;
     m->fkc = m->dalloc(m->fslot_stride * m->max_slots * m->esz);
     m->fvc = m->dalloc(m->fslot_stride * m->max_slots * m->esz);
+    m->mem_cat = 6;
     auto rt = rope_table_host(m->S, d.hd, c.rope_base);
     m->rope = (float*)m->dalloc(rt.size() * 4, false);
     HIPCHK(hipMemcpy(m->rope, rt.data(), rt.size() * 4, hipMemcpyHostToDevice));

@@ -1083,6 +1083,114 @@ int fm_op_batched_linear_q4(int device, const float* w, int N, int K, int gs, co
     });
 }
 
+// weight-only int8 / int4 on launch_linear (the 16-row MFMA tile kernel, any R): the model's own device quantizer,
+// then the same launch on the packed bf16 fragments of the quantised weights (y_bf16) and on linear_kernel's
+// code-reading form -- the step-granular codes alone, no bf16 weight (y_q).  Outputs in/out like fm_op_linear's.
+int fm_op_linear_q(int device, int quant, int gs, const float* w, int N, int K, const float* bias, const float* x,
+                   int ldx, const float* res, int ldr, int R, int epi, int split, float* y_q, float* y_bf16, int ldy,
+                   int y_rows, int reps, int* ksb, int* dirty, int8_t* q_out, float* scale_out, float* zero_out) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y_q && y_bf16 && ksb && dirty, "null argument");
+        FMCHECK(quant == FM_QUANT_INT8 || quant == FM_QUANT_INT4, "quant must be int8 or int4");
+        FMCHECK(epi == EPI_STORE || epi == EPI_RESID || epi == EPI_F32, "epi must be 0 (store), 1 (residual) or 3 (fp32)");
+        FMCHECK((epi == EPI_RESID) == (res != nullptr), "res goes with EPI_RESID (1) only");
+        FMCHECK(R >= 1 && R <= 1024 && N >= 1 && K >= 32 && K % 32 == 0, "need 1 <= R <= 1024, N >= 1, K a multiple of 32");
+        FMCHECK(ldx >= K && ldx % 8 == 0 && ldy >= N && y_rows >= R && (!res || ldr >= N), "bad row strides / output rows");
+        FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
+        const bool q4 = quant == FM_QUANT_INT4;
+        FMCHECK(!q4 || (gs >= 128 && gs % 128 == 0 && K % 128 == 0 && K % gs == 0),
+                "the int4 code form needs a group size and K in whole 128-k units, K a multiple of the group size");
+        FMCHECK(!q4 || !bias, "the int4 linears are bias-free");
+        StreamGuard g(device);
+        DevBufs b(g.s);
+        const int Np = (N + 15) / 16 * 16, ng = q4 ? K / gs : 1;
+        bf16_t* dw = (bf16_t*)b.alloc((size_t)Np * K * 2);
+        {
+            bf16_t* t = b.upload<bf16_t>(w, (size_t)N * K);
+            HIPCHK(hipMemcpyAsync(dw, t, (size_t)N * K * 2, hipMemcpyDeviceToDevice, g.s));
+        }
+        uint8_t* dq = (uint8_t*)b.alloc((size_t)Np * K);
+        LinearArgs<bf16_t> a{};
+        void* pq = nullptr;       // the step-granular codes
+        uint32_t* sz4 = nullptr;  // int4: their (scale, zero) table
+        if (q4) {
+            uint32_t* dsz = (uint32_t*)b.alloc((size_t)Np * ng * 4);
+            launch_quant4(g.s, dw, N, K, gs, dq, dsz);  // dw <- bf16(fma(q - 8, scale, zero))
+            pq = b.alloc((size_t)Np * K / 2);
+            launch_pack_q4s(g.s, dq, N, K, (uint32_t*)pq);
+            sz4 = (uint32_t*)b.alloc((size_t)(Np / 16) * (K / 128) * 16 * 4);
+            launch_pack_sz4(g.s, dsz, N, K, gs, sz4);
+            HIPCHK(hipGetLastError());
+            if (scale_out || zero_out) {
+                std::vector<uint32_t> hs((size_t)N * ng);
+                HIPCHK(hipMemcpyAsync(hs.data(), dsz, hs.size() * 4, hipMemcpyDeviceToHost, g.s));
+                HIPCHK(hipStreamSynchronize(g.s));
+                for (size_t i = 0; i < hs.size(); ++i) {
+                    const uint32_t us = hs[i] << 16, uz = hs[i] & 0xffff0000u;
+                    if (scale_out) memcpy(&scale_out[i], &us, 4);
+                    if (zero_out) memcpy(&zero_out[i], &uz, 4);
+                }
+            }
+        } else {
+            bf16_t* ds = (bf16_t*)b.alloc((size_t)Np * 2);
+            launch_quant_rows<bf16_t>(g.s, dw, N, K, (int8_t*)dq, ds);  // dw <- bf16(q)
+            pq = b.alloc((size_t)Np * K);
+            launch_pack_q8s(g.s, (const int8_t*)dq, N, K, (int8_t*)pq);
+            HIPCHK(hipGetLastError());
+            a.wscale = ds;
+            if (scale_out) download<bf16_t>(ds, (size_t)N, scale_out, g.s);
+        }
+        if (q_out) HIPCHK(hipMemcpyAsync(q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, g.s));
+        bf16_t* pk = (bf16_t*)b.alloc((size_t)Np * K * 2);
+        launch_pack<bf16_t>(g.s, dw, N, K, pk);
+        HIPCHK(hipGetLastError());
+        if (bias) a.bias = b.upload<bf16_t>(bias, (size_t)N);
+        a.X = b.upload<bf16_t>(x, (size_t)R * ldx);
+        a.ldx = ldx;
+        a.R = R;
+        a.N = N;
+        a.K = K;
+        a.ldy = ldy;
+        if (epi == EPI_RESID) {
+            a.res = b.upload<bf16_t>(res, (size_t)R * ldr);
+            a.ldr = ldr;
+        }
+        const bool f32 = epi == EPI_F32;
+        const int tiles = Np / 16;
+        const bool can_split = split && R > 8 && R <= 64;  // as the batched decode frame offers it
+        const int nk = linear_ksb(N, K, R, 1, can_split);
+        int* tickets = (int*)b.alloc((size_t)tiles * 4);
+        if (can_split) {
+            a.part = (float*)b.alloc((size_t)nk * R * N * 4);
+            a.tickets = tickets;
+        }
+        int left = 0;
+        for (int form = 0; form < 2; ++form) {
+            float* y = form ? y_q : y_bf16;
+            InOut<bf16_t> yt(b, y, f32 ? 1 : (size_t)y_rows * ldy);
+            InOut<float> yf(b, y, f32 ? (size_t)y_rows * ldy : 1);
+            LinearArgs<bf16_t> l = a;
+            l.Y = f32 ? nullptr : yt.d;
+            l.Yf = f32 ? yf.d : nullptr;
+            if (!form) {
+                l.W = pk;
+            } else if (q4) {
+                l.Wq4s = (const uint32_t*)pq;
+                l.wsz = sz4;
+            } else {
+                l.Wq8s = (const unsigned char*)pq;
+            }
+            for (int i = 0; i < reps; ++i) launch_linear<bf16_t>(g.s, l, epi);
+            HIPCHK(hipGetLastError());
+            if (f32) yf.get(g.s);
+            else yt.get(g.s);
+            left += count_nonzero(tickets, (size_t)tiles, g.s);
+        }
+        *ksb = nk;
+        *dirty = left;
+    });
+}
+
 // ---- the decode linears, one production launcher each (include/fishmi.h) -------------------------
 int fm_op_linear(int device, int precision, int epi, const float* w, const float* w2, const float* bias,
                  const float* x, int ldx, const float* res, int ldr, int R, int N, int K, int split, float* y, int ldy,

@@ -17,6 +17,9 @@ template <typename... V> constexpr int fm_knob_set(V... v) { return (0 | ... | (
 #define FM_ZERO_OR_MULT16 FM_RULE_MULT16, 1, 0          /* 0, or a multiple of 16 */
 #endif
 
+// A compact handle (fm_llm_set_quant_compact: no bf16 copy of its quantised linears) ignores the knobs that would
+// pick a reader of that copy -- bstream 0, bstream_acc 0, bstream_chain 1, bstream_q8 0, bstream_q4 0, int4_stream 0
+// -- and keeps its default routing; other handles in the process keep the knobs' meaning (include/fishmi.h, fm_tune).
 #ifdef FM_KNOB
 FM_KNOB(gemv_nt, 1, FM_BOOL)               // 1: non-temporal weight loads (each weight byte is read once a frame)
 FM_KNOB(gemv_u, 8, FM_SET(2, 4, 8))        // weight fragments in flight per wave (2, 4 or 8)

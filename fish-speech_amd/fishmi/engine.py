@@ -315,12 +315,13 @@ def _precision(precision) -> str:
     return "bf16"  # torch.bfloat16 / torch.half / "bf16": the bf16 path
 
 
-def load_model(checkpoint_path: str, device=0, precision="bf16", max_slots: int = 1):
-    """init_model (inference.py:362-392): the native Dual-AR model with its tokenizer attached."""
+def load_model(checkpoint_path: str, device=0, precision="bf16", max_slots: int = 1, compact: bool = False):
+    """init_model (inference.py:362-392): the native Dual-AR model with its tokenizer attached.
+    compact: a weight-only (int8) checkpoint keeps only its codes on the device (DualARModel compact=)."""
     from .llm import DualARModel
 
     model = DualARModel.from_pretrained(checkpoint_path, device=_device_index(device),
-                                       precision=_precision(precision), max_slots=max_slots)
+                                       precision=_precision(precision), max_slots=max_slots, compact=compact)
     if model.tokenizer is None:
         raise ValueError(f"{checkpoint_path} has no tokenizer.json")
     return model
@@ -328,7 +329,7 @@ def load_model(checkpoint_path: str, device=0, precision="bf16", max_slots: int 
 
 def launch_thread_safe_queue(checkpoint_path, device, precision, compile: bool = False,
                              model=None, max_slots: int = 1, tick_frames: int = 8,
-                             voice_cache_mb: int = 0) -> "queue.Queue":
+                             voice_cache_mb: int = 0, quant_compact: bool = False) -> "queue.Queue":
     """inference.py:748-799: a daemon worker owning the model; returns its input queue once the
     model is loaded.  `model` (optional) hands in an already-built DualARModel (tests).
 
@@ -336,14 +337,17 @@ def launch_thread_safe_queue(checkpoint_path, device, precision, compile: bool =
     max_slots > 1: fishmi.batching.BatchedWorker -- up to max_slots requests decode together on
     their own KV slots (batched hipGraph frames), same queue contract (BASELINE config 3).
     voice_cache_mb > 0: either worker keeps a fishmi.prefix_cache.PrefixCache of that many MiB of device
-    memory, built on the worker thread (0: off, the reference's flow)."""
+    memory, built on the worker thread (0: off, the reference's flow).
+    quant_compact: load a weight-only checkpoint with only its codes kept on the device (load_model compact=;
+    ValueError on a checkpoint that is not quantised)."""
     ready = threading.Event()
     failure: List[BaseException] = []
     holder: dict = {}
 
     def worker():
         try:
-            m = model if model is not None else load_model(checkpoint_path, device, precision, max_slots)
+            m = model if model is not None else load_model(checkpoint_path, device, precision, max_slots,
+                                                                compact=quant_compact)
         except BaseException as e:  # surface load failures to the caller instead of hanging
             failure.append(e)
             ready.set()

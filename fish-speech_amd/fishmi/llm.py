@@ -45,9 +45,13 @@ def resolve_im_end_id(path) -> Optional[int]:
 
 class DualARModel:
     def __init__(self, cfg: DualARConfig, device: int = 0, precision: str = "bf16",
-                 max_slots: int = 1, quant: Optional[str] = None, groupsize: int = 128):
+                 max_slots: int = 1, quant: Optional[str] = None, groupsize: int = 128, compact: bool = False):
+        """compact=True (weight-only handles, bf16): keep only the codes of the quantised linears -- no bf16 copy of
+        them stays on the device and every kernel reads codes (fm_llm_set_quant_compact); bit-identical outputs."""
         if cfg.im_end_id < 0:
             raise ValueError("config.im_end_id must be set (tokenizer's <|im_end|> id)")
+        if compact and quant is None:
+            raise ValueError("compact=True needs a weight-only model: quant='int8' / 'int4' (or an int8 checkpoint)")
         self.cfg = cfg
         self.device = device
         self.precision = precision
@@ -64,10 +68,13 @@ class DualARModel:
         if quant not in (None, "int8", "int4"):
             raise ValueError(f"quant must be None, 'int8' or 'int4', got {quant!r}")
         self.quant = quant
+        self.compact = bool(compact)
         if quant == "int8":  # WeightOnlyInt8QuantHandler.convert_for_runtime (llama.py:528-535)
             native.check(L.fm_llm_set_quant(h, native.FM_QUANT_INT8))
         elif quant == "int4":  # WeightOnlyInt4QuantHandler(model, groupsize) (llama.py:537-543), bf16 weights
             native.check(L.fm_llm_set_quant_int4(h, int(groupsize)))
+        if compact:
+            native.check(L.fm_llm_set_quant_compact(h, 1))
         self._finalized = False
         self.tokenizer = None  # FishTokenizer when loaded from a checkpoint with tokenizer.json
 
@@ -75,9 +82,11 @@ class DualARModel:
     @classmethod
     def from_pretrained(cls, path, device: int = 0, precision: str = "bf16", max_slots: int = 1,
                         max_length: Optional[int] = None, im_end_id: Optional[int] = None,
-                        quant: Optional[str] = None, groupsize: int = 128):
+                        quant: Optional[str] = None, groupsize: int = 128, compact: bool = False):
         """quant="int4": quantize the bf16 checkpoint's linears at load (the reference's quantize.py
-        --mode int4 --groupsize g, then its int4 runtime); int8 checkpoints are detected."""
+        --mode int4 --groupsize g, then its int4 runtime); int8 checkpoints are detected.
+        compact=True: keep only the codes (an int8 checkpoint is then never expanded to bf16); a bf16 checkpoint
+        without quant= raises ValueError."""
         cfg = DualARConfig.from_pretrained(path)
         if max_length is not None:
             cfg.max_seq_len = max_length
@@ -101,7 +110,7 @@ class DualARModel:
             if quant == "int4":
                 raise ValueError("int4 quantization needs a float checkpoint, this one is int8")
             quant = "int8"
-        m = cls(cfg, device, precision, max_slots, quant, groupsize)
+        m = cls(cfg, device, precision, max_slots, quant, groupsize, compact)
         m.load_weights(weights)
         m.finalize()
         m.tokenizer = tok
@@ -110,10 +119,10 @@ class DualARModel:
     @classmethod
     def synthetic(cls, cfg: DualARConfig, seed: int, log2_half: int = 5, device: int = 0,
                   precision: str = "bf16", max_slots: int = 1, quant: Optional[str] = None,
-                  groupsize: int = 128):
+                  groupsize: int = 128, compact: bool = False):
         """Seeded weights at cfg's shapes; quant="int8" quantizes the linears at finalize with
-        quantize.py's per-channel rule, quant="int4" with its groupwise rule (groupsize)."""
-        m = cls(cfg, device, precision, max_slots, quant, groupsize)
+        quantize.py's per-channel rule, quant="int4" with its groupwise rule (groupsize); compact: codes only."""
+        m = cls(cfg, device, precision, max_slots, quant, groupsize, compact)
         m.synth(seed, log2_half)
         m.finalize()
         return m
@@ -347,6 +356,17 @@ class DualARModel:
         return out[0], out[1]
 
     # ---- accounting / profiling --------------------------------------------------------
+    MEMORY_FIELDS = ("quant_fragments", "gemv_codes", "step_codes", "row_major", "other_weights", "kv_cache",
+                     "activations", "total")
+
+    def memory_info(self) -> dict:
+        """Steady-state device bytes of the finalized handle by class (fm_llm_memory_info): the bf16 / fp32 fragment
+        copies of quantised linears, the decode-GEMV code units + scale tables, the step-granular codes, the
+        row-major copies + tables, every other weight, the KV caches, activations and scratch, and their total."""
+        out = (ctypes.c_int64 * 8)()
+        native.check(native.lib().fm_llm_memory_info(self.h, out))
+        return dict(zip(self.MEMORY_FIELDS, (int(v) for v in out)))
+
     def frame_bytes(self, n: int, pos: int) -> int:
         return int(native.lib().fm_llm_frame_bytes(self.h, n, pos))
 

@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "fm_op_embed", "fm_op_quant4", "fm_op_batched_linear_q8", "fm_op_batched_linear_q4", "fm_rope_table",
     "fm_op_linear", "fm_op_gemv", "fm_op_rowgemv", "fm_op_rowgemv_pair", "fm_op_bstream", "fm_op_finalize_norm", "fm_op_prompt_skinny", "fm_op_sample",
     "fm_llm_prefix_save", "fm_llm_prefix_load", "fm_llm_prefix_drop", "fm_llm_prefix_info", "fm_llm_prefill_batch_at",
+    "fm_llm_set_quant_compact", "fm_llm_memory_info", "fm_op_linear_q",
 ]
 
 
@@ -110,6 +111,8 @@ def lib():
     L.fm_llm_open.argtypes = [vp, i32, i32, i32, ctypes.POINTER(vp)]
     L.fm_llm_set_quant.argtypes = [vp, i32]
     L.fm_llm_set_quant_int4.argtypes = [vp, i32]
+    L.fm_llm_set_quant_compact.argtypes = [vp, i32]
+    L.fm_llm_memory_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int64)]
     L.fm_llm_set_tensor.argtypes = [vp, ctypes.c_char_p, vp, i32, i64]
     L.fm_llm_synth_tensor.argtypes = [vp, ctypes.c_char_p, i64, u64, f32, i32]
     L.fm_llm_finalize.argtypes = [vp]
@@ -159,6 +162,8 @@ def lib():
     L.fm_rope_table.argtypes = [i32, i32, f32, pf32]
     L.fm_op_linear.argtypes = [i32, i32, i32, pf32, pf32, pf32, pf32, i32, pf32, i32, i32, i32, i32, i32, pf32, i32,
                                i32, i32, pi32, pi32]
+    L.fm_op_linear_q.argtypes = [i32, i32, i32, pf32, i32, i32, pf32, pf32, i32, pf32, i32, i32, i32, i32, pf32, pf32, i32,
+                                 i32, i32, pi32, pi32, ctypes.POINTER(ctypes.c_int8), pf32, pf32]
     L.fm_op_gemv.argtypes = [i32, i32, i32, i32, i32, pf32, pf32, pf32, pf32, f32, pf32, i32, pi32, i32, i32, i32,
                              pf32, i32, i32, i32, i32, i32, pf32, i32, i32, pf32, i32, pi32]
     L.fm_op_rowgemv.argtypes = [i32, i32, i32, pf32, pf32, pf32, f32, pf32, i32, i32, pf32, i32, i32, pi32, i32, i32,

@@ -208,6 +208,31 @@ def linear(w, x, y, epi=EPI_STORE, w2=None, bias=None, res=None, precision="bf16
     return int(ksb[0]), int(dirty[0])
 
 
+def linear_q(w, x, y_q, y_bf16, quant, epi=EPI_STORE, gs=128, bias=None, res=None, split=False, reps=1, device=0):
+    """fm_op_linear_q: w [N][K] (bf16-valued) quantised on the device (quant "int8": per-channel; "int4": groups of
+    gs), then launch_linear on x [R][ldx >= K] once from the packed bf16 fragments of the quantised weights
+    (y_bf16) and once from the step-granular codes alone (y_q); both [rows >= R][ldy >= N], filled in place.
+    Returns (ksb, dirty, q [N][K] int8 codes, scale, zero): scale [N] and zero None for int8, both [N][K / gs]
+    for int4."""
+    w, bias, x, res = _f(w), _f(bias), _f(x), _f(res)
+    N, K = w.shape
+    R, ldx = x.shape
+    y_q, y_bf16 = _out(y_q), _out(y_bf16)
+    assert y_q.shape == y_bf16.shape
+    q4 = quant == "int4"
+    ksb, dirty = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    q = np.zeros((N, K), np.int8)
+    sc = np.zeros((N, K // gs) if q4 else N, np.float32)
+    zr = np.zeros((N, K // gs), np.float32) if q4 else None
+    native.check(native.lib().fm_op_linear_q(device, native.FM_QUANT_INT4 if q4 else native.FM_QUANT_INT8, int(gs),
+                                             _p(w), N, K, _p(bias), _p(x), ldx, _p(res),
+                                             0 if res is None else res.shape[1], R, int(epi), int(split), _p(y_q),
+                                             _p(y_bf16), y_q.shape[1], y_q.shape[0], int(reps), native.i32p(ksb),
+                                             native.i32p(dirty), q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+                                             _p(sc), _p(zr)))
+    return int(ksb[0]), int(dirty[0]), q, sc, zr
+
+
 def gemv(w, x, y, pro=PRO_PLAIN, epi=EPI_STORE, ksb=1, R=None, w2=None, bias=None, nw=None, eps=1e-6, idx=None,
          idx_col=0, res=None, ss_gran=0, ss_out=None, precision="bf16", reps=1, device=0):
     """fm_op_gemv: launch_gemv.  x [R][ldx] (pro 1 with idx: the gathered table, R given), idx [R][idx_ld]

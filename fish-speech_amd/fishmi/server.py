@@ -286,18 +286,19 @@ def create_app(engine: "TTS.TTSInferenceEngine", max_text_length: int = 0, api_k
 
 def build_engine(llama_checkpoint_path: str, decoder_checkpoint_path: str, device=0, precision="bf16",
                  compile: bool = False, max_frames: int = 2048, slots: int = 1, reuse_prefix: bool = False,
-                 llama_queue=None, voice_cache_mb: int = 0):
+                 llama_queue=None, voice_cache_mb: int = 0, quant_compact: bool = False):
     """ModelManager (tools/server/model_manager.py): the LLM worker + the codec with its encoder.
     slots > 1: concurrent requests decode together on their own KV slots (fishmi.batching).
     voice_cache_mb > 0: the worker keeps the prompt KV of reference voices on the device, up to that many
     MiB (fishmi.prefix_cache); not wired through an already-launched llama_queue.
+    quant_compact: a weight-only checkpoint keeps only its codes on the device (no bf16 copy of the linears).
     llama_queue: an already-launched worker queue (the multi-GPU worker's, rank 0)."""
     from .codec import FishMICodec
     from .engine import launch_thread_safe_queue
 
     q = llama_queue if llama_queue is not None else \
         launch_thread_safe_queue(llama_checkpoint_path, device, precision, compile, max_slots=slots,
-                                 voice_cache_mb=voice_cache_mb)
+                                 voice_cache_mb=voice_cache_mb, quant_compact=quant_compact)
     codec = FishMICodec.from_checkpoint(decoder_checkpoint_path, device, precision, max_frames, encoder=True)
     return TTS.TTSInferenceEngine(q, codec, precision, compile, reuse_prefix=reuse_prefix)
 
@@ -322,6 +323,9 @@ def main(argv=None):
     ap.add_argument("--voice-cache-mb", type=int, default=0,
                     help="device MiB for the voice prefix cache: a reference voice's prompt KV is kept and copied "
                          "into later requests' slots instead of being prefilled again (0 = off)")
+    ap.add_argument("--quant-compact", action="store_true",
+                    help="weight-only (int8) checkpoints: keep only the codes on the device, no bf16 copy of the "
+                         "quantised linears (bit-identical output, less device memory; refused on a bf16 checkpoint)")
     a = ap.parse_args(argv)
     import uvicorn
 
@@ -343,9 +347,12 @@ def main(argv=None):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         if a.voice_cache_mb:
             ap.error("--voice-cache-mb: the voice prefix cache is not wired through the multi-GPU worker")
+        if a.quant_compact:
+            ap.error("--quant-compact is not wired through the multi-GPU worker")
         return _main_distributed(a)
     engine = build_engine(a.llama_checkpoint_path, a.decoder_checkpoint_path, _device_index(a.device), "bf16",
-                          slots=a.slots, reuse_prefix=a.reuse_prefix, voice_cache_mb=a.voice_cache_mb)
+                          slots=a.slots, reuse_prefix=a.reuse_prefix, voice_cache_mb=a.voice_cache_mb,
+                          quant_compact=a.quant_compact)
     host, port = a.listen.rsplit(":", 1)
     uvicorn.run(create_app(engine, a.max_text_length, a.api_key), host=host, port=int(port), workers=1)
 

@@ -119,6 +119,30 @@ int fm_llm_set_quant(fm_llm* h, int mode);
    stream the 4-bit codes (group size a multiple of 128).  The reference's packed checkpoint format
    (_convert_weight_to_int4pack tiles) is not read: quantize from the bf16 checkpoint instead. */
 int fm_llm_set_quant_int4(fm_llm* h, int groupsize);
+/* Compact weight-only handles, opt-in (bf16): keep only the codes.  Without it a quantised handle keeps, beside
+   the codes, a full bf16 fragment copy of every quantised linear (int8: bf16(q); int4: bf16(fma(q - 8, scale,
+   zero))) for the kernels that read bf16 tiles -- 2 bytes per weight.  With it fm_llm_finalize builds the
+   step-granular code copy of every quantised linear whatever max_slots is, frees each linear's bf16 copy once its
+   code copies are packed (an FM_DT_I8 tensor is never expanded to bf16 at all), and every launch reads codes: the
+   16-row MFMA tile kernel -- prompt chunks of more than 8 rows, the heads, every batched shape without a code
+   form of its own -- rebuilds each bf16 fragment from the codes right before its MFMAs, bit for bit, so a compact
+   handle computes exactly what the same handle computes without the flag.  The decode-GEMV units, the row-major
+   copies and the (scale, zero) / row-scale tables stay as they are.
+   Call after fm_llm_set_quant / fm_llm_set_quant_int4 and before any set_tensor: FM_ERR_STATE out of that order
+   or on an unquantised handle, FM_ERR_ARG on an fp32 handle (the code-reading forms are bf16).  fm_llm_finalize
+   on a compact handle returns FM_ERR_ARG, naming the tensor and leaving the handle as it was, unless every
+   quantised linear can be served from codes: int8, in_features a multiple of 64; int4, the group size and
+   in_features multiples of 128 and in_features a whole number of groups.
+   Peak memory during load is not lowered: set_tensor still uploads float weights whole before finalize quantises
+   them, and both copies of a linear exist until its codes are packed. */
+int fm_llm_set_quant_compact(fm_llm* h, int enable);
+/* Steady-state device bytes of a finalized handle, booked where they are allocated: out[0] the bf16 / fp32
+   fragment copies of quantised linears, [1] the decode-GEMV code units and their scale tables, [2] the
+   step-granular codes, [3] the row-major copies (codes or bf16 as they are) and their tables, [4] every other
+   weight (embeddings, norms, heads that are no quantised linear, an untied head's uploaded table, the QKV table),
+   [5] the KV caches, [6] activations and scratch, [7] their sum.  On an unquantised handle [0] .. [2] are 0 and
+   the packed weights count under [4].  Voice prefix snapshots are not included. */
+int fm_llm_memory_info(fm_llm* h, int64_t out[8]);
 /* name = reference state_dict key after remap (e.g. "layers.3.attention.wqkv.weight") */
 int fm_llm_set_tensor(fm_llm* h, const char* name, const void* host_data, int src_dtype,
                       int64_t numel);
@@ -252,7 +276,14 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    int4 handles, which those bits leave alone -- bit 0 (1) the first fast layer's QKV table (built the
    same way, by the quantised model's own launch), bit 1 (2) K / V only at codebook 0.  They act at batch
    1 in bf16 compute where the fused fast attention + wo launch runs, on models configured without an
-   o-bias, and change no output bit; inert on unquantised models and everywhere else. */
+   o-bias, and change no output bit; inert on unquantised models and everywhere else.
+   Compact handles (fm_llm_set_quant_compact) hold no bf16 copy of their quantised linears, so the six knobs
+   that would pick a reader of that copy are ignored for such a handle, which keeps its default routing:
+   "bstream" 0 and "bstream_acc" 0 (its batched frames stay on the accumulating kernel's code forms),
+   "bstream_chain" 1 (the chain forms read bf16 tiles), "bstream_q8" 0, "bstream_q4" 0 and "int4_stream" 0
+   (the codes are streamed whatever they say).  A shape whose batched kernel has no code form runs on the tile
+   kernel's code-reading form instead.  The knobs are process-wide: handles without the flag in the same
+   process keep their meaning. */
 int fm_tune(const char* key, int value);
 int fm_tune_get(const char* key, int* value);
 /* developer hook ("debug_ts" armed): per-block records of 8 words {tag = N<<32 | blockIdx.y<<16 |
@@ -329,6 +360,17 @@ int fm_op_batched_linear_q8(int device, const float* w, int N, int K, const floa
 int fm_op_linear(int device, int precision, int epi, const float* w, const float* w2, const float* bias,
                  const float* x, int ldx, const float* res, int ldr, int R, int N, int K, int split, float* y, int ldy,
                  int y_rows, int reps, int* ksb, int* dirty);
+/* Weight-only int8 / int4 on launch_linear (fm_llm_set_quant_compact's kernel forms; bf16): quantises the
+   bf16-valued w [N][K] on the device with the model's rule (quant 1: quantize.py's per-channel int8; quant 2:
+   group_quantize_tensor, group size gs a multiple of 128 dividing K, K a multiple of 128, no bias), packs the
+   bf16 fragments of the quantised weights and the step-granular codes, and runs launch_linear once per form on
+   the same operands: y_bf16 from the bf16 fragments, y_q from the codes alone (no bf16 weight is passed).  epi 0
+   (store), 1 (residual) or 3 (fp32); x, bias, res, split, ldy, y_rows, reps, ksb as fm_op_linear's; both outputs
+   are in/out; dirty sums both forms' leftover tickets.  q_out [N][K] (optional): the codes (int4: 0 .. 15);
+   scale_out: int8 [N] row scales, int4 [N][K / gs] group scales with zero_out [N][K / gs] (optional). */
+int fm_op_linear_q(int device, int quant, int gs, const float* w, int N, int K, const float* bias, const float* x,
+                   int ldx, const float* res, int ldr, int R, int epi, int split, float* y_q, float* y_bf16, int ldy,
+                   int y_rows, int reps, int* ksb, int* dirty, int8_t* q_out, float* scale_out, float* zero_out);
 /* launch_gemv (R <= 8) on ksb K slices (> 1 only with epi 4 / 5).  idx [R][idx_ld] (optional): column
    idx_col gathers the x rows (pro 1) or the residual rows (epi 5) from a table of idx_rows rows, indices
    clamped into it.  pro 3: x is first finalised by a zero-weight epi-5 launch, which leaves the sums of
