@@ -42,9 +42,9 @@ template <typename T> struct Run {
     // LDS-tiled implicit-GEMM kernels as a one-tap conv (conv_gemm2_kernel: 128-row x 96-128-column
     // tiles, or the 64 x 64 register tiles with split-K when the grid would not fill the chip).
     // The packed weight layout is the same; epilogues: round(acc + bias) and round(res + round(acc)).
-    bool prompt_gemm(const void* W, const void* W2, const void* bias, const void* X, int ldx, int R, int N, int K,
-                     void* Y, int ldy, const void* res, int ldr, int epi, const char* cls) {
-        if (R <= 32 || W2 || m->qinfo(W) || !fm_tuning().prompt_gemm ||
+    bool prompt_gemm(const Linear& W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
+                     const void* res, int ldr, int epi, const char* cls) {
+        if (R <= 32 || W.q8 || !fm_tuning().prompt_gemm ||
             (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU8) || N % 16 || K % 32 || N < 96 ||
             (epi == EPI_SWIGLU8 && (bias || N % 16)))
             return false;
@@ -54,7 +54,7 @@ template <typename T> struct Run {
         c.Ci = K;
         c.Lq = R;
         c.Lx = R;
-        c.w = (const T*)W;
+        c.w = (const T*)W.frag;
         c.Co = N;
         c.ntaps = 1;
         c.stride = 1;
@@ -79,7 +79,7 @@ template <typename T> struct Run {
                 c.ksplit = ks;
                 c.slab = m->skpart;
                 c.slab_cap = (size_t)m->skpart_cap;
-                PromptSkinnyArgs p{(const bf16_t*)W, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+                PromptSkinnyArgs p{(const bf16_t*)W.frag, (const bf16_t*)X, ldx, R, N, K, m->skpart};
                 const bool direct = ks == 1 && epi == EPI_SWIGLU8;  // the kernel stores act itself
                 if (direct) {
                     p.act = (bf16_t*)Y;
@@ -110,16 +110,16 @@ template <typename T> struct Run {
     // A prompt chunk's wo / w2 (32 < R <= 64, bf16) as raw K-slice partials in m->skpart ([ks][R][N], the
     // finalize_norm slab layout): the residual add, the bias and the next RMSNorm then run in one
     // finalize_norm launch instead of the split-K epilogue + an RMSNorm launch.  false: not eligible.
-    bool prompt_slab(const void* W, const void* X, int ldx, int R, int N, int K, int* ks_out) {
+    bool prompt_slab(const Linear& W, const void* X, int ldx, int R, int N, int K, int* ks_out) {
         if constexpr (sizeof(T) != 2) {
             return false;
         } else {
             if (!fm_tuning().prompt_fin || !fm_tuning().prompt_skinny || !fm_tuning().prompt_gemm || R <= 32 ||
-                R > 64 || m->qinfo(W) || N % 16 || K % 32 || ldx % 8 || ((uintptr_t)X & 15))
+                R > 64 || W.q8 || N % 16 || K % 32 || ldx % 8 || ((uintptr_t)X & 15))
                 return false;
             const int ks = prompt_skinny_ks(N, K, fm_tuning().prompt_skinny_blocks);
             if (ks <= 0 || (long long)ks * R * N > m->skpart_cap) return false;
-            const PromptSkinnyArgs p{(const bf16_t*)W, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+            const PromptSkinnyArgs p{(const bf16_t*)W.frag, (const bf16_t*)X, ldx, R, N, K, m->skpart};
             hipStream_t st = s;
             auto go = [st, p, ks] { launch_prompt_skinny(st, p, ks); };
             const int64_t bytes = (int64_t)N * K * E + (int64_t)R * K * E + (int64_t)ks * R * N * 4;
@@ -128,27 +128,25 @@ template <typename T> struct Run {
             return true;
         }
     }
-    void linear(const void* W, const void* W2, const void* bias, const void* X, int ldx, int R, int N,
-                int K, void* Y, int ldy, const void* res, int ldr, float* Yf, int epi, const char* cls) {
-        if (bs_use(R, false) && !W2 && !res && (epi == EPI_F32 || epi == EPI_STORE) &&
+    void linear(const Linear& W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
+                const void* res, int ldr, float* Yf, int epi, const char* cls) {
+        if (bs_use(R, false) && !res && (epi == EPI_F32 || epi == EPI_STORE) &&
             bs_linear(W, bias, X, ldx, R, N, K, Y, ldy, Yf, epi))
             return;  // heads / fast_project_in of a batched frame
-        if (prompt_gemm(W, W2, bias, X, ldx, R, N, K, Y, ldy, res, ldr, epi, cls)) return;
-        LinearArgs<T> a{(const T*)m->wdev(W), (const T*)W2, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y,
+        if (prompt_gemm(W, bias, X, ldx, R, N, K, Y, ldy, res, ldr, epi, cls)) return;
+        LinearArgs<T> a{(const T*)W.frag, nullptr, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y,
                         ldy, (const T*)res, ldr, Yf};
-        const auto* q = m->qinfo(W);
-        if (q) a.wscale = (const T*)q->scale;
-        const bool codes = q && q->compact;  // no bf16 copy: linear_kernel's code-reading form
-        if (codes) {
-            FMCHECK(sizeof(T) == 2 && !W2 && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_F32),
+        a.wscale = (const T*)W.scale;
+        if (!W.frag) {  // no bf16 copy: linear_kernel's code-reading form
+            FMCHECK(sizeof(T) == 2 && (epi == EPI_STORE || epi == EPI_RESID || epi == EPI_F32),
                     "compact linear: linear_kernel has no code-reading form of this launch");
-            if (q->sz) {
-                FMCHECK(q->q4s && K % 128 == 0, "compact int4 linear without its step-granular codes");
-                a.Wq4s = q->q4s;
-                a.wsz = q->sz;
+            if (W.sz) {
+                FMCHECK(W.q4s && K % 128 == 0, "compact int4 linear without its step-granular codes");
+                a.Wq4s = W.q4s;
+                a.wsz = W.sz;
             } else {
-                FMCHECK(q->q8s && K % 32 == 0, "compact int8 linear without its step-granular codes");
-                a.Wq8s = q->q8s;
+                FMCHECK(W.q8s && K % 32 == 0, "compact int8 linear without its step-granular codes");
+                a.Wq8s = W.q8s;
             }
         }
         if (R > GEMV_MAX_ROWS && R <= 64) {  // batched decode: split-K over the idle CUs
@@ -156,12 +154,9 @@ template <typename T> struct Run {
             a.part = m->skpart;
             a.tickets = m->tickets;
         }
-        // (a code form's bytes: bs_linear's formulas)
-        const int64_t wbytes = a.Wq4s   ? (int64_t)N * K / 2 + (int64_t)N * (K / 128) * 4
-                               : a.Wq8s ? (int64_t)N * K + (int64_t)N * 2
-                                        : (int64_t)N * K * E * (epi == EPI_SWIGLU ? 2 : 1);
-        const int64_t bytes = wbytes + (int64_t)R * K * E + (int64_t)R * N * (epi == EPI_F32 ? 4 : E);
-        const double flops = 2.0 * R * N * K * (epi == EPI_SWIGLU ? 2 : 1);
+        const int64_t bytes = step_wbytes(a.Wq4s ? 2 : (a.Wq8s ? 1 : 0), N, K, E) + (int64_t)R * K * E +
+                              (int64_t)R * N * (epi == EPI_F32 ? 4 : E);
+        const double flops = 2.0 * R * N * K;
         hipStream_t st = s;
         auto go = [st, a, epi] { launch_linear<T>(st, a, epi); };
         launch(cls, bytes, flops, go);
@@ -206,22 +201,21 @@ template <typename T> struct Run {
         void* res_out = nullptr;
         float* ss_out = nullptr;
     };
-    bool bs_linear(const void* W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
+    bool bs_linear(const Linear& W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
                    float* Yf, int epi, int* kparts_out = nullptr, const BsExtra* ex = nullptr) {
         const BstreamPlan p = bstream_plan(N, K, R, epi, E, m->compact);
         if (!p.ok || ((epi == EPI_SLABFIN || (ex && ex->pro == PRO_PRENORM)) && !p.acc)) return false;
-        BstreamArgs<T> a{(const T*)m->wdev(W), (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y, ldy, Yf};
-        const auto* q = m->qinfo(W);
-        const bool codes = q && q->compact;  // no bf16 copy: only a code-streaming form will do
-        if (q) a.wscale = (const T*)q->scale;
+        BstreamArgs<T> a{(const T*)W.frag, (const T*)bias, (const T*)X, ldx, R, N, K, (T*)Y, ldy, Yf};
+        const bool codes = !W.frag;  // no bf16 copy: only a code-streaming form will do
+        a.wscale = (const T*)W.scale;
         // weight-only int8 (fm_tune bstream_q8): the accumulating kernel streams the codes where it has the form
-        if (q && q->q8s && (fm_tuning().bstream_q8 || codes) && bsacc_q8_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E)) a.Wq8 = q->q8s;
+        if (W.q8s && (fm_tuning().bstream_q8 || codes) && bsacc_q8_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E)) a.Wq8 = W.q8s;
         // weight-only int4 (fm_tune bstream_q4; int4_stream 0 keeps the whole model on its dequantised weights):
         // the 4-bit codes and their (scale, zero) table
-        if (q && q->q4s && q->sz && ((fm_tuning().bstream_q4 && fm_tuning().int4_stream) || codes) &&
+        if (W.q4s && W.sz && ((fm_tuning().bstream_q4 && fm_tuning().int4_stream) || codes) &&
             bsacc_q4_ok(p, epi, ex ? ex->pro : PRO_PLAIN, E, K)) {
-            a.Wq4 = q->q4s;
-            a.wsz = q->sz;
+            a.Wq4 = W.q4s;
+            a.wsz = W.sz;
         }
         // the plan's kernel has no code instantiation: nothing launched, the caller's else branch reaches linear()
         if (codes && !a.Wq8 && !a.Wq4) return false;
@@ -239,10 +233,7 @@ template <typename T> struct Run {
             a.ss_out = ex->ss_out;
             a.tickets = m->tickets;
         }
-        const int64_t wbytes = a.Wq4   ? (int64_t)N * K / 2 + (int64_t)N * (K / 128) * 4  // codes + (scale, zero) words
-                               : a.Wq8 ? (int64_t)N * K + (int64_t)N * 2                  // codes + row scales
-                                       : (int64_t)N * K * E;
-        const int64_t bytes = wbytes + (int64_t)R * K * E +
+        const int64_t bytes = step_wbytes(a.Wq4 ? 2 : (a.Wq8 ? 1 : 0), N, K, E) + (int64_t)R * K * E +
                               (int64_t)R * N * (epi == EPI_SLAB ? 4 * p.kparts : (epi == EPI_F32 ? 4 : E));
         const double flops = 2.0 * R * N * K;
         hipStream_t st = s;
@@ -250,10 +241,6 @@ template <typename T> struct Run {
         launch("linear", bytes, flops, go);
         if (kparts_out) *kparts_out = p.kparts;
         return true;
-    }
-    const void* wscale(const void* W) const {
-        const auto* q = m->qinfo(W);
-        return q ? q->scale : nullptr;
     }
     // The batched bf16 chain on bsacc_kernel (fm_tune bstream_chain): Wo and W2 finalise the residual
     // rows and their tile sums of squares (EPI_SLABFIN), QKV and W13 normalise in their prologue
@@ -343,7 +330,7 @@ template <typename T> struct Run {
                                     attn_fd_ok(d.hd, d.nh / d.nkv);
             // (weight-only int8 keeps the STORE epilogue: its row scales apply before the rounding)
             const bool slab_ok = fm_tuning().bs_qkv_slab && fm_tuning().batched_fused_attn && m->bsQ && R <= 32 &&
-                                 (fused_fast || fused_slow) && !m->qinfo(L.wqkv);
+                                 (fused_fast || fused_slow) && !L.wqkv.q8;
             if (slab_ok && bs_linear(L.wqkv, nullptr, b.xnb, d.dim, R, d.nqkv(), d.dim, nullptr, d.nqkv(), m->bsQ,
                                      EPI_SLAB, &kp)) {
                 b.qslab = m->bsQ;
@@ -358,7 +345,7 @@ template <typename T> struct Run {
             b.qslab_kp = kp;
             return;
         }
-        linear(L.wqkv, nullptr, L.bqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, m->qkv, d.nqkv(), nullptr, 0, nullptr,
+        linear(L.wqkv, L.bqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, m->qkv, d.nqkv(), nullptr, 0, nullptr,
                EPI_STORE, "linear");
     }
     // One row per slot (batched decode frames, every fast pass): the fused decode attention
@@ -440,11 +427,11 @@ template <typename T> struct Run {
             FMCHECK(bs_linear(L.wo, L.bo, m->att, d.nq(), R, d.dim, d.nq(), nullptr, d.dim, m->bsA, EPI_SLABFIN, &kp, &eo),
                     "bsacc: no SLABFIN wo plan");
         } else if (b.bs && bs_linear(L.wo, nullptr, m->att, d.nq(), R, d.dim, d.nq(), nullptr, d.dim, m->bsA, EPI_SLAB, &kp)) {
-            finalize_norm(m->bsA, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, wscale(L.wo));
+            finalize_norm(m->bsA, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, L.wo.scale);
         } else if (!b.bs && prompt_slab(L.wo, m->att, d.nq(), R, d.dim, d.nq(), &kp)) {
             finalize_norm(m->skpart, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, nullptr);
         } else {
-            linear(L.wo, nullptr, L.bo, m->att, d.nq(), R, d.dim, d.nq(), b.hb, d.dim, b.xb, d.dim, nullptr,
+            linear(L.wo, L.bo, m->att, d.nq(), R, d.dim, d.nq(), b.hb, d.dim, b.xb, d.dim, nullptr,
                    EPI_RESID, "linear");
             run_("norm", 0, 0, [&] {
                 launch_rmsnorm<T>(s, (const T*)b.hb, d.dim, (const T*)L.fn, d.dim, m->c.norm_eps, (T*)b.xnb, d.dim, R);
@@ -470,10 +457,10 @@ template <typename T> struct Run {
             return;
         // a prompt chunk's w1 || w3 with the SwiGLU in its split-K epilogue (skinny path), else the
         // stored output and the SwiGLU launch
-        if (fm_tuning().prompt_swiglu && prompt_gemm(L.w13, nullptr, nullptr, b.xnb, d.dim, R, 2 * d.inter, d.dim, m->act,
+        if (fm_tuning().prompt_swiglu && prompt_gemm(L.w13, nullptr, b.xnb, d.dim, R, 2 * d.inter, d.dim, m->act,
                                                      d.inter, nullptr, 0, EPI_SWIGLU8, "linear"))
             return;
-        linear(L.w13, nullptr, nullptr, b.xnb, d.dim, R, 2 * d.inter, d.dim, m->act2, 2 * d.inter, nullptr, 0, nullptr,
+        linear(L.w13, nullptr, b.xnb, d.dim, R, 2 * d.inter, d.dim, m->act2, 2 * d.inter, nullptr, 0, nullptr,
                EPI_STORE, "linear");
         run_("other", 0, 0,
              [&] { launch_swiglu_i8<T>(s, (const T*)m->act2, 2 * d.inter, (T*)m->act, d.inter, d.inter, R); });
@@ -494,11 +481,11 @@ template <typename T> struct Run {
                     "bsacc: no SLABFIN w2 plan");
             x_ss = true;
         } else if (b.bs && bs_linear(L.w2, nullptr, m->act, d.inter, R, d.dim, d.inter, nullptr, d.dim, m->bsB, EPI_SLAB, &kp)) {
-            set_pending(m->bsB, kp, d.dim, R, b.hb, b.xb, wscale(L.w2));
+            set_pending(m->bsB, kp, d.dim, R, b.hb, b.xb, L.w2.scale);
         } else if (!b.bs && prompt_slab(L.w2, m->act, d.inter, R, d.dim, d.inter, &kp)) {
             set_pending(m->skpart, kp, d.dim, R, b.hb, b.xb, nullptr);
         } else {
-            linear(L.w2, nullptr, nullptr, m->act, d.inter, R, d.dim, d.inter, b.xb, d.dim, b.hb, d.dim, nullptr,
+            linear(L.w2, nullptr, m->act, d.inter, R, d.dim, d.inter, b.xb, d.dim, b.hb, d.dim, nullptr,
                    EPI_RESID, "linear");
         }
     }
@@ -526,15 +513,16 @@ template <typename T> struct Run {
     // ---- batch-1 GEMV chain: consecutive GEMVs of one row are deferred and launched together
     // (gemv_chain_kernel), up to GEMV_CHAIN_MAX per launch; any other launch flushes them first
     struct ChainSt {
+        const Linear* W;
         GemvArgs<T> a;
         int kind;
         int64_t bytes;
         double flops;
     };
     std::vector<ChainSt> chain;
-    int chain_kind(const GemvArgs<T>& a, int pro, int epi, int ksb) const {
+    int chain_kind(const Linear& W, const GemvArgs<T>& a, int pro, int epi, int ksb) const {
         const FmTuning& t = fm_tuning();
-        if (!t.gemv_chain || m->prof.on || ksb != 1 || a.R != 1 || a.Wq || m->qinfo(a.W) || !t.gemv_nt ||
+        if (!t.gemv_chain || m->prof.on || ksb != 1 || a.R != 1 || W.q8 || !t.gemv_nt ||
             t.gemv_u != 8 || t.gemv_wpb != 4 || a.N % 16 || a.xidx)
             return -1;
         if (pro == PRO_PLAIN && epi == EPI_SLABFIN) return GEMV_CHAIN_WO_W2;
@@ -552,7 +540,7 @@ template <typename T> struct Run {
         if (c.size() == 1) {
             static const int pro_of[4] = {PRO_PLAIN, PRO_PRENORM, PRO_PRENORM, PRO_PRENORM};
             static const int epi_of[4] = {EPI_SLABFIN, EPI_SWIGLU8, EPI_STORE, EPI_F32};
-            gemv_now(c[0].a, pro_of[c[0].kind], epi_of[c[0].kind], 1, "linear");
+            gemv_now(*c[0].W, c[0].a, pro_of[c[0].kind], epi_of[c[0].kind], 1, "linear");
             return;
         }
         GemvChainArgs<T> g{};
@@ -573,59 +561,50 @@ template <typename T> struct Run {
         auto go = [st, g] { launch_gemv_chain<T>(st, g); };
         launch("linear", bytes, flops, go);
     }
-    void gemv(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls, int tile0 = 0) {
-        const int kind = chain_kind(a, pro, epi, ksb);
+    // One decode GEMV of the linear W on the 16-row tile kernel; a carries everything but the weight.
+    void gemv(const Linear& W, GemvArgs<T> a, int pro, int epi, int ksb, const char* cls, int tile0 = 0) {
+        const int kind = chain_kind(W, a, pro, epi, ksb);
         if (kind < 0 || tile0) {
             chain_flush();
-            gemv_now(a, pro, epi, ksb, cls, tile0);
+            gemv_now(W, a, pro, epi, ksb, cls, tile0);
             return;
         }
-        const size_t E = sizeof(T);
-        const int64_t bytes = (int64_t)a.N * a.K * E + (int64_t)a.K * E;
-        chain.push_back(ChainSt{a, kind, bytes, 2.0 * a.N * a.K});
+        a.W = (const T*)W.frag;  // (chain_kind: not a quantised linear)
+        const int64_t bytes = gemv_wbytes(0, a.N, a.K, E) + (int64_t)a.K * E;
+        chain.push_back(ChainSt{&W, a, kind, bytes, 2.0 * a.N * a.K});
         if ((int)chain.size() >= std::min(GEMV_CHAIN_MAX, fm_tuning().chain_max) || kind == GEMV_CHAIN_HEAD)
             chain_flush();
     }
     // tile0 (fm_tune fast_dead_q bit 1; weight-only int8, whole K, STORE): the launch covers the 16-row tiles from
-    // tile0 on -- rows [16 tile0, N) of the same packed weight, found by its base a.W: the kernel's tile b is the
-    // weight's tile tile0 + b (a tile's codes are contiguous), so the codes, the row scales, the bias and Y move
-    // by the same rows and N shrinks; the tiles are independent, every output row is the full launch's
-    void gemv_now(GemvArgs<T> a, int pro, int epi, int ksb, const char* cls, int tile0 = 0) {
-        const auto* q = m->qinfo(a.W);
-        const bool codes = q && q->compact;  // a.W is the linear's key, not an address: the kernel gets the codes alone
-        if (q && q->sz && !fm_tuning().int4_stream && !codes) q = nullptr;  // int4 model on its dequantised bf16 weights
-        if (codes) {
-            FMCHECK(q->q8 && (q->sz || q->scale) && epi != EPI_SWIGLU, "compact linear without its decode-GEMV codes");
-            a.W = nullptr;
-        }
+    // tile0 on -- rows [16 tile0, N) of the same linear: the kernel's tile b is the weight's tile tile0 + b (a
+    // tile's codes are contiguous), so the codes, the row scales, the bias and Y move by the same rows and N
+    // shrinks; the tiles are independent, every output row is the full launch's
+    void gemv_now(const Linear& W, GemvArgs<T> a, int pro, int epi, int ksb, const char* cls, int tile0 = 0) {
+        // the form: the code units where the linear has them (an int4 handle on its dequantised bf16 weights under
+        // int4_stream 0 apart); a compact linear has nothing else
+        const int form = W.q8 && (!W.sz || fm_tuning().int4_stream || !W.frag) ? (W.sz ? 2 : 1) : 0;
+        FMCHECK(W.frag || (W.q8 && (W.sz || W.scale) && epi != EPI_SWIGLU), "compact linear without its decode-GEMV codes");
+        a.W = (const T*)W.frag;
         if (tile0) {
             const int r0 = 16 * tile0;
-            FMCHECK(q && !q->sz && ksb == 1 && epi == EPI_STORE && a.R == 1 && a.Y && tile0 > 0 && r0 < a.N && a.N % 16 == 0,
+            FMCHECK(form == 1 && ksb == 1 && epi == EPI_STORE && a.R == 1 && a.Y && tile0 > 0 && r0 < a.N && a.N % 16 == 0,
                     "GEMV from a tile offset: weight-only int8, whole K, one stored row");
             a.Y += r0;
             if (a.bias) a.bias += r0;
             a.N -= r0;
         }
-        int64_t wbytes = (int64_t)a.N * a.K * E * (epi == EPI_SWIGLU ? 2 : 1);
-        if (q) {
-            a.Wq = q->q8;
-            if (q->sz) {  // weight-only int4: 4-bit codes + group (scale, zero), whole 128-k units per slice
-                a.wsz = q->sz;
-                a.wscale = nullptr;
-                while (ksb > 1 && (a.K / ksb) % 128) ksb /= 2;
-                wbytes = (int64_t)a.N * a.K / 2 + (int64_t)(a.N + 15) / 16 * 16 * (a.K / 128) * 4;
-            } else {  // weight-only int8: the int8 stream, whole 64-k units per slice
-                a.wscale = (const T*)q->scale;
-                while (ksb > 1 && (a.K / ksb) % 64) ksb /= 2;
-                wbytes = (int64_t)a.N * a.K;
-                if (tile0) {
-                    a.Wq += (size_t)tile0 * 16 * a.K;
-                    a.wscale += 16 * tile0;
-                }
-            }
+        if (form == 2) {  // weight-only int4: 4-bit codes + group (scale, zero), whole 128-k units per slice
+            a.Wq = W.q8;
+            a.wsz = W.sz;
+            a.wscale = nullptr;
+            while (ksb > 1 && (a.K / ksb) % 128) ksb /= 2;
+        } else if (form == 1) {  // weight-only int8: the int8 stream, whole 64-k units per slice
+            a.Wq = W.q8 + (size_t)tile0 * 16 * a.K;
+            a.wscale = (const T*)W.scale + 16 * tile0;
+            while (ksb > 1 && (a.K / ksb) % 64) ksb /= 2;
         }
-        const int64_t bytes = wbytes + (int64_t)a.R * a.K * E;
-        const double flops = 2.0 * a.R * a.N * a.K * (epi == EPI_SWIGLU ? 2 : 1);
+        const int64_t bytes = gemv_wbytes(form, a.N, a.K, E) + (int64_t)a.R * a.K * E;
+        const double flops = 2.0 * a.R * a.N * a.K;
         hipStream_t st = s;
         if (!a.tickets) a.tickets = m->tickets;
         auto go = [st, a, pro, epi, ksb] { launch_gemv<T>(st, a, pro, epi, ksb); };
@@ -641,37 +620,34 @@ template <typename T> struct Run {
     bool row_fin(int n) const {
         const FmTuning& t = fm_tuning();
         return sizeof(T) == 2 && n == 1 && m->row_ok && (row_bits() & 1) && !t.gemv_chain && !t.attn_wo &&
-               (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact);
+               m->streams_codes();
     }
     // ... and wqkv (norm prologue, 8 rows per block)
     bool row_qkv(int n) const {
         const FmTuning& t = fm_tuning();
         // (int8: the tile kernel's wqkv measured as fast, 3.12 vs 3.14 ms per frame)
         return sizeof(T) == 2 && n == 1 && m->row_qkv_ok && m->quant != FM_QUANT_INT8 && (row_bits() & 2) &&
-               !t.gemv_chain && (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact);
+               !t.gemv_chain && m->streams_codes();
     }
     // ... and w1 || w3 (norm prologue, SwiGLU epilogue, 4 + 4 rows per block)
     bool row_w13(int n) const {
         const FmTuning& t = fm_tuning();
         return sizeof(T) == 2 && n == 1 && m->row_w13_ok && (row_bits() & 4) && !t.gemv_chain &&
-               (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact);
+               m->streams_codes();
     }
     // the row-block GEMV's weight: bf16 row-major, or the int8 codes + row scales, or the int4 code words + group
-    // (scale, zero) rows.  rowscale holds only w1 || w3's row-block interleaved scales (pack_w13 is its one
-    // writer), so for every other linear -- the codebook head included -- the lookup misses and the packed
-    // weight's own row scales apply.
-    void row_weight(RowGemvArgs& r, const void* rm, const void* packed) {
-        FMCHECK(rm, "row GEMV: the linear has no row-major copy");  // (packed may be a compact linear's key: never read)
+    // (scale, zero) rows
+    void row_weight(RowGemvArgs& r, const Linear& W) {
+        FMCHECK(W.rm, "row GEMV: the linear has no row-major copy");
         if (m->quant == FM_QUANT_INT4) {
-            r.Wq4 = (const uint32_t*)rm;
-            r.wsz = (const uint32_t*)m->rowsz.at(packed);
+            r.Wq4 = (const uint32_t*)W.rm;
+            r.wsz = W.rm_sz;
             r.gs = m->q4_gs;
         } else if (m->quant) {
-            r.Wq = (const int8_t*)rm;
-            auto it = m->rowscale.find(packed);
-            r.wscale = (const bf16_t*)(it != m->rowscale.end() ? it->second : m->qinfo(packed)->scale);
+            r.Wq = (const int8_t*)W.rm;
+            r.wscale = (const bf16_t*)W.rm_scale;
         } else {
-            r.W = (const bf16_t*)rm;
+            r.W = (const bf16_t*)W.rm;
         }
     }
     // ... from its row row0 on (K columns): the rows, and with them the int4 code words and (scale, zero) rows or the
@@ -687,11 +663,7 @@ template <typename T> struct Run {
             r.W += (size_t)row0 * K;
         }
     }
-    // weight bytes a row-block GEMV streams (int4: codes + group words; int8: codes + row scales)
-    static int64_t rowgemv_wbytes(const RowGemvArgs& a) {
-        return a.Wq4 ? (int64_t)a.N * a.K / 2 + (int64_t)a.N * (a.K / a.gs) * 4
-                     : (a.Wq ? (int64_t)a.N * a.K + (int64_t)a.N * 2 : (int64_t)a.N * a.K * 2);
-    }
+    static int64_t rowgemv_wbytes(const RowGemvArgs& a) { return row_wbytes(a.Wq4 ? 2 : (a.Wq ? 1 : 0), a.N, a.K, a.gs); }
     // the residual a wo GEMV adds: the layer's input row itself for a stack's first layer (a table row gathered
     // by xidx[xcol] at codebook > 0), else the residual row xb
     void row_residual(RowGemvArgs& r, bool first, const void* x_in, int ldx_in, const int32_t* xidx, int xcol,
@@ -757,7 +729,7 @@ template <typename T> struct Run {
     void qkv_row(const StackDims& d, const LayerW& L, const GemvArgs<T>& a, bool first, const void* x, int ldx,
                  const int32_t* xidx, int xcol, void* Y, bool kv_rows, bool two = false) {
         RowGemvArgs r{};
-        row_weight(r, L.wqkv_rm, L.wqkv);  // (bf16 or int4: row_qkv excludes int8 models)
+        row_weight(r, L.wqkv);  // (bf16 or int4: row_qkv excludes int8 models)
         r.X = (const bf16_t*)x;
         if (first) {
             r.ldx = ldx;
@@ -805,12 +777,11 @@ template <typename T> struct Run {
         a.xidx_col = xcol;
         a.xidx_rows = xidx ? m->cb : 0;
         // (kv_rows on the tile form: weight-only int8 only, small_path; the tiles from nq / 16 on)
-        gemv(a, PRO_NORM, EPI_STORE, 1, "linear", kv_rows ? d.nq() / 16 : 0);
+        gemv(L.wqkv, a, PRO_NORM, EPI_STORE, 1, "linear", kv_rows ? d.nq() / 16 : 0);
     }
     // the tile form's arguments of a fast layer's QKV at one row, no prefetch (the table build)
     GemvArgs<T> qkv_args(const StackDims& d, const LayerW& L, int n) {
         GemvArgs<T> a = ga();
-        a.W = (const T*)L.wqkv;
         a.bias = (const T*)L.bqkv;
         a.nw = (const T*)L.an;
         a.R = n;
@@ -874,7 +845,7 @@ template <typename T> struct Run {
         SmallPath p{};
         p.kv_only = kv_only;
         p.rf = row_fin(c.n);
-        const int fq = m->quant == FM_QUANT_INT8 ? 1 : (m->quant == FM_QUANT_INT4 ? 2 : 0);
+        const int fq = m->qmode();
         // (fw_any: the fused launch is this layer's form, whether or not this pass ends before it)
         const bool fw_any = c.is_fast && p.rf && fm_tuning().fattn_wo && m->fxt && m->fdm.n_layer * m->C >= 2 &&
                             m->fdm.n_layer * m->C <= 40 && fattn_wo_ok(d.nh, d.nkv, d.hd, c.cpos, d.dim, d.nq(), fq);
@@ -932,7 +903,7 @@ template <typename T> struct Run {
             a.ldx = d.dim;
             a.ss_in = m->ssX;
             a.ss_gran = p.rf ? 1 : 0;
-            gemv(a, PRO_PRENORM, EPI_STORE, 1, "linear", p.kv0 ? d.nq() / 16 : 0);  // (kv0 here: weight-only int8)
+            gemv(c.L.wqkv, a, PRO_PRENORM, EPI_STORE, 1, "linear", p.kv0 ? d.nq() / 16 : 0);  // (kv0 here: weight-only int8)
         }
     }
     // attention launch (none where wo does it: fw, att_wo)
@@ -972,7 +943,7 @@ template <typename T> struct Run {
         if (p.fw || p.rf) {
             FattnWoArgs A{};
             RowGemvArgs& r = A.wo;
-            row_weight(r, L.wo_rm, L.wo);
+            row_weight(r, L.wo);
             r.X = (const bf16_t*)m->att;  // (fw: unused, x comes from the tagged words)
             r.bias = (const bf16_t*)L.bo;
             if (!c.pair) {
@@ -1028,7 +999,6 @@ template <typename T> struct Run {
             return;
         }
         GemvArgs<T> a = ga();
-        a.W = (const T*)L.wo;
         a.bias = (const T*)L.bo;
         a.X = (const T*)m->att;
         a.ldx = d.nq();
@@ -1053,14 +1023,14 @@ template <typename T> struct Run {
         a.ss_out = m->ssH;
         a.tickets = m->tickets;
         if (p.att_wo) a.att = small_fast_args(c, p);
-        gemv(a, p.att_wo ? PRO_FATT : PRO_PLAIN, EPI_SLABFIN, c.kp.wo, "linear");
+        gemv(L.wo, a, p.att_wo ? PRO_FATT : PRO_PLAIN, EPI_SLABFIN, c.kp.wo, "linear");
     }
     // W1 || W3 (+ ffn_norm) -> SwiGLU act
     void small_w13(const Small& c, const SmallPath& p) {
         const StackDims& d = c.d;
         if (row_w13(c.n)) {
             RowGemvArgs r{};
-            row_weight(r, c.L.w13_rm, c.L.w13);
+            row_weight(r, c.L.w13);
             r.X = (const bf16_t*)row1(c, c.hb, d.dim);
             r.nw = (const bf16_t*)c.L.fn;
             r.eps = m->c.norm_eps;
@@ -1071,7 +1041,6 @@ template <typename T> struct Run {
             return;
         }
         GemvArgs<T> a = ga();
-        a.W = (const T*)c.L.w13;
         a.nw = (const T*)c.L.fn;
         a.R = c.pair == 1 ? 2 : c.n;  // (a pair's two rows: the ss_gran 1 prologue's two-row instantiation)
         a.N = 2 * d.inter;
@@ -1082,14 +1051,14 @@ template <typename T> struct Run {
         a.ss_gran = p.rf ? 1 : 0;
         a.Y = (T*)row1(c, m->act, d.inter);
         a.ldy = d.inter;
-        gemv(a, PRO_PRENORM, EPI_SWIGLU8, 1, "linear");
+        gemv(c.L.w13, a, PRO_PRENORM, EPI_SWIGLU8, 1, "linear");
     }
     // W2: the block output x = h + w2(act) into xo (tile form: split-K, finalised with its sums of squares)
     void small_w2(const Small& c, const SmallPath& p) {
         const StackDims& d = c.d;
         if (p.rf) {
             RowGemvArgs r{};
-            row_weight(r, c.L.w2_rm, c.L.w2);
+            row_weight(r, c.L.w2);
             r.X = (const bf16_t*)row1(c, m->act, d.inter);
             r.res = (const bf16_t*)row1(c, c.hb, d.dim);
             r.ldr = d.dim;
@@ -1106,7 +1075,6 @@ template <typename T> struct Run {
             return;
         }
         GemvArgs<T> a = ga();
-        a.W = (const T*)c.L.w2;
         a.X = (const T*)m->act;
         a.ldx = d.inter;
         a.R = c.n;
@@ -1120,7 +1088,7 @@ template <typename T> struct Run {
         a.ldro = d.dim;
         a.ss_out = m->ssX;
         a.tickets = m->tickets;
-        gemv(a, PRO_PLAIN, EPI_SLABFIN, c.kp.w2, "linear");
+        gemv(c.L.w2, a, PRO_PLAIN, EPI_SLABFIN, c.kp.w2, "linear");
     }
     // one pre-norm block (TransformerBlock.forward, llama.py:838-843) on n <= 8 rows.  Residual rows
     // are always finalised by the producing GEMV (EPI_SLABFIN: x / h in bf16 plus per-tile sums of
@@ -1153,7 +1121,6 @@ template <typename T> struct Run {
     const void* head_small(const void* xlast, bool pending, int n, int ksb_prev) {
         const fm_model_config& c = m->c;
         GemvArgs<T> a = ga();
-        a.W = (const T*)m->head_c;
         a.nw = (const T*)m->norm;
         a.R = n;
         a.N = m->Nhead;
@@ -1168,16 +1135,15 @@ template <typename T> struct Run {
             a.ldx = c.dim;
             a.ss_in = m->ssX;
             a.ss_gran = row_fin(n) ? 1 : 0;
-            gemv(a, PRO_PRENORM, EPI_F32, 1, "linear");
+            gemv(m->head_c, a, PRO_PRENORM, EPI_F32, 1, "linear");
         } else {
             a.X = (const T*)xlast;
             a.ldx = c.dim;
-            gemv(a, PRO_NORM, EPI_F32, 1, "linear");
+            gemv(m->head_c, a, PRO_NORM, EPI_F32, 1, "linear");
         }
         const void* hid = c.norm_fastlayer_input ? m->xnl : (pending ? xs : xlast);
         if (m->fproj_w) {
             GemvArgs<T> p = ga();
-            p.W = (const T*)m->fproj_w;
             p.bias = (const T*)m->fproj_b;
             p.X = (const T*)hid;
             p.ldx = c.dim;
@@ -1186,7 +1152,7 @@ template <typename T> struct Run {
             p.K = c.dim;
             p.Y = (T*)m->xl;
             p.ldy = c.fast_dim;
-            gemv(p, PRO_PLAIN, EPI_STORE, 1, "linear");
+            gemv(m->fproj_w, p, PRO_PLAIN, EPI_STORE, 1, "linear");
             return m->xl;
         }
         return hid;
@@ -1210,10 +1176,10 @@ template <typename T> struct Run {
     // the codebook head on the fast stack's output row(s) x
     void fast_head(int n, const void* x) {
         const fm_model_config& c = m->c;
-        if (sizeof(T) == 2 && n == 1 && m->fout_rm && (row_bits() & 8) && !fm_tuning().gemv_chain &&
-            (m->quant != FM_QUANT_INT4 || fm_tuning().int4_stream || m->compact)) {
+        if (sizeof(T) == 2 && n == 1 && m->fout.rm && (row_bits() & 8) && !fm_tuning().gemv_chain &&
+            m->streams_codes()) {
             RowGemvArgs r{};  // the codebook head on the row-block GEMV (norm prologue, fp32 logits)
-            row_weight(r, m->fout_rm, m->fout);
+            row_weight(r, m->fout);
             r.X = (const bf16_t*)x;
             r.nw = (const bf16_t*)m->fnorm;
             r.eps = c.norm_eps;
@@ -1223,7 +1189,6 @@ template <typename T> struct Run {
             rowgemv(r, ROWGEMV_NORM_F32);
         } else {
             GemvArgs<T> a = ga();
-            a.W = (const T*)m->fout;
             a.nw = (const T*)m->fnorm;
             a.R = n;
             a.N = m->cb;
@@ -1234,7 +1199,7 @@ template <typename T> struct Run {
             a.ldx = c.fast_dim;
             a.ss_in = m->ssX;
             a.ss_gran = row_fin(n) ? 1 : 0;
-            gemv(a, PRO_PRENORM, EPI_F32, 1, "linear");
+            gemv(m->fout, a, PRO_PRENORM, EPI_F32, 1, "linear");
         }
     }
 
@@ -1332,11 +1297,11 @@ template <typename T> struct Run {
             launch_rmsnorm<T>(s, (const T*)xlast, c.dim, (const T*)m->norm, c.dim, c.norm_eps, (T*)m->xnl,
                               c.dim, n);
         });
-        linear(m->head_c, nullptr, nullptr, m->xnl, c.dim, n, m->Nhead, c.dim, nullptr, m->Nhead,
+        linear(m->head_c, nullptr, m->xnl, c.dim, n, m->Nhead, c.dim, nullptr, m->Nhead,
                nullptr, 0, m->logits, EPI_F32, "linear");
         const void* src = c.norm_fastlayer_input ? m->xnl : xlast;
         if (m->fproj_w)
-            linear(m->fproj_w, nullptr, m->fproj_b, src, c.dim, n, c.fast_dim, c.dim, m->fx, c.fast_dim,
+            linear(m->fproj_w, m->fproj_b, src, c.dim, n, c.fast_dim, c.dim, m->fx, c.fast_dim,
                    nullptr, 0, nullptr, EPI_STORE, "linear");
         else
             HIPCHK(hipMemcpyAsync(m->fx, src, (size_t)n * c.dim * E, hipMemcpyDeviceToDevice, s));
@@ -1354,7 +1319,7 @@ template <typename T> struct Run {
                 launch_rmsnorm<T>(s, (const T*)m->fx, c.fast_dim, (const T*)m->fnorm, c.fast_dim,
                                   c.norm_eps, (T*)m->fxn, c.fast_dim, n);
             });
-            linear(m->fout, nullptr, nullptr, m->fxn, c.fast_dim, n, m->cb, c.fast_dim, nullptr, m->cb,
+            linear(m->fout, nullptr, m->fxn, c.fast_dim, n, m->cb, c.fast_dim, nullptr, m->cb,
                    nullptr, 0, m->flogits, EPI_F32, "linear");
         }
     }
@@ -1522,7 +1487,7 @@ template <typename F> static int with_prec(fm_llm* m, F&& f) {
 // launch can run at all (row-major wo / w2 copies; int4: int4_stream).
 void ensure_qkv0(fm_llm* m) {
     FmTuning& t = fm_tuning();
-    const bool want = m->quant ? (Run<bf16_t>::dead_q_bits(m) & 1) && m->row_ok && (m->quant != FM_QUANT_INT4 || t.int4_stream || m->compact)
+    const bool want = m->quant ? (Run<bf16_t>::dead_q_bits(m) & 1) && m->row_ok && m->streams_codes()
                                : (t.rowgemv & 32) != 0;
     if (!m->finalized || m->prec != FM_PREC_BF16 || !want || !m->fxt || m->C < 2 || !t.fattn_wo || t.gemv_chain ||
         m->fast.empty())

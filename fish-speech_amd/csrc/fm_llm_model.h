@@ -3,8 +3,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <deque>
-
 #include "fm_kernels.h"
 #include "fm_runtime.h"
 
@@ -43,10 +41,50 @@ inline int pick_ksb(int N, int K, int R, size_t esz) {
     return ksb;
 }
 
+// One nn.Linear [N][K] on the device, in every layout a kernel reads.  finalize() fills it once; the launches only
+// read it, and a pointer that is null means the linear has no such layout.  Every pointer is a device address.
+// Ownership: each buffer below is in fm_llm::allocs (freed once, at close), never in the DTensor map -- except an
+// int8 checkpoint's row scales (scale / rm_scale), which stay the "<name>.scales" DTensor's.
+struct Linear {
+    int N = 0, K = 0;
+    // packed bf16 / fp32 MFMA fragments (fm_kernels.h); null: a compact handle's quantised linear (fm_llm_set_quant_compact
+    // keeps only the codes), which every launcher serves from the code layouts below
+    const void* frag = nullptr;
+    // weight-only int8 / int4, decode-GEMV units: the packed codes (int4: 4-bit) with the int8 row scales [rows padded
+    // to 16] or the int4 packed (scale, zero) per (tile, 128-k unit, row)
+    const unsigned char* q8 = nullptr;
+    const void* scale = nullptr;
+    const uint32_t* sz = nullptr;
+    // bf16: the step-granular copy of the same codes the batched linears stream (max_slots > 8) and the tile kernel's
+    // code form reads (compact), with scale / sz above (launch_pack_q8s / launch_pack_q4s)
+    const unsigned char* q8s = nullptr;
+    const uint32_t* q4s = nullptr;
+    // the row-block GEMV's row-major copy (fm_rowgemv.hip): bf16 rows, int8 codes with their row scales (w1 || w3: in
+    // its row-block interleaved order), or int4 code words with their (scale, zero) rows
+    const void* rm = nullptr;
+    const void* rm_scale = nullptr;
+    const uint32_t* rm_sz = nullptr;
+    explicit operator bool() const { return frag || q8; }
+};
+
+// Weight bytes one launch streams (bench.py's roofline and fm_llm_profile_read report them), one formula per layout;
+// form: 0 the T weight (E bytes per element), 1 int8 codes, 2 int4 codes.  N: the rows the launch covers.
+// decode-GEMV units: int8 books no scales, int4 its (scale, zero) words of rows padded to 16
+inline int64_t gemv_wbytes(int form, int64_t N, int64_t K, int64_t E) {
+    return form == 2 ? N * K / 2 + (N + 15) / 16 * 16 * (K / 128) * 4 : (form == 1 ? N * K : N * K * E);
+}
+// the tile kernel's and bstream's step-granular codes: + a 2-byte scale per row, or a (scale, zero) word per 128-k unit
+inline int64_t step_wbytes(int form, int64_t N, int64_t K, int64_t E) {
+    return form == 2 ? N * K / 2 + N * (K / 128) * 4 : (form == 1 ? N * K + N * 2 : N * K * E);
+}
+// the row-major copy (bf16): + a 2-byte scale per row, or a (scale, zero) word per group of gs
+inline int64_t row_wbytes(int form, int64_t N, int64_t K, int gs) {
+    return form == 2 ? N * K / 2 + N * (K / gs) * 4 : (form == 1 ? N * K + N * 2 : N * K * 2);
+}
+
 struct LayerW {
-    void *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *bo = nullptr, *qn = nullptr, *kn = nullptr;
-    void *w13 = nullptr, *w2 = nullptr, *an = nullptr, *fn = nullptr;  // w13: row-interleaved W1||W3
-    void *wo_rm = nullptr, *w2_rm = nullptr, *wqkv_rm = nullptr, *w13_rm = nullptr;  // row-major as well (fm_rowgemv.hip)
+    Linear wqkv, wo, w13, w2;  // w13: row-interleaved W1||W3
+    void *bqkv = nullptr, *bo = nullptr, *qn = nullptr, *kn = nullptr, *an = nullptr, *fn = nullptr;
 };
 
 struct StackDims {
@@ -65,8 +103,9 @@ struct fm_llm {
     StackDims sd{}, fdm{};
     int S = 0, C = 0, C1 = 0, cb = 0, nsem = 0, Nhead = 0, maxsplit = 0, Rmax = 0;
     std::vector<LayerW> slow, fast;
-    void *emb = nullptr, *cbemb = nullptr, *norm = nullptr, *head_c = nullptr, *fproj_w = nullptr,
-         *fproj_b = nullptr, *femb = nullptr, *fnorm = nullptr, *fout = nullptr;
+    void *emb = nullptr, *cbemb = nullptr, *norm = nullptr, *fproj_b = nullptr, *femb = nullptr, *fnorm = nullptr;
+    // the constrained slow head; fast_project_in (unset when dim == fast_dim); the codebook head
+    Linear head_c, fproj_w, fout;
     // caches
     void *kc = nullptr, *vc = nullptr, *fkc = nullptr, *fvc = nullptr;
     size_t slot_stride = 0, layer_stride = 0, fslot_stride = 0, flayer_stride = 0;
@@ -110,50 +149,28 @@ struct fm_llm {
     std::map<int, hipGraphExec_t> graphs;
     Profiler prof;
     std::vector<void*> allocs;
-    // weight-only int8 (fm_llm_set_quant): packed T pointer of a linear -> its int8 form
+    // weight-only int8 / int4 (fm_llm_set_quant, fm_llm_set_quant_int4): the linears' code layouts are in their Linear
     int quant = FM_QUANT_NONE;
     int q4_gs = 0;  // int4: group size along K
+    int qmode() const { return quant == FM_QUANT_INT8 ? 1 : (quant == FM_QUANT_INT4 ? 2 : 0); }  // the kernels' QM
     int* fin_cnt = nullptr;   // split finalize_norm: [max rows][2] counters (zero between launches)
     float* fin_ss = nullptr;  //                      [max rows][16] chunk sums of squares
-    struct QInfo {
-        const unsigned char* q8 = nullptr;  // packed int8 (int4: 4-bit codes) decode-GEMV layout
-        const void* scale = nullptr;        // int8: [rows padded to 16] in packed row order
-        const uint32_t* sz = nullptr;       // int4: packed (scale, zero) per (tile, 128-k unit, row)
-        // int8, bf16, max_slots > 8: the step-granular code copy the batched linears stream
-        // (launch_pack_q8s; its own allocation, whatever row_copies frees)
-        const unsigned char* q8s = nullptr;
-        // int4 (sz set), bf16, max_slots > 8: the step-granular code copy the batched linears stream with
-        // sz (launch_pack_q4s; its own allocation too)
-        const uint32_t* q4s = nullptr;
-        // fm_llm_set_quant_compact: the linear has no bf16 fragment copy -- its key is no device address
-        // (compact_key) and every launcher reads the codes above
-        bool compact = false;
-    };
-    std::map<const void*, QInfo> qmap;
     // compact weight-only handles (fm_llm_set_quant_compact): finalize keeps the codes of every quantised
-    // linear and frees (int8 checkpoints: never makes) its bf16 copy.  A compact linear's key -- what LayerW,
-    // head_c, fout and fproj_w hold and qinfo() / rowmajor / rowsz / rowscale are looked up by -- is the
-    // address of one byte of ckeys: a host address no kernel may be handed (wdev() is null for it).
+    // linear and frees (int8 checkpoints: never makes) its bf16 copy: Linear::frag is null
     bool compact = false;
-    std::deque<char> ckeys;
-    const void* compact_key() {
-        ckeys.push_back(0);
-        return &ckeys.back();
-    }
+    // whether the <= 8-row launches stream the linears' codes: an int4 handle under fm_tune int4_stream 0 runs on its
+    // dequantised bf16 weights instead, unless it is compact and has none
+    bool streams_codes() const { return quant != FM_QUANT_INT4 || fm_tuning().int4_stream || compact; }
     // fm_llm_memory_info: steady-state device bytes, booked where they are allocated
     // (finalize; ensure_qkv0's table): [0] fragment copies of quantised linears, [1] decode-GEMV code units
     // and their scale tables, [2] step-granular codes, [3] row-major copies and their tables, [4] every
     // other weight, [5] KV caches, [6] activations and scratch
     int64_t mem[7] = {0, 0, 0, 0, 0, 0, 0};
     int mem_cat = 6;  // the class dalloc books under
-    std::map<const void*, void*> rowmajor;  // packed wo / w2 / wqkv -> row-major bf16 copy (int8 / int4: codes)
-    std::map<const void*, const void*> rowsz;  // int4: packed -> its row-major (scale, zero) table
-    std::map<const void*, const void*> rowscale;  // int8 w1 || w3: packed -> its row-block interleaved scales
-    bool row_ok = false;                    // every layer of both stacks has wo / w2 row-major
+    bool row_ok = false;                    // every layer of both stacks has wo / w2 row-major (Linear::rm)
     bool row_qkv_ok = false;                //                         ... and wqkv
     bool row_w13_ok = false;                //                         ... and w1 || w3
     uint32_t* fxt = nullptr;                // fused fast attention + wo: tagged attention words [nh * hd]
-    void* fout_rm = nullptr;                // the codebook head row-major (int8 / int4: codes), row-block GEMV
     int32_t* fiota = nullptr;               // [16]: fiota[c] = c - 1 (the fast KV prefetch's last cached row)
     // fm_tune rowgemv bit 5: the first fast layer's raw q|k|v row of every code [cb][fast nqkv] (bf16, unquantised
     // models; ensure_qkv0), valid while qkv0_epoch is the tuning epoch it was built under
@@ -171,21 +188,12 @@ struct fm_llm {
     std::map<int, Prefix> prefixes;
     int next_prefix_id = 1;
     int* pfx_slots = nullptr;  // device [max_slots]: the slot list of one prefix copy launch
-    const QInfo* qinfo(const void* W) const {
-        auto it = qmap.find(W);
-        return it == qmap.end() ? nullptr : &it->second;
-    }
-    // the packed T weight a kernel may read: null for a compact linear (its key is a host address)
-    const void* wdev(const void* W) const {
-        const QInfo* q = qinfo(W);
-        return q && q->compact ? nullptr : W;
-    }
 
     ~fm_llm() {
         if (device >= 0) (void)hipSetDevice(device);
         for (auto& g : graphs) (void)hipGraphExecDestroy(g.second);
-        for (auto& kv : w) {
-            if (kv.second.p && wdev(kv.second.p)) (void)hipFree(kv.second.p);  // (not a compact linear's key)
+        for (auto& kv : w) {  // the tensors as uploaded (finalize hands the linears' buffers over to allocs)
+            if (kv.second.p) (void)hipFree(kv.second.p);
             if (kv.second.q) (void)hipFree(kv.second.q);
         }
         for (void* p : allocs) (void)hipFree(p);

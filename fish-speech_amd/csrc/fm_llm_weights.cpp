@@ -79,14 +79,14 @@ static void* Wopt(fm_llm* m, const std::string& n) {
     return (it != m->w.end() && it->second.set) ? it->second.p : nullptr;
 }
 
+static bool ends(const std::string& n, const char* suf) {
+    const size_t L = strlen(suf);
+    return n.size() >= L && n.compare(n.size() - L, L, suf) == 0;
+}
+static bool is_ffn_w13(const std::string& n) { return ends(n, "feed_forward.w1.weight") || ends(n, "feed_forward.w3.weight"); }
 static bool is_linear_weight(const std::string& n) {
-    auto ends = [&](const char* suf) {
-        const size_t L = strlen(suf);
-        return n.size() >= L && n.compare(n.size() - L, L, suf) == 0;
-    };
-    return ends("attention.wqkv.weight") || ends("attention.wo.weight") || ends("feed_forward.w1.weight") ||
-           ends("feed_forward.w2.weight") || ends("feed_forward.w3.weight") || n == "fast_output.weight" ||
-           n == "fast_project_in.weight";
+    return ends(n, "attention.wqkv.weight") || ends(n, "attention.wo.weight") || is_ffn_w13(n) ||
+           ends(n, "feed_forward.w2.weight") || n == "fast_output.weight" || n == "fast_project_in.weight";
 }
 
 // every nn.Linear of the model (WeightOnlyInt8QuantHandler quantizes them all, quantize.py:190-206);
@@ -94,16 +94,41 @@ static bool is_linear_weight(const std::string& n) {
 bool is_quant_linear(const std::string& n) { return is_linear_weight(n) || n == "output.weight"; }
 std::string base_of(const std::string& n) { return n.substr(0, n.size() - strlen(".weight")); }
 
+static size_t pad16(int64_t rows) { return (size_t)(rows + 15) / 16 * 16; }
+
+// Every buffer a Linear reads is the handle's until close (fm_llm::allocs) and booked under one class of
+// fm_llm_memory_info: a new one ...
+static void* keep_alloc(fm_llm* m, size_t bytes, int cat, bool zero = false) {
+    m->mem_cat = cat;
+    void* p = m->dalloc(bytes, zero);
+    m->mem_cat = 6;
+    return p;
+}
+// ... or a tensor's own buffer that its Linear goes on reading
+static void keep(fm_llm* m, const void* p, size_t bytes, int cat) {
+    m->allocs.push_back(const_cast<void*>(p));
+    m->mem[cat] += (int64_t)bytes;
+}
+// finalize's temporaries: freed (null: none) once the stream's work on them is done
+static void* tmp_alloc(std::vector<void*>& tmp, size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, bytes));
+    tmp.push_back(p);
+    return p;
+}
+static void free_dev(fm_llm* m, const std::vector<void*>& ps) {
+    HIPCHK(hipStreamSynchronize(m->stream));
+    for (void* p : ps)
+        if (p) HIPCHK(hipFree(p));
+}
+
 // int8 row-major [rows][cols] (rows padded to 16) -> packed int8 decode-GEMV layout
-static void* pack_q8_dev(fm_llm* m, const void* q, int rows, int cols) {
+static const unsigned char* pack_q8_dev(fm_llm* m, const void* q, int rows, int cols) {
     FMCHECK(cols % 64 == 0, "int8 weights need in_features % 64 == 0");
-    void* dst = nullptr;
-    HIPCHK(hipMalloc(&dst, (size_t)(rows + 15) / 16 * 16 * cols));
+    void* dst = keep_alloc(m, pad16(rows) * cols, 1);
     launch_pack_q8(m->stream, (const int8_t*)q, rows, cols, (int8_t*)dst);
     HIPCHK(hipGetLastError());
-    m->allocs.push_back(dst);
-    m->mem[1] += (int64_t)(rows + 15) / 16 * 16 * cols;
-    return dst;
+    return (const unsigned char*)dst;
 }
 
 // the batched linears' step-granular copy of the same codes: only where bsacc_kernel can take it (int8,
@@ -112,56 +137,46 @@ static void* pack_q8_dev(fm_llm* m, const void* q, int rows, int cols) {
 static const unsigned char* pack_q8s_dev(fm_llm* m, const void* q, int rows, int cols) {
     if (m->quant != FM_QUANT_INT8 || m->prec != FM_PREC_BF16 || (m->max_slots <= GEMV_MAX_ROWS && !m->compact) || cols % 32)
         return nullptr;
-    void* dst = nullptr;
-    HIPCHK(hipMalloc(&dst, (size_t)(rows + 15) / 16 * 16 * cols));
+    void* dst = keep_alloc(m, pad16(rows) * cols, 2);
     launch_pack_q8s(m->stream, (const int8_t*)q, rows, cols, (int8_t*)dst);
     HIPCHK(hipGetLastError());
-    m->allocs.push_back(dst);
-    m->mem[2] += (int64_t)(rows + 15) / 16 * 16 * cols;
     return (const unsigned char*)dst;
 }
 
-// int4: codes row-major [rows][cols] + sz [rows][cols / gs] -> the packed GEMV stream and its
-// (scale, zero) table; none (the bf16 dequantised copy serves every kernel) unless the group size
-// and K are whole 128-k units
-static fm_llm::QInfo pack_q4_dev(fm_llm* m, const void* q, const void* sz, int rows, int cols) {
-    if (m->q4_gs % 128 || cols % 128) return fm_llm::QInfo{};
-    const size_t tiles = (size_t)(rows + 15) / 16;
-    void* dq = nullptr;
-    void* ds = nullptr;
-    HIPCHK(hipMalloc(&dq, tiles * 16 * cols / 2));
-    HIPCHK(hipMalloc(&ds, tiles * (cols / 128) * 16 * 4));
+// int4: codes row-major [L.N][L.K] + sz [L.N][L.K / gs] -> the packed GEMV stream and its (scale, zero) table; none
+// (the bf16 dequantised copy serves every kernel) unless the group size and K are whole 128-k units
+static void pack_q4_dev(fm_llm* m, Linear& L, const void* q, const void* sz) {
+    const int rows = L.N, cols = L.K;
+    if (m->q4_gs % 128 || cols % 128) return;
+    const size_t tiles = pad16(rows) / 16;
+    void* dq = keep_alloc(m, tiles * 16 * cols / 2, 1);
+    void* ds = keep_alloc(m, tiles * (cols / 128) * 16 * 4, 1);
     launch_pack_q4(m->stream, (const uint8_t*)q, rows, cols, (uint8_t*)dq);
     launch_pack_sz4(m->stream, (const uint32_t*)sz, rows, cols, m->q4_gs, (uint32_t*)ds);
     HIPCHK(hipGetLastError());
-    m->allocs.push_back(dq);
-    m->allocs.push_back(ds);
-    m->mem[1] += (int64_t)(tiles * 16 * cols / 2 + tiles * (cols / 128) * 16 * 4);
+    L.q8 = (const unsigned char*)dq;
+    L.sz = (const uint32_t*)ds;
     // the batched linears' step-granular copy of the same codes (they stream it with ds): only where
     // bsacc_kernel can take it -- bf16, a handle with more than GEMV_MAX_ROWS slots; a max_slots <= 8
     // handle allocates nothing here (a compact one does: linear_kernel's code form reads it).  Its own allocation:
     // row_copies 0 frees none of it.
-    void* d4 = nullptr;
     if (m->prec == FM_PREC_BF16 && (m->max_slots > GEMV_MAX_ROWS || m->compact)) {
-        HIPCHK(hipMalloc(&d4, tiles * 16 * cols / 2));
+        void* d4 = keep_alloc(m, tiles * 16 * cols / 2, 2);
         launch_pack_q4s(m->stream, (const uint8_t*)q, rows, cols, (uint32_t*)d4);
         HIPCHK(hipGetLastError());
-        m->allocs.push_back(d4);
-        m->mem[2] += (int64_t)(tiles * 16 * cols / 2);
+        L.q4s = (const uint32_t*)d4;
     }
-    return fm_llm::QInfo{(const unsigned char*)dq, nullptr, (const uint32_t*)ds, nullptr, (const uint32_t*)d4};
 }
 
 // int8 mode, before packing: every quantized linear ends with t.p = T(q) row-major (what the
 // T-fragment kernels read), t.q = int8 row-major, t.s = row scales.  int8 checkpoints supply q and
 // "<name>.scales"; float weights are quantized here with quantize.py's per-channel rule.
 static void quantize_linears(fm_llm* m) {
-    m->mem_cat = 1;  // (the int8 row scales allocated below belong to the decode-GEMV units)
     if (m->quant == FM_QUANT_INT4) {  // every linear: codes, group (scale, zero), dequantised bf16 in place
         for (auto& kv : m->w) {
             if (!is_quant_linear(kv.first)) continue;
             DTensor& t = kv.second;
-            const size_t rp = (size_t)(t.rows + 15) / 16 * 16;
+            const size_t rp = pad16(t.rows);
             HIPCHK(hipMalloc(&t.q, rp * t.cols));
             HIPCHK(hipMemsetAsync(t.q, 8, rp * t.cols, m->stream));
             void* sz = nullptr;
@@ -172,13 +187,12 @@ static void quantize_linears(fm_llm* m) {
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipStreamSynchronize(m->stream));
-        m->mem_cat = 6;
         return;
     }
     for (auto& kv : m->w) {
         if (!is_quant_linear(kv.first)) continue;
         DTensor& t = kv.second;
-        const size_t rp = (size_t)(t.rows + 15) / 16 * 16;
+        const size_t rp = pad16(t.rows);
         DTensor& sc = m->w.at(base_of(kv.first) + ".scales");
         if (t.q) {
             FMCHECK(sc.set, "int8 weight without scales: " + kv.first);
@@ -195,7 +209,7 @@ static void quantize_linears(fm_llm* m) {
             FMCHECK(!sc.set, "scales given with a float weight: " + kv.first);
             HIPCHK(hipMalloc(&t.q, rp * t.cols));
             HIPCHK(hipMemsetAsync(t.q, 0, rp * t.cols, m->stream));
-            t.s = m->dalloc(rp * m->esz);
+            t.s = keep_alloc(m, rp * m->esz, 1, true);  // (the int8 row scales belong to the decode-GEMV units)
             if (m->prec == FM_PREC_BF16)
                 launch_quant_rows<bf16_t>(m->stream, (bf16_t*)t.p, (int)t.rows, (int)t.cols, (int8_t*)t.q, (bf16_t*)t.s);
             else
@@ -204,22 +218,39 @@ static void quantize_linears(fm_llm* m) {
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(m->stream));
-    m->mem_cat = 6;
 }
 
 // row-major [rows][cols] device tensor -> packed fragment layout (fm_kernels.h)
 // (booked as the fragment copy of a quantised linear, qlin, or as any other weight)
 static void* pack_dev(fm_llm* m, const void* src, int rows, int cols, bool qlin) {
-    const size_t n = (size_t)(rows + 15) / 16 * 16 * cols;
-    void* dst = nullptr;
-    HIPCHK(hipMalloc(&dst, n * m->esz));
-    m->mem[qlin ? 0 : 4] += (int64_t)(n * m->esz);
+    void* dst = keep_alloc(m, pad16(rows) * cols * m->esz, qlin ? 0 : 4);
     if (m->prec == FM_PREC_BF16)
         launch_pack<bf16_t>(m->stream, (const bf16_t*)src, rows, cols, (bf16_t*)dst);
     else
         launch_pack<float>(m->stream, (const float*)src, rows, cols, (float*)dst);
     HIPCHK(hipGetLastError());
     return dst;
+}
+
+// The layouts every linear has, from its row-major forms.  The fragment copy of the T weight p [N][K]; a compact
+// handle packs none of a quantised linear, qlin (p null: its int8 checkpoint tensor was never expanded) ...
+static Linear frag_linear(fm_llm* m, const void* p, int N, int K, bool qlin) {
+    Linear L;
+    L.N = N;
+    L.K = K;
+    if (!(m->compact && qlin)) L.frag = pack_dev(m, p, N, K, qlin);
+    return L;
+}
+// ... and the code layouts of a quantised linear, from its codes q and their row scales / group (scale, zero) rows s
+static void pack_codes(fm_llm* m, Linear& L, const std::string& name, const void* q, const void* s) {
+    if (m->quant == FM_QUANT_INT4) {
+        pack_q4_dev(m, L, q, s);
+        FMCHECK(L.q8 || !m->compact, "compact: no int4 code layout for " + name);
+    } else {
+        L.q8 = pack_q8_dev(m, q, L.N, L.K);
+        L.scale = s;
+        L.q8s = pack_q8s_dev(m, q, L.N, L.K);
+    }
 }
 
 // bf16 wo / w2 / wqkv whose shapes the row-block GEMV takes keep their row-major copy
@@ -229,132 +260,153 @@ static bool row_bits(fm_llm* m, int bits) {
     const FmTuning& t = fm_tuning();
     return t.row_copies || ((m->quant == FM_QUANT_INT4 ? t.rowgemv_q4 : t.rowgemv) & bits) != 0;
 }
+// (bf16: the T row-major weight; weight-only int8 / int4: the row-major codes, rowgemv QM 1 / 2)
+static bool row_shape_ok(fm_llm* m, int cols) {
+    const int qm = m->qmode();
+    return m->prec == FM_PREC_BF16 && rowgemv_u(cols, qm) > 0 && (qm != 2 || (m->q4_gs % 8 == 0 && cols % m->q4_gs == 0));
+}
 static bool row_keep(fm_llm* m, const std::string& n, int rows, int cols) {
-    auto ends = [&](const char* suf) {
-        const size_t L = strlen(suf);
-        return n.size() >= L && n.compare(n.size() - L, L, suf) == 0;
-    };
-    // bf16: the T row-major weight; weight-only int8: the int8 row-major codes (rowgemv QM 1)
-    const int qm = m->quant == FM_QUANT_INT8 ? 1 : (m->quant == FM_QUANT_INT4 ? 2 : 0);
-    if (m->prec != FM_PREC_BF16 || rowgemv_u(cols, qm) == 0) return false;
-    if (qm == 2 && (m->q4_gs % 8 || cols % m->q4_gs)) return false;
-    if (ends("attention.wo.weight") || ends("feed_forward.w2.weight")) return rows % 2 == 0 && row_bits(m, 1);
-    if (n == "fast_output.weight") return rows % 8 == 0 && rowgemv_u(cols, qm) <= 8 && row_bits(m, 8);
-    return ends("attention.wqkv.weight") && rows % 8 == 0 && rowgemv_u(cols, qm) <= 8 && row_bits(m, 2 | 16);
+    if (!row_shape_ok(m, cols)) return false;
+    if (ends(n, "attention.wo.weight") || ends(n, "feed_forward.w2.weight")) return rows % 2 == 0 && row_bits(m, 1);
+    const bool u8 = rows % 8 == 0 && rowgemv_u(cols, m->qmode()) <= 8;
+    if (n == "fast_output.weight") return u8 && row_bits(m, 8);
+    return ends(n, "attention.wqkv.weight") && u8 && row_bits(m, 2 | 16);
 }
 
-static bool is_ffn_w13(const std::string& n) {
-    auto ends = [&](const char* suf) {
-        const size_t L = strlen(suf);
-        return n.size() >= L && n.compare(n.size() - L, L, suf) == 0;
-    };
-    return ends("feed_forward.w1.weight") || ends("feed_forward.w3.weight");
+// wqkv, wo, w2, the codebook head, fast_project_in: the tensor's row-major buffers are packed, then handed to the
+// row-block GEMV where it takes the shape (row_keep), else freed
+static Linear plain_linear(fm_llm* m, const std::string& n) {
+    auto it = m->w.find(n);
+    FMCHECK(it != m->w.end() && it->second.set, "tensor not set: " + n);
+    DTensor& t = it->second;
+    const int N = (int)t.rows, K = (int)t.cols;
+    Linear L = frag_linear(m, t.p, N, K, m->quant != FM_QUANT_NONE);
+    if (m->quant) pack_codes(m, L, n, t.q, t.s);
+    const bool rk = row_keep(m, n, N, K);
+    if (rk && m->quant == FM_QUANT_INT4) {  // the codes as packed row-major words + the row-major (scale, zero) table
+        void* rw = keep_alloc(m, (size_t)N * K / 2, 3);
+        launch_pack_q4_rows(m->stream, (const uint8_t*)t.q, N, K, (uint32_t*)rw);
+        HIPCHK(hipGetLastError());
+        L.rm = rw;
+        L.rm_sz = (const uint32_t*)t.s;
+        keep(m, t.s, pad16(N) * (K / m->q4_gs) * 4, 3);
+    } else if (rk && m->quant) {  // the int8 codes, row-major, and the row scales as they are
+        L.rm = t.q;
+        L.rm_scale = t.s;
+        keep(m, t.q, pad16(N) * K, 3);
+    } else if (rk) {
+        L.rm = t.p;
+        keep(m, t.p, pad16(N) * K * m->esz, 3);
+    }
+    // (int4's group rows are this tensor's own allocation; int8's row scales are not: quantize_linears)
+    std::vector<void*> done{t.q, m->quant == FM_QUANT_INT4 ? t.s : nullptr, t.p};
+    for (void*& p : done)
+        if (p == L.rm || p == L.rm_sz) p = nullptr;
+    free_dev(m, done);
+    t.p = t.q = t.s = nullptr;
+    return L;
+}
+
+// dst [2 * rows] rows of rb bytes: per block, rpb rows of a then the same rpb rows of b
+static void* interleave_rows(fm_llm* m, void* dst, const void* a, const void* b, int rows, int rpb, size_t rb) {
+    HIPCHK(hipMemcpy2DAsync(dst, 2 * rpb * rb, a, rpb * rb, rpb * rb, rows / rpb, hipMemcpyDeviceToDevice, m->stream));
+    HIPCHK(hipMemcpy2DAsync((char*)dst + rpb * rb, 2 * rpb * rb, b, rpb * rb, rpb * rb, rows / rpb, hipMemcpyDeviceToDevice,
+                            m->stream));
+    return dst;
 }
 
 // W1 [inter][dim] and W3 -> one packed [2*inter][dim] matrix whose 16-row tiles hold 8 rows of W1
 // then the same 8 rows of W3, so one GEMV tile (EPI_SWIGLU8) has both halves of 8 SwiGLU outputs and
 // the decode grid is 2*inter/16 single-matrix blocks.  The row-major W1/W3 are freed; their map
-// entries keep the shapes (the packed matrix hangs off the w1 entry).
-static void* pack_w13(fm_llm* m, const std::string& p, int inter, int dim) {
+// entries keep the shapes.
+static Linear w13_linear(fm_llm* m, const std::string& p, int inter, int dim) {
     FMCHECK(inter % 8 == 0, "intermediate_size must be a multiple of 8");
     DTensor& t1 = m->w.at(p + "feed_forward.w1.weight");
     DTensor& t3 = m->w.at(p + "feed_forward.w3.weight");
-    const size_t E = m->esz, rb = (size_t)dim * E;
-    void* tmp = nullptr;
-    void* pk = nullptr;
-    if (m->compact) {  // no T tiles: the key of the codes packed below
-        pk = const_cast<void*>(m->compact_key());
-    } else {
-        HIPCHK(hipMalloc(&tmp, 2 * (size_t)inter * rb));
-        HIPCHK(hipMemcpy2DAsync(tmp, 16 * rb, t1.p, 8 * rb, 8 * rb, inter / 8, hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync((char*)tmp + 8 * rb, 16 * rb, t3.p, 8 * rb, 8 * rb, inter / 8, hipMemcpyDeviceToDevice,
-                                m->stream));
-        pk = pack_dev(m, tmp, 2 * inter, dim, m->quant != FM_QUANT_NONE);
-    }
-    m->mem_cat = 3;  // the row-block GEMV's copies and their tables
+    const int qm = m->qmode();
+    // bytes per row: the T weight, its codes (one byte each), their row scale or group (scale, zero) words
+    const size_t E = m->esz, rb = (size_t)dim * E, qb = (size_t)dim, sb = qm == 2 ? (size_t)(dim / m->q4_gs) * 4 : E;
+    const size_t n2 = 2 * (size_t)inter;
+    std::vector<void*> tmp, ptmp;
+    auto il = [&](void* dst, const void* a1, const void* a3, int rpb, size_t bytes) {
+        return interleave_rows(m, dst, a1, a3, inter, rpb, bytes);
+    };
+    // the tile kernels' 8 + 8 interleave of the rows ...
+    const void* pt = m->compact ? nullptr : il(tmp_alloc(ptmp, n2 * rb), t1.p, t3.p, 8, rb);
+    Linear L = frag_linear(m, pt, 2 * inter, dim, qm != 0);
     // the row-block GEMV's copy (fm_rowgemv.hip ROWGEMV_NORM_SWIGLU): row-major, rows 4b .. 4b+3 of W1
     // then the same rows of W3, per 8-row block (bf16 rows, or int8 codes + scales, or int4 packed
     // code words + (scale, zero) rows)
-    const int qm = m->quant == FM_QUANT_INT8 ? 1 : (m->quant == FM_QUANT_INT4 ? 2 : 0);
-    const bool rk = m->prec == FM_PREC_BF16 && inter % 4 == 0 && rowgemv_u(dim, qm) > 0 && rowgemv_u(dim, qm) <= 8 &&
-                    (qm != 2 || (m->q4_gs % 8 == 0 && dim % m->q4_gs == 0)) && row_bits(m, 4);
-    auto il4 = [&](const void* a1, const void* a3, size_t rb4) -> void* {  // rb4: bytes per row
-        void* d = m->dalloc(2 * (size_t)inter * rb4, false);
-        HIPCHK(hipMemcpy2DAsync(d, 8 * rb4, a1, 4 * rb4, 4 * rb4, inter / 4, hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync((char*)d + 4 * rb4, 8 * rb4, a3, 4 * rb4, 4 * rb4, inter / 4, hipMemcpyDeviceToDevice,
-                                m->stream));
-        return d;
-    };
-    if (rk && qm == 0) m->rowmajor[pk] = il4(t1.p, t3.p, rb);
-    if (rk && qm == 1) {
-        m->rowmajor[pk] = il4(t1.q, t3.q, (size_t)dim);
-        m->rowscale[pk] = il4(t1.s, t3.s, E);
+    if (inter % 4 == 0 && row_shape_ok(m, dim) && rowgemv_u(dim, qm) <= 8 && row_bits(m, 4)) {
+        if (qm == 2) {  // one byte per code, interleaved, then packed to row words
+            std::vector<void*> ctmp;
+            const void* codes = il(tmp_alloc(ctmp, n2 * qb), t1.q, t3.q, 4, qb);
+            void* words = keep_alloc(m, n2 * qb / 2, 3);
+            launch_pack_q4_rows(m->stream, (const uint8_t*)codes, 2 * inter, dim, (uint32_t*)words);
+            HIPCHK(hipGetLastError());
+            free_dev(m, ctmp);
+            L.rm = words;
+            L.rm_sz = (const uint32_t*)il(keep_alloc(m, n2 * sb, 3), t1.s, t3.s, 4, sb);
+        } else {
+            L.rm = qm ? il(keep_alloc(m, n2 * qb, 3), t1.q, t3.q, 4, qb) : il(keep_alloc(m, n2 * rb, 3), t1.p, t3.p, 4, rb);
+            if (qm) L.rm_scale = il(keep_alloc(m, n2 * sb, 3), t1.s, t3.s, 4, sb);
+        }
     }
-    if (rk && qm == 2) {
-        void* codes = nullptr;  // one byte per code, interleaved, then packed to row words
-        HIPCHK(hipMalloc(&codes, 2 * (size_t)inter * dim));
-        HIPCHK(hipMemcpy2DAsync(codes, 8 * (size_t)dim, t1.q, 4 * (size_t)dim, 4 * (size_t)dim, inter / 4,
-                                hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync((char*)codes + 4 * (size_t)dim, 8 * (size_t)dim, t3.q, 4 * (size_t)dim, 4 * (size_t)dim,
-                                inter / 4, hipMemcpyDeviceToDevice, m->stream));
-        void* words = m->dalloc((size_t)inter * dim, false);
-        launch_pack_q4_rows(m->stream, (const uint8_t*)codes, 2 * inter, dim, (uint32_t*)words);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(m->stream));
-        HIPCHK(hipFree(codes));
-        m->rowmajor[pk] = words;
-        m->rowsz[pk] = il4(t1.s, t3.s, (size_t)(dim / m->q4_gs) * 4);
+    if (qm) {  // ... and the same interleave of the code rows and of their scale / (scale, zero) rows
+        const void* qt = il(tmp_alloc(tmp, n2 * qb), t1.q, t3.q, 8, qb);
+        // (int8: the row scales the code layouts go on reading; int4: pack_q4_dev repacks the group rows)
+        const void* st = il(qm == 1 ? keep_alloc(m, n2 * sb, 1) : tmp_alloc(tmp, n2 * sb), t1.s, t3.s, 8, sb);
+        pack_codes(m, L, p + "feed_forward.w1.weight", qt, st);
     }
-    if (m->quant == FM_QUANT_INT4) {  // the same interleave of the code rows and of the (scale, zero) rows
-        const size_t gb = (size_t)(dim / m->q4_gs) * 4;
-        void* qt = nullptr;
-        void* st = nullptr;
-        HIPCHK(hipMalloc(&qt, 2 * (size_t)inter * dim));
-        HIPCHK(hipMalloc(&st, 2 * (size_t)inter * gb));
-        HIPCHK(hipMemcpy2DAsync(qt, 16 * (size_t)dim, t1.q, 8 * (size_t)dim, 8 * (size_t)dim, inter / 8,
-                                hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync((char*)qt + 8 * (size_t)dim, 16 * (size_t)dim, t3.q, 8 * (size_t)dim,
-                                8 * (size_t)dim, inter / 8, hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync(st, 16 * gb, t1.s, 8 * gb, 8 * gb, inter / 8, hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync((char*)st + 8 * gb, 16 * gb, t3.s, 8 * gb, 8 * gb, inter / 8, hipMemcpyDeviceToDevice,
-                                m->stream));
-        fm_llm::QInfo qi = pack_q4_dev(m, qt, st, 2 * inter, dim);
-        qi.compact = m->compact;
-        FMCHECK(qi.q8 || !m->compact, "compact: no int4 code layout for " + p + "feed_forward.w1.weight");
-        if (qi.q8) m->qmap[pk] = qi;
-        HIPCHK(hipStreamSynchronize(m->stream));
-        for (void* p : {qt, st, t1.q, t3.q, t1.s, t3.s}) HIPCHK(hipFree(p));
-        t1.q = t3.q = nullptr;
-        t1.s = t3.s = nullptr;
-    } else if (m->quant) {  // the same interleave of the int8 rows and of the row scales
-        void* qt = nullptr;
-        HIPCHK(hipMalloc(&qt, 2 * (size_t)inter * dim));
-        HIPCHK(hipMemcpy2DAsync(qt, 16 * (size_t)dim, t1.q, 8 * (size_t)dim, 8 * (size_t)dim, inter / 8,
-                                hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync((char*)qt + 8 * (size_t)dim, 16 * (size_t)dim, t3.q, 8 * (size_t)dim,
-                                8 * (size_t)dim, inter / 8, hipMemcpyDeviceToDevice, m->stream));
-        m->mem_cat = 1;
-        void* s13 = m->dalloc(2 * (size_t)inter * E);
-        m->mem_cat = 3;
-        HIPCHK(hipMemcpy2DAsync(s13, 16 * E, t1.s, 8 * E, 8 * E, inter / 8, hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpy2DAsync((char*)s13 + 8 * E, 16 * E, t3.s, 8 * E, 8 * E, inter / 8, hipMemcpyDeviceToDevice,
-                                m->stream));
-        m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, qt, 2 * inter, dim), s13, nullptr,
-                                    pack_q8s_dev(m, qt, 2 * inter, dim), nullptr, m->compact};
-        HIPCHK(hipStreamSynchronize(m->stream));
-        HIPCHK(hipFree(qt));
-        HIPCHK(hipFree(t1.q));
-        HIPCHK(hipFree(t3.q));
-        t1.q = t3.q = nullptr;
+    // (int4's group rows are the tensors' own allocations; int8's row scales are not: quantize_linears)
+    // (freed codes first, T rows last: see finalize on the order)
+    tmp.insert(tmp.end(), {t1.q, t3.q, qm == 2 ? t1.s : nullptr, qm == 2 ? t3.s : nullptr});
+    tmp.insert(tmp.end(), ptmp.begin(), ptmp.end());
+    tmp.insert(tmp.end(), {t1.p, t3.p});
+    free_dev(m, tmp);
+    for (DTensor* t : {&t1, &t3}) t->p = t->q = t->s = nullptr;
+    return L;
+}
+
+// dst [Nhead padded to 16] rows of rb bytes: the constrained head's rows of the [vocab] table src -- the semantic
+// rows, then <|im_end|>
+static void* head_rows(fm_llm* m, void* dst, const void* src, size_t rb) {
+    const fm_model_config& c = m->c;
+    HIPCHK(hipMemcpyAsync(dst, (const char*)src + (size_t)c.semantic_begin_id * rb, (size_t)m->nsem * rb,
+                          hipMemcpyDeviceToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync((char*)dst + (size_t)m->nsem * rb, (const char*)src + (size_t)c.im_end_id * rb, rb,
+                          hipMemcpyDeviceToDevice, m->stream));
+    return dst;
+}
+
+// constrained head (inference.py:308-320): only the semantic rows + <|im_end|> can be
+// finite after the bias, so the LM head streams exactly those rows.
+static Linear head_linear(fm_llm* m) {
+    const fm_model_config& c = m->c;
+    m->nsem = c.semantic_end_id - c.semantic_begin_id + 1;
+    m->Nhead = m->nsem + 1;
+    FMCHECK(m->Nhead <= 8192, "constrained head wider than 8192 rows is not supported");
+    const size_t np = pad16(m->Nhead), rb = (size_t)c.dim * m->esz, qb = (size_t)c.dim;
+    if (!m->quant || c.tie_word_embeddings) {  // (a tied head is the embedding table's rows: not a quantised linear)
+        const void* table = c.tie_word_embeddings ? W(m, "embeddings.weight") : W(m, "output.weight");
+        return frag_linear(m, head_rows(m, keep_alloc(m, np * rb, 4, true), table, rb), m->Nhead, c.dim, false);
     }
-    HIPCHK(hipStreamSynchronize(m->stream));
-    m->mem_cat = 6;
-    if (tmp) HIPCHK(hipFree(tmp));
-    if (t1.p) HIPCHK(hipFree(t1.p));  // (null: a compact handle's int8 checkpoint tensor was never expanded)
-    if (t3.p) HIPCHK(hipFree(t3.p));
-    t1.p = pk;
-    t3.p = nullptr;
-    return pk;
+    // output.weight is a quantised linear: the same rows of its codes and of their scales / groups
+    DTensor& o = m->w.at("output.weight");
+    std::vector<void*> tmp;
+    const bool q4 = m->quant == FM_QUANT_INT4;
+    const size_t sb = q4 ? (size_t)(c.dim / m->q4_gs) * 4 : m->esz;
+    const void* hp = m->compact ? nullptr : head_rows(m, keep_alloc(m, np * rb, 4, true), o.p, rb);
+    Linear L = frag_linear(m, hp, m->Nhead, c.dim, true);
+    const void* hq = head_rows(m, q4 ? tmp_alloc(tmp, np * qb) : keep_alloc(m, np * qb, 1, true), o.q, qb);
+    const void* hs = head_rows(m, q4 ? tmp_alloc(tmp, np * sb) : keep_alloc(m, np * sb, 1, true), o.s, sb);
+    pack_codes(m, L, "output.weight", hq, hs);
+    // the table's codes (int4: and its own group rows) served only these rows; a compact handle's T copy too
+    tmp.insert(tmp.end(), {o.q, q4 ? o.s : nullptr, m->compact ? o.p : nullptr});
+    o.q = o.s = nullptr;
+    if (m->compact) o.p = nullptr;
+    free_dev(m, tmp);
+    return L;
 }
 
 void finalize(fm_llm* m) {
@@ -379,80 +431,32 @@ void finalize(fm_llm* m) {
         }
     }
     if (m->quant) quantize_linears(m);
-    for (auto& kv : m->w) {
-        if (!is_linear_weight(kv.first) || is_ffn_w13(kv.first)) continue;  // W1/W3: pack_w13 below
-        DTensor& t = kv.second;
-        // (a compact handle packs no T tiles: the linear's key stands where the packed pointer would)
-        void* pk = m->compact ? const_cast<void*>(m->compact_key())
-                              : pack_dev(m, t.p, (int)t.rows, (int)t.cols, m->quant != FM_QUANT_NONE);
-        if (m->quant == FM_QUANT_INT4) {
-            fm_llm::QInfo qi = pack_q4_dev(m, t.q, t.s, (int)t.rows, (int)t.cols);
-            qi.compact = m->compact;
-            FMCHECK(qi.q8 || !m->compact, "compact: no int4 code layout for " + kv.first);
-            if (qi.q8) m->qmap[pk] = qi;
-            const bool keep = row_keep(m, kv.first, (int)t.rows, (int)t.cols);
-            if (keep) {  // the codes as packed row-major words + the row-major (scale, zero) table
-                m->mem_cat = 3;
-                void* rw = m->dalloc((size_t)t.rows * t.cols / 2, false);
-                m->mem_cat = 6;
-                launch_pack_q4_rows(m->stream, (const uint8_t*)t.q, (int)t.rows, (int)t.cols, (uint32_t*)rw);
-                HIPCHK(hipGetLastError());
-                m->rowmajor[pk] = rw;
-                m->rowsz[pk] = t.s;
-                m->allocs.push_back(const_cast<void*>(t.s));
-                m->mem[3] += (int64_t)((t.rows + 15) / 16 * 16 * (t.cols / m->q4_gs) * 4);
-            }
-            HIPCHK(hipStreamSynchronize(m->stream));
-            HIPCHK(hipFree(t.q));
-            if (!keep) HIPCHK(hipFree(const_cast<void*>(t.s)));
-            t.q = nullptr;
-            t.s = nullptr;
-        } else if (m->quant) {
-            m->qmap[pk] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, t.q, (int)t.rows, (int)t.cols), t.s, nullptr,
-                                        pack_q8s_dev(m, t.q, (int)t.rows, (int)t.cols), nullptr, m->compact};
-            HIPCHK(hipStreamSynchronize(m->stream));
-            if (row_keep(m, kv.first, (int)t.rows, (int)t.cols)) {
-                m->rowmajor[pk] = t.q;  // the int8 codes, row-major, for the row-block GEMV
-                m->allocs.push_back(t.q);
-                m->mem[3] += (int64_t)((t.rows + 15) / 16 * 16 * t.cols);
-            } else {
-                HIPCHK(hipFree(t.q));
-            }
-            t.q = nullptr;
-        }
-        HIPCHK(hipStreamSynchronize(m->stream));
-        if (!m->quant && row_keep(m, kv.first, (int)t.rows, (int)t.cols)) {
-            m->rowmajor[pk] = t.p;  // kept for the batch-1 row-pair GEMV
-            m->allocs.push_back(t.p);
-            m->mem[3] += (int64_t)((t.rows + 15) / 16 * 16 * t.cols * m->esz);
-        } else if (t.p) {  // (null: a compact handle's int8 checkpoint tensor was never expanded)
-            HIPCHK(hipFree(t.p));
-        }
-        t.p = pk;
-    }
+    // wqkv, wo, w2, the codebook head, fast_project_in (W1 / W3: w13_linear below), all before the first W1 || W3
+    // and in the tensor map's order: the order of the allocations (and of the frees between them) decides where the
+    // weights lie on the device, and the frame times follow it by a few tenths of a percent (profiles/linear_record.md)
+    std::map<std::string, Linear> plain;
+    for (auto& kv : m->w)
+        if (is_linear_weight(kv.first) && !is_ffn_w13(kv.first)) plain[kv.first] = plain_linear(m, kv.first);
+    m->row_ok = m->row_qkv_ok = m->row_w13_ok = true;
     auto stack = [&](const std::string& pre, const StackDims& d, std::vector<LayerW>& out) {
         out.resize(d.n_layer);
         for (int i = 0; i < d.n_layer; ++i) {
             std::string p = pre + std::to_string(i) + ".";
             LayerW& L = out[i];
-            L.wqkv = W(m, p + "attention.wqkv.weight");
-            L.bqkv = Wopt(m, p + "attention.wqkv.bias");
-            L.wo = W(m, p + "attention.wo.weight");
-            L.bo = Wopt(m, p + "attention.wo.bias");
+            L.wqkv = plain.at(p + "attention.wqkv.weight");
+            L.wo = plain.at(p + "attention.wo.weight");
+            L.w13 = w13_linear(m, p, d.inter, d.dim);
+            L.w2 = plain.at(p + "feed_forward.w2.weight");
+            // WeightOnlyInt8Linear has no bias (quantize.py:206-229): the checkpoint's are unused
+            L.bqkv = m->quant ? nullptr : Wopt(m, p + "attention.wqkv.bias");
+            L.bo = m->quant ? nullptr : Wopt(m, p + "attention.wo.bias");
             L.qn = Wopt(m, p + "attention.q_norm.weight");
             L.kn = Wopt(m, p + "attention.k_norm.weight");
-            L.w13 = pack_w13(m, p, d.inter, d.dim);
-            L.w2 = W(m, p + "feed_forward.w2.weight");
             L.an = W(m, p + "attention_norm.weight");
             L.fn = W(m, p + "ffn_norm.weight");
-            auto rm = [&](const void* pk) -> void* {
-                auto it = m->rowmajor.find(pk);
-                return it == m->rowmajor.end() ? nullptr : it->second;
-            };
-            L.wo_rm = rm(L.wo);
-            L.w2_rm = rm(L.w2);
-            L.wqkv_rm = rm(L.wqkv);
-            L.w13_rm = rm(L.w13);
+            m->row_ok = m->row_ok && L.wo.rm && L.w2.rm;
+            m->row_qkv_ok = m->row_qkv_ok && L.wqkv.rm;
+            m->row_w13_ok = m->row_w13_ok && L.w13.rm;
         }
     };
     stack("layers.", m->sd, m->slow);
@@ -466,98 +470,15 @@ void finalize(fm_llm* m) {
     if (m->prec == FM_PREC_BF16)
         // (two rows: fm_tune fast_pair publishes codebook positions 0 and 1 in one launch)
         m->fxt = (uint32_t*)m->dalloc(2 * (size_t)m->fdm.nh * m->fdm.hd * sizeof(uint32_t));  // tags 0: never current
-    m->row_ok = m->row_qkv_ok = m->row_w13_ok = true;
-    for (auto* st : {&m->slow, &m->fast})
-        for (const LayerW& L : *st) {
-            m->row_ok = m->row_ok && L.wo_rm && L.w2_rm;
-            m->row_qkv_ok = m->row_qkv_ok && L.wqkv_rm;
-            m->row_w13_ok = m->row_w13_ok && L.w13_rm;
-        }
-    if (m->quant) {  // WeightOnlyInt8Linear has no bias (quantize.py:206-229): the checkpoint's are unused
-        for (auto* st : {&m->slow, &m->fast})
-            for (LayerW& L : *st) L.bqkv = L.bo = nullptr;
-    }
     m->emb = W(m, "embeddings.weight");
     m->cbemb = W(m, "codebook_embeddings.weight");
     m->norm = W(m, "norm.weight");
-    m->fproj_w = Wopt(m, "fast_project_in.weight");
+    if (plain.count("fast_project_in.weight")) m->fproj_w = plain.at("fast_project_in.weight");
     m->fproj_b = m->quant ? nullptr : Wopt(m, "fast_project_in.bias");
     m->femb = W(m, "fast_embeddings.weight");
     m->fnorm = W(m, "fast_norm.weight");
-    m->fout = W(m, "fast_output.weight");
-    {
-        auto it = m->rowmajor.find(m->fout);
-        m->fout_rm = it == m->rowmajor.end() ? nullptr : it->second;
-    }
-    // constrained head (inference.py:308-320): only the semantic rows + <|im_end|> can be
-    // finite after the bias, so the LM head streams exactly those rows.
-    const void* outw = c.tie_word_embeddings ? m->emb : W(m, "output.weight");
-    m->nsem = c.semantic_end_id - c.semantic_begin_id + 1;
-    m->Nhead = m->nsem + 1;
-    FMCHECK(m->Nhead <= 8192, "constrained head wider than 8192 rows is not supported");
-    const size_t rowb = (size_t)c.dim * m->esz;
-    const bool head_q = m->quant && !c.tie_word_embeddings;  // output.weight is a quantised linear; a tied head is not
-    if (m->compact && head_q) {
-        m->head_c = const_cast<void*>(m->compact_key());  // served from the compact rows of the codes packed below
-    } else {
-        m->mem_cat = 4;
-        void* head_rm = m->dalloc((size_t)(m->Nhead + 15) / 16 * 16 * rowb);
-        m->mem_cat = 6;
-        HIPCHK(hipMemcpyAsync(head_rm, (const char*)outw + (size_t)c.semantic_begin_id * rowb,
-                              (size_t)m->nsem * rowb, hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync((char*)head_rm + (size_t)m->nsem * rowb,
-                              (const char*)outw + (size_t)c.im_end_id * rowb, rowb, hipMemcpyDeviceToDevice,
-                              m->stream));
-        m->head_c = pack_dev(m, head_rm, m->Nhead, c.dim, head_q);
-        m->allocs.push_back(m->head_c);
-    }
-    if (m->quant == FM_QUANT_INT4 && !c.tie_word_embeddings) {  // the compact rows of the codes and groups
-        DTensor& o = m->w.at("output.weight");
-        const size_t gb = (size_t)(c.dim / m->q4_gs) * 4;
-        void* hq = nullptr;
-        void* hs = nullptr;
-        HIPCHK(hipMalloc(&hq, (size_t)(m->Nhead + 15) / 16 * 16 * c.dim));
-        HIPCHK(hipMalloc(&hs, (size_t)(m->Nhead + 15) / 16 * 16 * gb));
-        HIPCHK(hipMemcpyAsync(hq, (const char*)o.q + (size_t)c.semantic_begin_id * c.dim, (size_t)m->nsem * c.dim,
-                              hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync((char*)hq + (size_t)m->nsem * c.dim, (const char*)o.q + (size_t)c.im_end_id * c.dim,
-                              c.dim, hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync(hs, (const char*)o.s + (size_t)c.semantic_begin_id * gb, (size_t)m->nsem * gb,
-                              hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync((char*)hs + (size_t)m->nsem * gb, (const char*)o.s + (size_t)c.im_end_id * gb, gb,
-                              hipMemcpyDeviceToDevice, m->stream));
-        fm_llm::QInfo qi = pack_q4_dev(m, hq, hs, m->Nhead, c.dim);
-        qi.compact = m->compact;
-        FMCHECK(qi.q8 || !m->compact, "compact: no int4 code layout for output.weight");
-        if (qi.q8) m->qmap[m->head_c] = qi;
-        HIPCHK(hipStreamSynchronize(m->stream));
-        for (void* p : {hq, hs, o.q, o.s}) HIPCHK(hipFree(p));
-        o.q = o.s = nullptr;
-    } else if (m->quant && !c.tie_word_embeddings) {  // the same compact rows of the int8 head and its scales
-        DTensor& o = m->w.at("output.weight");
-        m->mem_cat = 1;
-        void* hq = m->dalloc((size_t)(m->Nhead + 15) / 16 * 16 * c.dim);
-        HIPCHK(hipMemcpyAsync(hq, (const char*)o.q + (size_t)c.semantic_begin_id * c.dim, (size_t)m->nsem * c.dim,
-                              hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync((char*)hq + (size_t)m->nsem * c.dim, (const char*)o.q + (size_t)c.im_end_id * c.dim,
-                              c.dim, hipMemcpyDeviceToDevice, m->stream));
-        void* hs = m->dalloc((size_t)(m->Nhead + 15) / 16 * 16 * m->esz);
-        HIPCHK(hipMemcpyAsync(hs, (const char*)o.s + (size_t)c.semantic_begin_id * m->esz, (size_t)m->nsem * m->esz,
-                              hipMemcpyDeviceToDevice, m->stream));
-        HIPCHK(hipMemcpyAsync((char*)hs + (size_t)m->nsem * m->esz, (const char*)o.s + (size_t)c.im_end_id * m->esz,
-                              m->esz, hipMemcpyDeviceToDevice, m->stream));
-        m->mem_cat = 6;
-        m->qmap[m->head_c] = fm_llm::QInfo{(const unsigned char*)pack_q8_dev(m, hq, m->Nhead, c.dim), hs, nullptr,
-                                           pack_q8s_dev(m, hq, m->Nhead, c.dim), nullptr, m->compact};
-        HIPCHK(hipStreamSynchronize(m->stream));
-        HIPCHK(hipFree(o.q));
-        o.q = nullptr;
-    }
-    if (m->compact && head_q) {  // the whole table's T copy served only the head rows above
-        DTensor& o = m->w.at("output.weight");
-        if (o.p) HIPCHK(hipFree(o.p));
-        o.p = nullptr;
-    }
+    m->fout = plain.at("fast_output.weight");
+    m->head_c = head_linear(m);
     // every tensor still held as uploaded: embeddings, norms, biases, an untied head's table (int8: the row scales)
     for (auto& kv : m->w) {
         const DTensor& t = kv.second;

@@ -244,6 +244,79 @@ def test_decode_frames_run_the_same_launches(quant, max_slots):
         cmp_.close()
 
 
+HANDLES = {"bf16": (None, False), "int8": ("int8", False), "int4": ("int4", False),
+           "int8_compact": ("int8", True), "int4_compact": ("int4", True)}
+MEM = ("quant_fragments", "gemv_codes", "step_codes", "row_major", "other_weights", "kv_cache", "activations", "total")
+# (handle, max_slots) -> memory_info() in MEM's order, then [launches, bytes] of prefill "linear", prefill "attn",
+# decode "linear", decode "attn"
+BOOKED = {
+    ("bf16", 1): ((0, 0, 0, 17891328, 19442688, 137216, 84685920, 122157152),
+                  [40, 45156352], [12, 5242880], [40, 45012992], [12, 5242880]),
+    ("bf16", 12): ((0, 0, 0, 17891328, 19442688, 1646592, 86859072, 125839680),
+                   [62, 70390832], [36, 0], [62, 67521584], [14, 0]),
+    ("int8", 1): ((17973248, 9075776, 0, 8962048, 1469440, 137216, 84685920, 122303648),
+                  [43, 29376640], [14, 2894848], [43, 24780928], [14, 2894848]),
+    ("int8", 12): ((17973248, 9075776, 8986624, 8962048, 1469440, 1646592, 86859072, 134972800),
+                   [62, 42884402], [36, 0], [62, 35463474], [14, 0]),
+    ("int4", 1): ((17973248, 4774144, 0, 4752384, 1469440, 137216, 84685920, 113792352),
+                  [43, 19872256], [14, 1531904], [43, 13183488], [14, 1531904]),
+    ("int4", 12): ((17973248, 4774144, 4493312, 4752384, 1469440, 1646592, 86859072, 121968192),
+                   [62, 30165312], [36, 0], [62, 20640064], [14, 0]),
+    ("int8_compact", 1): ((0, 9075776, 8986624, 8962048, 977920, 137216, 84685920, 112825504),
+                          [43, 24935552], [14, 2894848], [43, 24780928], [14, 2894848]),
+    ("int8_compact", 12): ((0, 9075776, 8986624, 8962048, 977920, 1646592, 86859072, 116508032),
+                           [62, 38443314], [36, 0], [62, 35463474], [14, 0]),
+    ("int4_compact", 1): ((0, 4774144, 4493312, 4752384, 977920, 137216, 84685920, 99820896),
+                          [43, 13326848], [14, 1531904], [43, 13183488], [14, 1531904]),
+    ("int4_compact", 12): ((0, 4774144, 4493312, 4752384, 977920, 1646592, 86859072, 103503424),
+                           [62, 23619904], [36, 0], [62, 20640064], [14, 0]),
+}
+
+
+def _booked(handle, max_slots):
+    """the handle's memory_info() and the profile_read deltas [launches, bytes] of "linear" and "attn" over
+    prefill_batch of the slots' 6 + s-token prompts, then over one eager decode of all slots"""
+    from fishmi.llm import DualARModel
+
+    quant, compact = HANDLES[handle]
+    cfg = _cfg()
+    m = DualARModel.synthetic(cfg, 11, 5, 0, "bf16", max_slots, quant=quant, groupsize=GS, compact=compact)
+    slots = list(range(max_slots))
+    prompts = [_tokens(cfg, 6 + s, 2, 40 + s)[0] for s in slots]
+    sps = [DualARModel.sampling(top_k=1) for _ in slots]
+    read = lambda: {c: m.profile_read(c)[1:] for c in ("linear", "attn")}  # noqa: E731
+    delta = lambda a, b: {c: [b[c][0] - a[c][0], b[c][1] - a[c][1]] for c in a}  # noqa: E731
+    try:
+        out = {"memory": m.memory_info()}
+        m.profile(True)
+        try:
+            r0 = read()
+            m.prefill_batch(slots, prompts, sps)
+            r1 = read()
+            m.decode(slots)
+            r2 = read()
+        finally:
+            m.profile(False)
+        out["prefill"], out["decode"] = delta(r0, r1), delta(r1, r2)
+        return out
+    finally:
+        m.close()
+
+
+@pytest.mark.parametrize("max_slots", [1, NS])
+@pytest.mark.parametrize("handle", list(HANDLES))
+def test_booked_figures(handle, max_slots):
+    """The absolute figures the handle books: every memory_info() class, and the "linear" / "attn" launch counts and
+    bytes of a batched prefill and of one eager decode frame, equal to the integers recorded on the MI355X from
+    commit 471cf80 (compact weight-only handles), the last one before each linear became one Linear record: the
+    weight-byte formula of every layout and the byte class of every buffer are unchanged."""
+    got = _booked(handle, max_slots)
+    print(handle, max_slots, got)
+    mem, pl, pa, dl, da = BOOKED[(handle, max_slots)]
+    assert got == {"memory": dict(zip(MEM, mem)), "prefill": {"linear": pl, "attn": pa},
+                   "decode": {"linear": dl, "attn": da}}
+
+
 # ------------------------------------------------------------------------------------------ 3. op level
 EPIS = {"store": ops.EPI_STORE, "resid": ops.EPI_RESID, "f32": ops.EPI_F32}
 
