@@ -11,24 +11,8 @@
 #include <memory>
 
 #include "fm_codec.h"
+#include "fm_codec_prep.h"
 #include "fm_runtime.h"
-
-struct PackedW {
-    void* w = nullptr;
-    size_t wphase = 0;
-    int Co = 0, Ci = 0, ntaps = 1, nphase = 1, stride = 1;
-    int shift[8] = {0};
-    void* bias = nullptr;
-    int ks = 1;  // split-K factor (small-M layers; a property of the layer, so every chunking of a
-                 // streamed decode sums in the same order as the one-shot decode)
-};
-// split-K factor of a layer that runs at a few hundred rows: K steps of 32 per slice >= 8, <= 8 slices
-static void small_m(PackedW& W) {
-    const int S = (W.ntaps * W.Ci + 31) / 32;
-    int ks = 1;
-    while (ks < 8 && S / (2 * ks) >= 8) ks *= 2;
-    W.ks = W.Co % 8 == 0 ? ks : 1;
-}
 
 // [A rows | B rows] of two packed one-tap linears over the same input as one PackedW (the packed
 // layout is 16-row tile-major, so it is the two buffers back to back)
@@ -339,7 +323,6 @@ static void* as_snake(fm_codec* m, const float* src, int64_t n) {
     return d;
 }
 
-// prepare a GEMM weight: kind per conv_weight_kernel; returns phases packed
 static PackedW concat_rows(fm_codec* m, const PackedW& A, const PackedW& B) {
     FMCHECK(A.Ci == B.Ci && A.ntaps == 1 && B.ntaps == 1 && A.nphase == 1 && B.nphase == 1 && A.Co % 16 == 0 &&
                 A.Co == B.Co && !A.bias && !B.bias && A.ks == B.ks && A.wphase == B.wphase,
@@ -354,36 +337,11 @@ static PackedW concat_rows(fm_codec* m, const PackedW& A, const PackedW& B) {
     return p;
 }
 
+// prepare a GEMM weight (pack_conv_weight, fm_codec_prep.h) and its bias
 static PackedW prep(fm_codec* m, const float* w, int kind, int Ci, int Co, int k, int s, int dil,
                     const float* bias) {
-    PackedW p;
-    p.Co = Co;
-    p.Ci = Ci;
-    p.ntaps = kind == 0 ? k : (kind == 1 ? 2 : 1);
-    p.nphase = (kind == 1 || kind == 2) ? s : 1;
-    p.stride = (kind == 1 || kind == 2) ? s : 1;
-    FMCHECK(p.ntaps <= 8, "too many taps");
-    FMCHECK(Ci % 8 == 0, "codec channel counts must be multiples of 8");
-    for (int j = 0; j < p.ntaps; ++j) p.shift[j] = kind == 0 ? (k - 1 - j) * dil : j;
-    const int Kt = (p.ntaps * Ci + 31) / 32 * 32;  // padded
-    const size_t rm = (size_t)p.nphase * Co * Kt;
-    p.wphase = (size_t)(Co + 15) / 16 * 16 * Kt;
-    void* tmp = nullptr;
-    HIPCHK(hipMalloc(&tmp, rm * m->esz));
-    p.w = m->dalloc(p.wphase * p.nphase * m->esz);
-    if (m->prec == FM_PREC_BF16) {
-        launch_conv_weight<bf16_t>(m->stream, w, kind, Ci, Co, k, s, (bf16_t*)tmp);
-        for (int ph = 0; ph < p.nphase; ++ph)
-            launch_pack<bf16_t>(m->stream, (const bf16_t*)tmp + (size_t)ph * Co * Kt, Co, Kt,
-                                (bf16_t*)p.w + ph * p.wphase);
-    } else {
-        launch_conv_weight<float>(m->stream, w, kind, Ci, Co, k, s, (float*)tmp);
-        for (int ph = 0; ph < p.nphase; ++ph)
-            launch_pack<float>(m->stream, (const float*)tmp + (size_t)ph * Co * Kt, Co, Kt,
-                               (float*)p.w + ph * p.wphase);
-    }
-    HIPCHK(hipStreamSynchronize(m->stream));
-    HIPCHK(hipFree(tmp));
+    PackedW p = pack_conv_weight(m->stream, m->prec, w, kind, Ci, Co, k, s, dil,
+                                 [m](size_t bytes) { return m->dalloc(bytes); });
     p.bias = bias ? as_T(m, bias, Co) : nullptr;
     return p;
 }
@@ -415,18 +373,9 @@ static std::vector<float> to_host(fm_codec* m, const float* d, size_t n) {
     HIPCHK(hipMemcpy(h.data(), d, n * 4, hipMemcpyDeviceToHost));
     return h;
 }
-// causal conv k = 2s, stride s (CausalConvNet, modded_dac.py:59-90; left pad k - s, no right pad
-// when L % s == 0): out[t] = sum_j W[j] x[ts + j - s] = tap0 . x'[t-1] + tap1 . x'[t] over the
-// contiguous view x'[L/s][s*Ci] of a time-major x, with x'[t][jj*Ci + ci] = x[ts + jj][ci]
+// causal conv k = 2s, stride s as two taps over the [L/s][s*Ci] view (strided_as_two_taps, fm_codec_prep.h)
 static PackedW prep_strided(fm_codec* m, const float* wdev, int Ci, int Co, int s, const float* bias) {
-    const std::vector<float> w = to_host(m, wdev, (size_t)Co * Ci * 2 * s);
-    std::vector<float> o((size_t)Co * s * Ci * 2);
-    for (int co = 0; co < Co; ++co)
-        for (int ci = 0; ci < Ci; ++ci)
-            for (int jj = 0; jj < s; ++jj)
-                for (int tap = 0; tap < 2; ++tap)
-                    o[(((size_t)co * s + jj) * Ci + ci) * 2 + tap] = w[((size_t)co * Ci + ci) * 2 * s + tap * s + jj];
-    return prep_host(m, o, s * Ci, Co, 2, bias);
+    return prep_host(m, strided_as_two_taps(to_host(m, wdev, (size_t)Co * Ci * 2 * s), Ci, Co, s), s * Ci, Co, 2, bias);
 }
 static void prep_tlayers(fm_codec* m, std::vector<TLayer>& tl, const std::string& pre, int dim, int layers, int HD,
                          int I) {
@@ -705,39 +654,17 @@ template <typename T> struct CRun {
     void gemm(const PackedW& W, const void* x, int ldx, int Lq, int Lx, void* out, int ldo, int flags,
               const void* res = nullptr, int ldr = 0, const void* gamma = nullptr, const void* alpha2 = nullptr,
               void* out2 = nullptr, int ldo2 = 0, int lo = 0) {
-        ConvArgs<T> a{};
-        a.x = (const T*)x;
-        a.ldx = ldx;
-        a.Ci = W.Ci;
-        a.Lq = Lq;
-        a.Lx = Lx;
-        a.w = (const T*)W.w;
-        a.wphase = W.wphase;
-        a.Co = W.Co;
-        a.ntaps = W.ntaps;
-        a.stride = W.stride;
-        a.nphase = W.nphase;
-        for (int j = 0; j < 8; ++j) a.shift[j] = W.shift[j];
-        a.bias = (const T*)W.bias;
-        a.gamma = (const T*)gamma;
-        a.res = (const T*)res;
-        a.ldr = ldr;
-        a.alpha2 = (const T*)alpha2;
+        const float* ia2 = nullptr;
         if (alpha2) {
             auto it = m->ialpha.find(alpha2);
             FMCHECK(it != m->ialpha.end(), "codec: Snake alpha without reciprocals");
-            a.ialpha2 = it->second;
+            ia2 = it->second;
         }
-        a.out = out;
-        a.ldo = ldo;
-        a.out2 = (T*)out2;
-        a.ldo2 = ldo2;
-        a.flags = flags | (W.bias ? CE_BIAS : 0) | ((out2 && !(flags & CE_NORM)) ? CE_SNAKE : 0);
+        ConvArgs<T> a = conv_site_args<T>(W, x, ldx, Lq, Lx, out, ldo, flags, res, ldr, gamma, alpha2, ia2, out2, ldo2, lo);
         if (flags & CE_NORM) {
             a.normw = (const T*)norm_w_;
             a.norm_eps = m->c.norm_eps;
         }
-        a.lo = lo;
         a.slab = m->ksp;
         a.slab_cap = m->ksp_cap;
         a.ksplit = fm_tuning().conv_splitk ? W.ks : 1;

@@ -90,6 +90,16 @@ struct RvqPtrs {
     const float* b[16];   // out_proj bias [D]
 };
 
+// What launch_conv_gemm does with a call (a pure function of the shape, the flags, the operands'
+// alignment and fm_tune conv2): the GEMM kernel, the K slices, the row segments a split-K call is cut
+// into (seg_rows each, the last one shorter; kernel is that of the full segments, kernel_last that of
+// the last one) and the kernel that runs the epilogue.
+enum { CK_REG = 0, CK_LDS6 = 1, CK_LDS8 = 2 };      // conv_gemm_kernel, conv_gemm2_kernel<6>, <8>
+enum { CEK_GEMM = 0, CEK_SPLITK = 1, CEK_NORM = 2 };  // in the GEMM kernel, conv_splitk_epi(_norm)_kernel
+struct ConvPlan {
+    int kernel, ksplit, nseg, epi, seg_rows, kernel_last;
+};
+template <typename T> ConvPlan conv_plan(const ConvArgs<T>& a);
 template <typename T> void launch_conv_gemm(hipStream_t s, const ConvArgs<T>& a);
 // the split-K epilogue alone over a.ksplit slabs in a.slab (the prompt skinny GEMM's finisher)
 template <typename T> void launch_conv_epi(hipStream_t s, const ConvArgs<T>& a);

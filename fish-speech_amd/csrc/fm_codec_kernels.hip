@@ -103,7 +103,9 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs<T> a) {
             for (int u = 0; u < 2; ++u) {
                 const int t = tq0 + 16 * u + (lane & 15);
                 if (t >= a.Lq) continue;
-                float* dst = a.slab + ((size_t)(kz * a.nphase + phase) * a.Lq + t) * a.Co + co0 + 16 * c + 4 * (lane >> 4);
+                const int co = co0 + 16 * c + 4 * (lane >> 4);
+                if (co >= a.Co) continue;  // Co % 16 == 8: the tile's upper half is past the slab row (Co % 4 == 0)
+                float* dst = a.slab + ((size_t)(kz * a.nphase + phase) * a.Lq + t) * a.Co + co;
                 *reinterpret_cast<f32x4_t*>(dst) = acc[c][u];
             }
         }
@@ -809,12 +811,64 @@ template <typename T, int NCO> static void conv2_go(hipStream_t s, const ConvArg
 
 
 
+// The GEMM kernel of one launch over Lq rows: LDS-staged tiles where the channels fill them and the
+// grid gives the chip >= 256 blocks (the 128-row tile, 96-128 channels), else the register kernel
+template <typename T> static int conv_kernel_of(const ConvArgs<T>& a, int Lq, int ksplit, bool vec_ok) {
+    const long long blocks = (long long)FM_CEIL(Lq, CG2_BM) * FM_CEIL(a.Co, 128) * a.nphase * ksplit;
+    const bool wide = fm_tuning().conv2 && vec_ok && a.Ci % 8 == 0 && a.Ci >= 32 && a.Co % 16 == 0 && a.Co >= 96;
+    if (!wide || !(blocks >= 256 || (ksplit == 1 && Lq >= 4096))) return CK_REG;
+    return (a.Co % 128 == 0 || a.Co >= 384) ? CK_LDS8 : CK_LDS6;
+}
+
+template <typename T> ConvPlan conv_plan(const ConvArgs<T>& a) {
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const bool vec_ok = !(a.flags & CE_F32OUT) && al16(a.out) && al16(a.out2) && al16(a.res) && a.ldo % 8 == 0 &&
+                        a.ldo2 % 8 == 0 && a.ldr % 8 == 0;  // the coalesced epilogue's 16-B accesses
+    ConvPlan p{};
+    if (a.ksplit > 1 && a.slab && vec_ok && a.Co % 8 == 0) {
+        // rows in segments that fit the workspace
+        const size_t per_row = (size_t)a.ksplit * a.nphase * a.Co;
+        p.seg_rows = (int)std::min<size_t>((size_t)a.Lq, a.slab_cap / per_row / 64 * 64);
+        p.ksplit = a.ksplit;
+        p.nseg = p.seg_rows > 0 ? FM_CEIL(a.Lq, p.seg_rows) : 0;
+        p.kernel = conv_kernel_of(a, std::max(p.seg_rows, 1), a.ksplit, true);
+        // (a shorter last segment has a smaller grid, so it may fall back to the register kernel)
+        const int last = p.seg_rows > 0 ? a.Lq - (p.nseg - 1) * p.seg_rows : 1;
+        p.kernel_last = conv_kernel_of(a, last, a.ksplit, true);
+        p.epi = (a.flags & CE_NORM) ? CEK_NORM : CEK_SPLITK;
+        return p;
+    }
+    p.seg_rows = a.Lq;
+    p.ksplit = 1;
+    p.nseg = 1;
+    p.kernel = p.kernel_last = conv_kernel_of(a, a.Lq, 1, vec_ok);
+    p.epi = CEK_GEMM;
+    return p;
+}
+
+template <typename T> static void conv_go(hipStream_t s, const ConvArgs<T>& b, int kernel) {
+    if (kernel == CK_LDS8) {
+        conv2_go<T, 8>(s, b);
+    } else if (kernel == CK_LDS6) {
+        conv2_go<T, 6>(s, b);
+    } else {
+        dim3 g(FM_CEIL(b.Lq, 64), FM_CEIL(b.Co, 64), b.nphase * (b.ksplit > 1 ? b.ksplit : 1));
+        conv_gemm_kernel<T><<<g, 256, 0, s>>>(b);
+    }
+}
+
 // A split-K layer (PackedW::ks > 1): K slices into fp32 slabs, then conv_splitk_epi_kernel; rows in
 // segments that fit the workspace (pointers offset, the carried-context bound lo moved with them)
-template <typename T> static void conv_splitk_go(hipStream_t s, const ConvArgs<T>& a) {
-    const size_t per_row = (size_t)a.ksplit * a.nphase * a.Co;
-    const int seg = (int)std::min<size_t>((size_t)a.Lq, a.slab_cap / per_row / 64 * 64);
+template <typename T> static void conv_splitk_go(hipStream_t s, const ConvArgs<T>& a, const ConvPlan& p) {
+    const int seg = p.seg_rows;
     FMCHECK(seg >= 64 || seg == a.Lq, "conv split-K: workspace too small");
+    // the epilogues' 8-channel chunks: a SwiGLU half, a RoPE head and the q / k span are whole chunks
+    FMCHECK(!(a.flags & CE_SWIGLU) || a.Co % 16 == 0, "conv: the SwiGLU epilogue needs Co % 16 == 0");
+    FMCHECK(!(a.flags & CE_ROPE) || (a.rope && a.rope_hd >= 8 && a.rope_hd % 8 == 0 && a.rope_nqk % a.rope_hd == 0 &&
+                                     a.rope_nqk <= a.Co && a.rope_pos0 >= 0),
+            "conv: the RoPE epilogue needs its table, head_dim % 8 == 0 and whole heads within Co");
+    FMCHECK(!(a.flags & CE_NORM) || (a.nphase == 1 && a.Co % 512 == 0 && a.Co <= 2048 && a.normw && a.out2),
+            "conv: the norm epilogue needs one phase, Co a multiple of 512 up to 2048, weight and out2");
     for (int r0 = 0; r0 < a.Lq; r0 += seg) {
         ConvArgs<T> b = a;
         b.Lq = std::min(seg, a.Lq - r0);
@@ -826,19 +880,8 @@ template <typename T> static void conv_splitk_go(hipStream_t s, const ConvArgs<T
         if (a.out) b.out = (char*)a.out + o * a.ldo * sizeof(T);
         if (a.res) b.res = a.res + o * a.ldr;
         if (a.out2) b.out2 = a.out2 + o * a.ldo2;
-        const long long t128 = (long long)FM_CEIL(b.Lq, CG2_BM) * FM_CEIL(b.Co, 128) * b.nphase * b.ksplit;
-        if (fm_tuning().conv2 && b.Ci % 8 == 0 && b.Ci >= 32 && b.Co % 16 == 0 && b.Co >= 96 && t128 >= 256) {
-            if (b.Co % 128 == 0 || b.Co >= 384)
-                conv2_go<T, 8>(s, b);
-            else
-                conv2_go<T, 6>(s, b);
-        } else {
-            dim3 g(FM_CEIL(b.Lq, 64), FM_CEIL(b.Co, 64), b.nphase * b.ksplit);
-            conv_gemm_kernel<T><<<g, 256, 0, s>>>(b);
-        }
-        if (b.flags & CE_NORM) {
-            FMCHECK(b.nphase == 1 && b.Co % 512 == 0 && b.Co <= 2048 && b.normw && b.out2,
-                    "conv: the norm epilogue needs one phase, Co a multiple of 512 up to 2048, weight and out2");
+        conv_go<T>(s, b, r0 + seg < a.Lq ? p.kernel : p.kernel_last);
+        if (p.epi == CEK_NORM) {
             const int rpb = 256 / (b.Co / 8);
             conv_splitk_epi_norm_kernel<T><<<FM_CEIL(b.Lq, rpb), 256, 0, s>>>(b);
             continue;
@@ -859,6 +902,13 @@ template <typename T> void launch_conv_epi(hipStream_t s, const ConvArgs<T>& b) 
 
 template <typename T> void launch_conv_gemm(hipStream_t s, const ConvArgs<T>& a0) {
     ConvArgs<T> a = a0;
+    // a lane's 8-element k chunk lies inside one tap; rows [lo, Lx) are read, clamped to that range
+    FMCHECK(a.Ci >= 8 && a.Ci % 8 == 0 && a.ntaps >= 1 && a.ntaps <= 8 && a.Co >= 1 && a.Lq >= 1 && a.nphase >= 1 &&
+                a.lo <= 0 && a.Lx > a.lo,
+            "conv: Ci a multiple of 8, 1..8 taps, at least one output row and one input row, lo <= 0");
+    // x is read in 16-byte chunks of 8 (bf16) / 4 (fp32) channels
+    FMCHECK(a.x && ((uintptr_t)a.x & 15) == 0 && a.ldx >= a.Ci && a.ldx % 8 == 0,
+            "conv: x 16-byte aligned, rows of ldx >= Ci elements, ldx a multiple of 8");
     a.shift0 = a.shift[0];
     a.shiftd = a.ntaps > 1 ? a.shift[1] - a.shift[0] : 0;
     for (int j = 0; j < a.ntaps; ++j) FMCHECK(a.shift[j] == a.shift0 + j * a.shiftd, "conv: tap shifts must be linear in the tap");
@@ -866,30 +916,15 @@ template <typename T> void launch_conv_gemm(hipStream_t s, const ConvArgs<T>& a0
     // the few narrow ones (encoder stem, 1-channel output conv) keep the register-only kernel
     // (measured per shape, 10 s decode: 442k x 96 k7 282 vs 292 us, 221k x 192 371 vs 452, 55k x 384
     // 348 vs 370, 6.9k x 768 192 vs 202; at 216-864 rows the LDS tile leaves too few blocks and loses)
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec_ok = !(a.flags & CE_F32OUT) && al16(a.out) && al16(a.out2) && al16(a.res) && a.ldo % 8 == 0 &&
-                        a.ldo2 % 8 == 0 && a.ldr % 8 == 0;  // the coalesced epilogue's 16-B accesses
-    if (a.ksplit > 1 && a.slab && vec_ok && a.Co % 8 == 0) {
-        conv_splitk_go<T>(s, a);
+    const ConvPlan p = conv_plan(a);
+    if (p.epi != CEK_GEMM) {
+        conv_splitk_go<T>(s, a, p);
         return;
     }
     FMCHECK(!(a.flags & (CE_SWIGLU | CE_ROPE | CE_NORM)), "conv: the SwiGLU / RoPE / norm epilogues run on the split-K path only");
-    // LDS tiles once they give the chip >= 256 blocks (the 128-row tile, 96-128 channels)
-    const long long cg2_blocks = (long long)FM_CEIL(a.Lq, CG2_BM) * FM_CEIL(a.Co, 128) * a.nphase;
-    if (fm_tuning().conv2 && vec_ok && a.Ci % 8 == 0 && a.Ci >= 32 && a.Co % 16 == 0 && a.Co >= 96 &&
-        (a.Lq >= 4096 || cg2_blocks >= 256)) {
-        ConvArgs<T> b = a;
-        b.ksplit = 1;
-        if (b.Co % 128 == 0 || b.Co >= 384)
-            conv2_go<T, 8>(s, b);
-        else
-            conv2_go<T, 6>(s, b);
-        return;
-    }
     ConvArgs<T> b = a;
     b.ksplit = 1;
-    dim3 g(FM_CEIL(a.Lq, 64), FM_CEIL(a.Co, 64), a.nphase);
-    conv_gemm_kernel<T><<<g, 256, 0, s>>>(b);
+    conv_go<T>(s, b, p.kernel);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1163,15 +1198,18 @@ void launch_rvq_decode(hipStream_t s, const int32_t* codes, int Tn, int nq1, int
 template <typename T>
 void launch_dwconv_ln(hipStream_t s, const T* x, int L, int D, const T* dw, const T* db, const T* lw,
                       const T* lb, T* y, int lo) {
+    FMCHECK(D >= 1 && D <= 2048 && L >= 1 && lo <= 0, "dwconv + LayerNorm: 1 <= D <= 2048 (8 values per thread), lo <= 0");
     dwconv_ln_kernel<T><<<L, 256, 0, s>>>(x, L, D, dw, db, lw, lb, y, lo);
 }
 template <typename T>
 void launch_rope_qk(hipStream_t s, T* qkv, int Tn, int H, int hd, const float* tab, int pos0) {
+    FMCHECK(hd >= 2 && hd % 2 == 0 && pos0 >= 0, "rope: an even head_dim, pos0 >= 0");
     rope_qk_kernel<T><<<Tn, 256, 0, s>>>(qkv, Tn, H, hd, tab, pos0);
 }
 template <typename T>
 void launch_window_attn(hipStream_t s, const T* qkv, int Tn, int H, int hd, int window, T* out, int npre) {
-    FMCHECK(hd <= 64 && window <= 512, "window attention: head_dim <= 64, window <= 512");
+    FMCHECK(hd >= 8 && hd <= 64 && hd % 8 == 0 && window >= 1 && window <= 512 && npre >= 0,
+            "window attention: head_dim a multiple of 8 up to 64, 1 <= window <= 512");
     if (window <= 128)
         window_attn_kernel<T, 2><<<dim3(Tn, H), 64, 0, s>>>(qkv, Tn, H, hd, window, out, npre);
     else
@@ -1199,6 +1237,7 @@ void launch_conv_weight(hipStream_t s, const float* w, int kind, int Ci, int Co,
 
 #define CINST(T)                                                                                     \
     template void launch_conv_gemm<T>(hipStream_t, const ConvArgs<T>&);                              \
+    template ConvPlan conv_plan<T>(const ConvArgs<T>&);                                              \
     template void launch_conv_epi<T>(hipStream_t, const ConvArgs<T>&);                               \
     template void launch_silu_mul<T>(hipStream_t, const T*, T*, size_t);                             \
     template void launch_rvq_decode<T>(hipStream_t, const int32_t*, int, int, int, int, int,         \

@@ -36,70 +36,12 @@
 #include <vector>
 
 #include "fm_kernels.h"
+#include "fm_ops_util.h"
 #include "fm_runtime.h"
 
+using namespace fm_ops_util;
+
 namespace {
-
-// Every fill, copy and launch of a hook goes to the hook's own non-blocking stream, in order. (A
-// non-blocking stream does not wait for the null stream, so a null-stream hipMemset of a buffer
-// could land after a kernel on `s` has written it.)
-struct DevBufs {
-    hipStream_t s;
-    std::vector<void*> ptrs;
-    explicit DevBufs(hipStream_t st) : s(st) {}
-    ~DevBufs() {
-        (void)hipStreamSynchronize(s);
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-    void* alloc(size_t bytes) {
-        void* p = nullptr;
-        HIPCHK(hipMalloc(&p, bytes ? bytes : 16));
-        HIPCHK(hipMemsetAsync(p, 0, bytes ? bytes : 16, s));
-        ptrs.push_back(p);
-        return p;
-    }
-    void put(void* d, const void* h, size_t bytes) {
-        HIPCHK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));  // the host array may be a temporary
-    }
-    // fp32 host -> device storage type T
-    template <typename T> T* upload(const float* h, size_t n) {
-        float* tmp = (float*)alloc(n * 4);
-        put(tmp, h, n * 4);
-        T* d = (T*)alloc(n * sizeof(T));
-        launch_convert<T>(s, tmp, 0, (int64_t)n, d);
-        HIPCHK(hipGetLastError());
-        return d;
-    }
-};
-
-template <typename T> void download(const T* d, size_t n, float* out, hipStream_t s) {
-    std::vector<T> h(n);
-    HIPCHK(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    for (size_t i = 0; i < n; ++i) {
-        if constexpr (sizeof(T) == 2) {
-            const uint32_t u = (uint32_t)h[i] << 16;
-            memcpy(&out[i], &u, 4);
-        } else {
-            out[i] = h[i];
-        }
-    }
-}
-
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    explicit StreamGuard(int device) {
-        int n = 0;
-        FMCHECK(hipGetDeviceCount(&n) == hipSuccess && n > 0, "no HIP device visible");
-        FMCHECK(device >= 0 && device < n, "bad device index");
-        HIPCHK(hipSetDevice(device));
-        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    }
-    ~StreamGuard() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-};
 
 template <typename T>
 void rmsnorm_t(hipStream_t s, int mode, const float* x, const float* w, int R, int d, float eps, float* y) {
@@ -314,16 +256,6 @@ void embed_t(hipStream_t s, const int32_t* tok, int R, const float* emb, int V, 
 }
 
 // ---- linear hooks (fm_op_linear .. fm_op_prompt_skinny) -----------------------------------------
-// A caller output array, in/out: uploaded before the launches (the caller's sentinel fill lands in
-// the padding columns and rows the kernel must not touch) and downloaded after them.
-template <typename T> struct InOut {
-    T* d;
-    float* h;
-    size_t n;
-    InOut(DevBufs& b, float* host, size_t count) : d(b.upload<T>(host, count)), h(host), n(count) {}
-    void get(hipStream_t s) { download<T>(d, n, h, s); }
-};
-
 int count_nonzero(const int* d, size_t n, hipStream_t s) {
     std::vector<int> h(n);
     HIPCHK(hipMemcpyAsync(h.data(), d, n * 4, hipMemcpyDeviceToHost, s));

@@ -33,6 +33,8 @@ ABI_SYMBOLS = [
     "fm_op_linear", "fm_op_gemv", "fm_op_rowgemv", "fm_op_rowgemv_pair", "fm_op_bstream", "fm_op_finalize_norm", "fm_op_prompt_skinny", "fm_op_sample",
     "fm_llm_prefix_save", "fm_llm_prefix_load", "fm_llm_prefix_drop", "fm_llm_prefix_info", "fm_llm_prefill_batch_at",
     "fm_llm_set_quant_compact", "fm_llm_memory_info", "fm_op_linear_q",
+    "fm_op_codec_conv", "fm_op_codec_resunit", "fm_op_codec_window_attn", "fm_op_codec_rope_qk", "fm_op_codec_dwconv_ln",
+    "fm_op_codec_rvq_decode", "fm_op_codec_snake", "fm_op_codec_silu_mul", "fm_op_codec_wn_fold", "fm_op_codec_vq_encode",
 ]
 
 
@@ -64,6 +66,15 @@ def tree_source_hash() -> str:
 class SamplingC(ctypes.Structure):
     _fields_ = [("temperature", ctypes.c_float), ("top_p", ctypes.c_float),
                 ("top_k", ctypes.c_int), ("seed", ctypes.c_uint64), ("mask_im_end", ctypes.c_int)]
+
+
+class CodecConvDesc(ctypes.Structure):
+    """fm_codec_conv_desc (include/fishmi.h)"""
+    _fields_ = [(n, ctypes.c_int) for n in
+                "precision kind Ci Co k stride dil strided npre Lx ldx Lq flags ksplit slab_rows rope_pos0 rope_nqk "
+                "rope_hd".split()] + \
+               [("rope_base", ctypes.c_float), ("norm_eps", ctypes.c_float)] + \
+               [(n, ctypes.c_int) for n in "ldo out_rows ldr res_rows ldo2 out2_rows reps".split()]
 
 
 def lib():
@@ -178,6 +189,19 @@ def lib():
     L.fm_op_sample.argtypes = [i32, i32, i32, pf32, i32, i32, i32, pi32, i32, pf32, pf32, pi32, pi32,
                                ctypes.POINTER(ctypes.c_uint64), pi32, pi32, i32, i32, i32, i32, i32, i32, pi32, i32,
                                pi32, pi32, i32, pf32, i32, pi32]
+    L.fm_op_codec_conv.argtypes = [i32, ctypes.POINTER(CodecConvDesc), pf32, pf32, pf32, pf32, pf32, pf32, pf32, pf32, pf32,
+                                   pi32, pi32]
+    L.fm_op_codec_resunit.argtypes = [i32, i32, i32, i32, i32, pf32, pf32, pf32, pf32, pf32, pf32, pf32, pf32, i32, i32,
+                                      pf32, i32, i32, pi32, pi32]
+    L.fm_op_codec_window_attn.argtypes = [i32, i32, pf32, i32, i32, i32, i32, i32, pf32, i32, i32, pi32]
+    L.fm_op_codec_rope_qk.argtypes = [i32, i32, pf32, i32, i32, i32, i32, f32, i32, i32, pi32]
+    L.fm_op_codec_dwconv_ln.argtypes = [i32, i32, pf32, i32, i32, i32, pf32, pf32, pf32, pf32, pf32, i32, i32, pi32]
+    L.fm_op_codec_rvq_decode.argtypes = [i32, i32, pi32, i32, i32, i32, i32, i32, pf32, pf32, pf32, pf32, i32, pf32, i32,
+                                         i32, pi32]
+    L.fm_op_codec_snake.argtypes = [i32, i32, pf32, i32, i64, pf32, pf32, i64, pf32, i32, pi32]
+    L.fm_op_codec_silu_mul.argtypes = [i32, i32, pf32, pf32, i64, i64, i32, pi32]
+    L.fm_op_codec_wn_fold.argtypes = [i32, pf32, pf32, i32, i32, pf32, i64, i32, pi32]
+    L.fm_op_codec_vq_encode.argtypes = [i32, pf32, i32, i32, i32, i32, pf32, pf32, pf32, pi32, pf32, pf32, pi32, i32, pi32]
     if hasattr(L, "fm_codec_open"):
         L.fm_codec_open.argtypes = [vp, i32, i32, i32, ctypes.POINTER(vp)]
         L.fm_codec_set_tensor.argtypes = [vp, ctypes.c_char_p, vp, i32, i64]

@@ -429,3 +429,141 @@ def sample(logits, Nl, row_slot, slots, cols, tap, slow, sb, se, im_end, cb, dra
                                            int(bool(ras_enable)), i32p(force_cols), i32p(cols), ldc, _p(tap),
                                            tap.shape[1], i32p(kernel)))
     return int(kernel[0])
+
+
+# ---- the codec kernels (fm_op_codec_*; tests/test_gpu_codec_ops.py) -----------------------------------
+# conv_gemm epilogue flags (FM_CE_* of include/fishmi.h; bias and the Snake follow the operands)
+CE_GELU, CE_RES, CE_GAMMA, CE_STORE, CE_TANH, CE_F32OUT, CE_SWIGLU, CE_ROPE, CE_NORM = 2, 4, 8, 16, 64, 128, 256, 512, 1024
+CONV_KERNELS = ("conv_gemm", "conv_gemm2<6>", "conv_gemm2<8>")
+CONV_EPILOGUES = ("gemm", "splitk_epi", "splitk_epi_norm")
+
+
+def codec_conv(w, x, Lq, kind=0, stride=1, dil=1, strided=False, npre=0, flags=CE_STORE, bias=None, gamma=None,
+               res=None, alpha2=None, normw=None, out=None, out2=None, ksplit=0, slab_rows=0, rope=None, norm_eps=1e-5,
+               precision="bf16", reps=1, device=0):
+    """fm_op_codec_conv: launch_conv_weight + launch_pack + launch_conv_gemm on w in torch layout (kind 0
+    Conv1d [Co][Ci][k], 1 / 2 ConvTranspose1d [Ci][Co][2s] / [Ci][Co][s], 3 Linear [Co][Ci]) and x
+    [npre + Lx][ldx]; out / out2 are filled in place.  rope = (pos0, nqk, hd, base) with CE_ROPE.
+    Returns ({kernel, ksplit, segments, epilogue, changed, kernel_last}, dirty); kernel_last is the kernel of a
+    shorter last row segment."""
+    w, x, bias, gamma, res, alpha2, normw = _f(w), _f(x), _f(bias), _f(gamma), _f(res), _f(alpha2), _f(normw)
+    d = native.CodecConvDesc()
+    d.precision, d.kind, d.stride, d.dil, d.strided = _prec(precision), int(kind), int(stride), int(dil), int(bool(strided))
+    if kind in (1, 2):
+        d.Ci, d.Co, d.k = w.shape
+    elif kind == 0:
+        d.Co, d.Ci, d.k = w.shape
+    else:
+        (d.Co, d.Ci), d.k = w.shape, 1
+    d.npre, d.Lx, d.ldx, d.Lq = int(npre), x.shape[0] - int(npre), x.shape[1], int(Lq)
+    d.flags, d.ksplit, d.slab_rows, d.reps, d.norm_eps = int(flags), int(ksplit), int(slab_rows), int(reps), float(norm_eps)
+    if rope is not None:
+        d.rope_pos0, d.rope_nqk, d.rope_hd, d.rope_base = int(rope[0]), int(rope[1]), int(rope[2]), float(rope[3])
+    if out is not None:
+        d.out_rows, d.ldo = _out(out).shape
+    if out2 is not None:
+        d.out2_rows, d.ldo2 = _out(out2).shape
+    if res is not None:
+        d.res_rows, d.ldr = res.shape
+    plan, dirty = np.zeros(6, np.int32), np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_codec_conv(device, ctypes.byref(d), _p(w), _p(bias), _p(x), _p(gamma), _p(res),
+                                               _p(alpha2), _p(normw), _p(out), _p(out2), native.i32p(plan),
+                                               native.i32p(dirty)))
+    return dict(kernel=CONV_KERNELS[plan[0]], ksplit=int(plan[1]), segments=int(plan[2]),
+                epilogue=CONV_EPILOGUES[plan[3]], changed=int(plan[4]), kernel_last=CONV_KERNELS[plan[5]]), int(dirty[0])
+
+
+def codec_resunit(x, L, dil, w7, b7, a2, w1, b1, an, res, out2, npre=0, store_res=True, reps=1, device=0):
+    """fm_op_codec_resunit: launch_resunit (bf16) on x [npre + L][C]; res and out2 are filled in place.
+    Returns (taken, changed)."""
+    x, w7, b7, a2, w1, b1, an = _f(x), _f(w7), _f(b7), _f(a2), _f(w1), _f(b1), _f(an)
+    C = x.shape[1]
+    taken, changed = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    native.check(native.lib().fm_op_codec_resunit(device, C, int(L), int(npre), int(dil), _p(x), _p(w7), _p(b7), _p(a2),
+                                                  _p(w1), _p(b1), _p(an), _p(_out(res)), res.shape[0], int(store_res),
+                                                  _p(_out(out2)), out2.shape[0], int(reps), native.i32p(taken),
+                                                  native.i32p(changed)))
+    return bool(taken[0]), int(changed[0])
+
+
+def _reps(call, reps):
+    """the trailing (reps, changed) of a codec hook -> the output words a repeated launch changed"""
+    changed = np.zeros(1, np.int32)
+    native.check(call(int(reps), native.i32p(changed)))
+    return int(changed[0])
+
+
+def codec_window_attn(qkv, Tn, H, hd, window, out, npre=0, precision="bf16", reps=1, device=0):
+    """fm_op_codec_window_attn: qkv [npre + Tn][3 H hd], out [rows >= Tn][H hd] filled in place.  This and the hooks
+    below return the number of output words a repeated launch (reps > 1) on the same scratch changed."""
+    qkv = _f(qkv)
+    L = native.lib()
+    return _reps(lambda *r: L.fm_op_codec_window_attn(device, _prec(precision), _p(qkv), int(Tn), int(H), int(hd), int(window),
+                                                      int(npre), _p(_out(out)), out.shape[0], *r), reps)
+
+
+def codec_rope_qk(qkv, Tn, H, hd, base, pos0=0, precision="bf16", reps=1, device=0):
+    """fm_op_codec_rope_qk in place on qkv [rows >= Tn][3 H hd]"""
+    L = native.lib()
+    return _reps(lambda *r: L.fm_op_codec_rope_qk(device, _prec(precision), _p(_out(qkv)), qkv.shape[0], int(Tn), int(H), int(hd),
+                                                  float(base), int(pos0), *r), reps)
+
+
+def codec_dwconv_ln(x, L, dw, db, lw, lb, y, npre=0, precision="bf16", reps=1, device=0):
+    """fm_op_codec_dwconv_ln: x [npre + L][D], y [rows >= L][D] filled in place"""
+    x, dw, db, lw, lb = _f(x), _f(dw), _f(db), _f(lw), _f(lb)
+    lib = native.lib()
+    return _reps(lambda *r: lib.fm_op_codec_dwconv_ln(device, _prec(precision), _p(x), int(L), x.shape[1], int(npre), _p(dw),
+                                                      _p(db), _p(lw), _p(lb), _p(_out(y)), y.shape[0], *r), reps)
+
+
+def codec_rvq_decode(codes, cb_sem, cb, w, bias, z, precision="bf16", reps=1, device=0):
+    """fm_op_codec_rvq_decode: codes [nq1][Tn], cb_sem [sem][cd], cb [nq1 - 1][cbs][cd], w [nq1][D][cd], bias
+    [nq1][D]; z [rows >= Tn][D] filled in place"""
+    codes = np.ascontiguousarray(codes, np.int32)
+    cb_sem, cb, w, bias = _f(cb_sem), _f(cb), _f(w), _f(bias)
+    nq1, Tn = codes.shape
+    L = native.lib()
+    return _reps(lambda *r: L.fm_op_codec_rvq_decode(device, _prec(precision), native.i32p(codes), Tn, nq1, cb_sem.shape[0],
+                                                     cb.shape[1], cb_sem.shape[1], _p(cb_sem), _p(cb), _p(w), _p(bias),
+                                                     w.shape[1], _p(_out(z)), z.shape[0], *r), reps)
+
+
+def codec_snake(x, alpha, y, precision="bf16", reps=1, device=0):
+    """fm_op_codec_snake: y[:x.size] = snake(x [L][C], alpha [C]) in place; returns (the fp32 reciprocals [C],
+    changed)"""
+    x, alpha = _f(x), _f(alpha)
+    ia = np.zeros(alpha.size, np.float32)
+    L = native.lib()
+    changed = _reps(lambda *r: L.fm_op_codec_snake(device, _prec(precision), _p(x), alpha.size, x.size, _p(alpha), _p(_out(y)),
+                                                   y.size, _p(ia), *r), reps)
+    return ia, changed
+
+
+def codec_silu_mul(g, y, precision="bf16", reps=1, device=0):
+    """fm_op_codec_silu_mul: y[:g.size] = round(silu(g)) * y in place"""
+    g = _f(g)
+    L = native.lib()
+    return _reps(lambda *r: L.fm_op_codec_silu_mul(device, _prec(precision), _p(g), _p(_out(y)), g.size, y.size, *r), reps)
+
+
+def codec_wn_fold(g, v, w, reps=1, device=0):
+    """fm_op_codec_wn_fold: w[:rows * per] = v [rows][per] * g / ||v|| in place"""
+    g, v = _f(g), _f(v)
+    L = native.lib()
+    return _reps(lambda *r: L.fm_op_codec_wn_fold(device, _p(g), _p(v), v.shape[0], v.shape[1], _p(_out(w)), w.size, *r), reps)
+
+
+def codec_vq_encode(r, wi, bi, cbs, wo, bo, reps=1, device=0):
+    """fm_op_codec_vq_encode: r [Tn][D] updated in place; wi [nst][cd][D], bi [nst][cd], cbs a list of
+    [cbn][cd] codebooks, wo [nst][D][cd], bo [nst][D].  Returns (the codes [nst][Tn], changed)."""
+    wi, bi, wo, bo = _f(wi), _f(bi), _f(wo), _f(bo)
+    nst, cd, D = wi.shape
+    cb = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32) for c in cbs], 0), np.float32)
+    cbn = np.array([len(c) for c in cbs], np.int32)
+    Tn = r.shape[0]
+    codes = np.zeros((nst, Tn), np.int32)
+    L = native.lib()
+    changed = _reps(lambda *a: L.fm_op_codec_vq_encode(device, _p(_out(r)), Tn, D, nst, cd, _p(wi), _p(bi), _p(cb),
+                                                       native.i32p(cbn), _p(wo), _p(bo), native.i32p(codes), *a), reps)
+    return codes, changed

@@ -445,6 +445,86 @@ int fm_op_batched_linear_q4(int device, const float* w, int N, int K, int gs, co
    out [seq_len][head_dim/2][2], bf16-valued floats.  No device needed. */
 int fm_rope_table(int seq_len, int head_dim, float base, float* out);
 
+/* ---- codec per-op hooks (tests/test_gpu_codec_ops.py): one production launcher of the codec kernels
+   on caller operands, prepared by the functions the model itself calls.  fp32 host arrays converted to
+   the precision's storage type; every output array is in/out, so what the kernel leaves alone comes
+   back as the caller filled it; FM_ERR_ARG for a shape a launcher refuses.  reps (1..8) launches run on the
+   same scratch (an in-place kernel gets the caller's values again before each); changed = the output words
+   a later launch left different from the first one's. */
+/* conv_gemm epilogue flags of fm_codec_conv_desc.flags (bias and the Snake follow the operands) */
+#define FM_CE_GELU 2
+#define FM_CE_RES 4
+#define FM_CE_GAMMA 8
+#define FM_CE_STORE 16
+#define FM_CE_TANH 64
+#define FM_CE_F32OUT 128
+#define FM_CE_SWIGLU 256 /* split-K only: out [.][Co / 2] over w = [W1 rows | W3 rows] */
+#define FM_CE_ROPE 512   /* split-K only: RoPE on channels [0, rope_nqk) at position t + rope_pos0 */
+#define FM_CE_NORM 1024  /* split-K only: out2 = RMSNorm(y) with weight normw */
+typedef struct fm_codec_conv_desc {
+    int precision;
+    /* the layer: w in torch layout per kind -- 0 Conv1d [Co][Ci][k] (dilation dil), 1 ConvTranspose1d
+       [Ci][Co][2 stride], 2 ConvTranspose1d [Ci][Co][stride], 3 Linear [Co][Ci].  strided != 0: a Conv1d
+       with k = 2 stride run as the encoder runs it, two taps over the [L / stride][stride * Ci] view of x
+       (x, Lx, Lq, npre and ldx then describe that view) */
+    int kind, Ci, Co, k, stride, dil, strided;
+    int npre, Lx, ldx, Lq; /* x [npre + Lx][ldx]: npre carried context rows (lo = -npre), then rows [0, Lx) */
+    int flags;
+    int ksplit;    /* 0: the split-K factor the model gives such a layer; >= 1: forced */
+    int slab_rows; /* 0: a split-K workspace for all Lq rows; else for this many (rows run in segments) */
+    int rope_pos0, rope_nqk, rope_hd;
+    float rope_base, norm_eps;
+    int ldo, out_rows, ldr, res_rows, ldo2, out2_rows;
+    int reps; /* launches on the same scratch */
+} fm_codec_conv_desc;
+/* launch_conv_weight + launch_pack + launch_conv_gemm.  out [out_rows][ldo] (with FM_CE_STORE; fp32
+   words with FM_CE_F32OUT), out2 [out2_rows][ldo2] (the Snake with alpha2, or the norm with
+   FM_CE_NORM), res [res_rows][ldr]; output row = t * stride + phase for the transposed kinds.  The
+   split-K workspace has guard words behind it: dirty = any of them changed.  plan: kernel (0
+   conv_gemm, 1 conv_gemm2<6>, 2 conv_gemm2<8>), K slices, row segments, epilogue kernel (0 in the
+   GEMM, 1 conv_splitk_epi, 2 conv_splitk_epi_norm), output words a repeated launch changed, the kernel of
+   a shorter last row segment (it has a smaller grid; the same as kernel otherwise).  plan [6]. */
+int fm_op_codec_conv(int device, const fm_codec_conv_desc* d, const float* w, const float* bias, const float* x,
+                     const float* gamma, const float* res, const float* alpha2, const float* normw, float* out,
+                     float* out2, int* plan, int* dirty);
+/* launch_resunit (bf16): x [npre + L][C] (the Snake of the unit input), k7 / k1 weights [C][C][7] /
+   [C][C][1] and biases, the alphas of the inner Snake (a2) and of the output Snake (an), res
+   [res_rows][C] in/out (written when store_res), out2 [out2_rows][C].  taken = 0: shape not covered
+   (nothing ran); changed = output words a repeated launch changed. */
+int fm_op_codec_resunit(int device, int C, int L, int npre, int dil, const float* x, const float* w7, const float* b7,
+                        const float* a2, const float* w1, const float* b1, const float* an, float* res, int res_rows,
+                        int store_res, float* out2, int out2_rows, int reps, int* taken, int* changed);
+/* launch_window_attn: qkv [npre + Tn][3 H hd] (post-RoPE; npre carried rows), out [out_rows][H hd] */
+int fm_op_codec_window_attn(int device, int precision, const float* qkv, int Tn, int H, int hd, int window, int npre,
+                            float* out, int out_rows, int reps, int* changed);
+/* launch_rope_qk in place on qkv [rows >= Tn][3 H hd], row t at position pos0 + t of fm_rope_table */
+int fm_op_codec_rope_qk(int device, int precision, float* qkv, int rows, int Tn, int H, int hd, float base, int pos0,
+                        int reps, int* changed);
+/* launch_dwconv_ln: x [npre + L][D], depthwise weight [D][7] and bias, LayerNorm weight and bias, y [y_rows][D] */
+int fm_op_codec_dwconv_ln(int device, int precision, const float* x, int L, int D, int npre, const float* dw,
+                          const float* db, const float* lw, const float* lb, float* y, int y_rows, int reps, int* changed);
+/* launch_rvq_decode: codes [nq1][Tn] (>= 0), semantic codebook [sem][cd], residual codebooks
+   [nq1 - 1][cbs][cd], folded out_proj w [nq1][D][cd] and bias [nq1][D], z [z_rows][D] */
+int fm_op_codec_rvq_decode(int device, int precision, const int32_t* codes, int Tn, int nq1, int sem, int cbs, int cd,
+                           const float* cb_sem, const float* cb, const float* w, const float* bias, int D, float* z,
+                           int z_rows, int reps, int* changed);
+/* launch_snake_inv + launch_snake: y[i] = snake(x[i], alpha[i % C]) for i < n, y [y_len]; ialpha (may be
+   null) [C]: the fp32 reciprocals 1 / (alpha + 1e-9) */
+int fm_op_codec_snake(int device, int precision, const float* x, int C, int64_t n, const float* alpha, float* y,
+                      int64_t y_len, float* ialpha, int reps, int* changed);
+/* launch_silu_mul: y[i] = round(silu(g[i])) * y[i] for i < n, y [y_len] */
+int fm_op_codec_silu_mul(int device, int precision, const float* g, float* y, int64_t n, int64_t y_len, int reps,
+                         int* changed);
+/* launch_wn_fold (fp32): w[r][i] = v[r][i] * g[r] / ||v[r]||, w [w_len >= rows * per] */
+int fm_op_codec_wn_fold(int device, const float* g, const float* v, int rows, int per, float* w, int64_t w_len, int reps,
+                        int* changed);
+/* launch_vq_encode (fp32): r [Tn][D] in/out (the residual after the last stage), in_proj wi [nst][cd][D]
+   and bi [nst][cd], the codebooks back to back ([cbn[q]][cd] each), out_proj wo [nst][D][cd] and bo
+   [nst][D]; codes [nst][Tn] */
+int fm_op_codec_vq_encode(int device, float* r, int Tn, int D, int nst, int cd, const float* wi, const float* bi,
+                          const float* cb, const int32_t* cbn, const float* wo, const float* bo, int32_t* codes, int reps,
+                          int* changed);
+
 /* ---- codec (modded DAC decode side, modded_dac_vq.yaml shapes) --------------------- */
 typedef struct fm_codec_config {
     int latent, decoder_dim, n_codebooks, codebook_size, semantic_codebook_size, codebook_dim;
