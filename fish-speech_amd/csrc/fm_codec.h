@@ -54,6 +54,10 @@ template <typename T> struct ConvArgs {
     int rope_pos0 = 0, rope_nqk = 0, rope_hd = 0;
     const T* normw = nullptr;     // CE_NORM: the RMSNorm weight [Co] and eps
     float norm_eps = 0.f;
+    // split-K epilogue only (launch_conv_epi; CE_STORE with CE_BIAS / CE_RES, or CE_SWIGLU8): the row scales
+    // [Co] of a weight-only int8 LLM linear -- every channel is round(round(sum) * rscale[co]) before the
+    // bias (linear_epi).  Null for every codec call.
+    const T* rscale = nullptr;
 };
 
 // One decoder ResidualUnit (modded_dac.py:599-620) in one launch, bf16, C in {96, 192, 384}:

@@ -186,6 +186,16 @@ __global__ __launch_bounds__(256) void conv_splitk_epi_kernel(ConvArgs<T> a) {
         }
         if (half) {  // (no bias: the FeedForward linears have none)
             float o[8];
+            if (a.rscale) {  // weight-only int8: gate and up are round(round(sum) * scale of their row) first
+                float sg[8], su[8];
+                load8(a.rscale + co, sg);
+                load8(a.rscale + co + half, su);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    y[j] = rnd<T>(rnd<T>(y[j]) * sg[j]);
+                    u[j] = rnd<T>(rnd<T>(u[j]) * su[j]);
+                }
+            }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float g = rnd<T>(y[j]);
@@ -194,11 +204,13 @@ __global__ __launch_bounds__(256) void conv_splitk_epi_kernel(ConvArgs<T> a) {
             store8(reinterpret_cast<T*>(a.out) + ((size_t)t * a.stride + phase) * a.ldo + 8 * cc, o);
             continue;
         }
-        float b[8];
+        float b[8], rs[8];
         if (fl & CE_BIAS) load8(a.bias + co, b);
+        if (a.rscale) load8(a.rscale + co, rs);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             float v = y[j];
+            if (a.rscale) v = rnd<T>(rnd<T>(v) * rs[j]);  // weight-only int8 (linear_epi)
             if (fl & CE_BIAS) v += b[j];
             v = rnd<T>(v);
             if (fl & CE_GELU) v = rnd<T>(0.5f * v * (1.0f + erff(v * 0.70710678118654752f)));

@@ -488,6 +488,15 @@ struct PromptSkinnyArgs {
     // straight to act [R][lda] (swiglu_i8_kernel's roundings)
     bf16_t* act = nullptr;
     int lda = 0;
+    // weight-only int8 with act: the row scales of the packed (interleaved) rows [N]; gate and up are
+    // round(round(acc) * wscale[n]) before the SwiGLU (linear_epi's STORE, then swiglu_i8_kernel)
+    const bf16_t* wscale = nullptr;
+    // the code-reading forms: w is null and the kernel rebuilds every bf16 fragment, bit for bit, from the
+    // step-granular code copy right before its MFMAs -- q8s (launch_pack_q8s, Frag::dq8s), or q4s with sz
+    // (launch_pack_q4s / launch_pack_sz4, Frag::dq4s; K a multiple of 128)
+    const unsigned char* q8s = nullptr;
+    const uint32_t* q4s = nullptr;
+    const uint32_t* sz = nullptr;
 };
 void launch_prompt_skinny(hipStream_t s, const PromptSkinnyArgs& a, int ks);
 // K slices: the smallest divisor of K/32 with >= 8 k-steps per slice giving >= target blocks of 64

@@ -38,13 +38,40 @@ template <typename T> struct Run {
     }
     explicit Run(fm_llm* mm) : m(mm), s(mm->stream), E(sizeof(T)) {}
 
+    // Which weight form the skinny prompt GEMM streams for W (fm_tune prompt_skinny_q): 0 the packed bf16 fragments,
+    // 1 the step-granular int8 codes, 2 the int4 codes with their (scale, zero) table; -1: none (a quantised linear
+    // at R > 64, in fp32, under prompt_skinny_q 2, or a compact one whose codes have no step-granular copy), and
+    // the caller's fallback reaches linear().  A handle with both prefers the codes under 1, its bf16 copy under 0;
+    // a compact handle has only the codes.
+    int skinny_form(const Linear& W, int R, int K) const {
+        if (!W.q8) return 0;
+        if (sizeof(T) != 2 || R > 64 || fm_tuning().prompt_skinny_q == 2) return -1;
+        const int codes = W.sz ? ((W.q4s && K % 128 == 0) ? 2 : 0) : (W.q8s ? 1 : 0);
+        if (codes && (!W.frag || fm_tuning().prompt_skinny_q == 1)) return codes;
+        return W.frag ? 0 : -1;
+    }
+    // the skinny GEMM's weight operand of that form
+    void skinny_weight(PromptSkinnyArgs& p, const Linear& W, int form) const {
+        if (form == 2) {
+            FMCHECK(W.q4s && W.sz, "prompt skinny GEMM: int4 linear without its step-granular codes");
+            p.q4s = W.q4s;
+            p.sz = W.sz;
+        } else if (form == 1) {
+            FMCHECK(W.q8s, "prompt skinny GEMM: int8 linear without its step-granular codes");
+            p.q8s = W.q8s;
+        } else {
+            FMCHECK(W.frag, "prompt skinny GEMM: linear without its bf16 fragments");
+            p.w = (const bf16_t*)W.frag;
+        }
+    }
     // Prompt chunks (R > 32 rows): a linear is a GEMM, not a weight stream, so it runs on the codec's
     // LDS-tiled implicit-GEMM kernels as a one-tap conv (conv_gemm2_kernel: 128-row x 96-128-column
     // tiles, or the 64 x 64 register tiles with split-K when the grid would not fill the chip).
     // The packed weight layout is the same; epilogues: round(acc + bias) and round(res + round(acc)).
     bool prompt_gemm(const Linear& W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
                      const void* res, int ldr, int epi, const char* cls) {
-        if (R <= 32 || W.q8 || !fm_tuning().prompt_gemm ||
+        const int form = skinny_form(W, R, K);
+        if (R <= 32 || form < 0 || !fm_tuning().prompt_gemm ||
             (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU8) || N % 16 || K % 32 || N < 96 ||
             (epi == EPI_SWIGLU8 && (bias || N % 16)))
             return false;
@@ -66,8 +93,9 @@ template <typename T> struct Run {
         c.ldo = ldy;
         c.flags = CE_STORE | (bias ? CE_BIAS : 0) | (epi == EPI_RESID ? CE_RES : 0) |
                   (epi == EPI_SWIGLU8 ? CE_SWIGLU8 : 0);  // SWIGLU8: Y = act [R][N/2], ldy = N/2
+        c.rscale = W.q8 ? (const T*)W.scale : nullptr;  // weight-only int8: round(round(sum) * scale) in the split-K epilogue
         hipStream_t st = s;
-        const int64_t bytes = (int64_t)N * K * E + (int64_t)R * K * E + (int64_t)R * N * E;
+        const int64_t bytes = step_wbytes(form, N, K, E) + (int64_t)R * K * E + (int64_t)R * N * E;
         const double flops = 2.0 * R * N * K;
         if constexpr (sizeof(T) == 2) {
             // R <= 64: one weight pass for all rows (fm_prompt.hip), K slices finished by the conv
@@ -79,21 +107,25 @@ template <typename T> struct Run {
                 c.ksplit = ks;
                 c.slab = m->skpart;
                 c.slab_cap = (size_t)m->skpart_cap;
-                PromptSkinnyArgs p{(const bf16_t*)W.frag, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+                PromptSkinnyArgs p{nullptr, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+                skinny_weight(p, W, form);
                 const bool direct = ks == 1 && epi == EPI_SWIGLU8;  // the kernel stores act itself
                 if (direct) {
                     p.act = (bf16_t*)Y;
                     p.lda = ldy;
+                    p.wscale = (const bf16_t*)c.rscale;
                 }
                 auto go = [st, c, p, ks, direct] {
                     launch_prompt_skinny(st, p, ks);
                     if (!direct) launch_conv_epi<T>(st, c);
                 };
                 launch(cls, bytes, flops, go);
+                if (form) m->prof.note("prompt_q", bytes);  // the code-streaming launches, counted apart as well
                 return true;
             }
         }
-        if (epi == EPI_SWIGLU8) return false;  // the conv GEMMs' own epilogues have no interleaved SwiGLU
+        // (a quantised linear has the skinny path alone: the conv GEMMs stage bf16 fragments and know no row scale)
+        if (epi == EPI_SWIGLU8 || W.q8) return false;  // the conv GEMMs' own epilogues have no interleaved SwiGLU
         // split K (fp32 slabs + the conv split-K epilogue) until the 128 x 128 tiles number >=
         // prompt_ks_tiles (default 384)
         const long long t128 = (long long)FM_CEIL(R, 128) * FM_CEIL(N, 128);
@@ -110,20 +142,25 @@ template <typename T> struct Run {
     // A prompt chunk's wo / w2 (32 < R <= 64, bf16) as raw K-slice partials in m->skpart ([ks][R][N], the
     // finalize_norm slab layout): the residual add, the bias and the next RMSNorm then run in one
     // finalize_norm launch instead of the split-K epilogue + an RMSNorm launch.  false: not eligible.
-    bool prompt_slab(const Linear& W, const void* X, int ldx, int R, int N, int K, int* ks_out) {
+    // A weight-only int8 linear's row scales apply where the slabs' sum is rounded: scaled says the caller's
+    // finisher takes them (finalize_norm's wscale); qk_rope_cache_kernel does not, so an int8 wqkv declines.
+    bool prompt_slab(const Linear& W, const void* X, int ldx, int R, int N, int K, int* ks_out, bool scaled) {
         if constexpr (sizeof(T) != 2) {
             return false;
         } else {
+            const int form = skinny_form(W, R, K);
             if (!fm_tuning().prompt_fin || !fm_tuning().prompt_skinny || !fm_tuning().prompt_gemm || R <= 32 ||
-                R > 64 || W.q8 || N % 16 || K % 32 || ldx % 8 || ((uintptr_t)X & 15))
+                R > 64 || form < 0 || (W.scale && W.q8 && !scaled) || N % 16 || K % 32 || ldx % 8 || ((uintptr_t)X & 15))
                 return false;
             const int ks = prompt_skinny_ks(N, K, fm_tuning().prompt_skinny_blocks);
             if (ks <= 0 || (long long)ks * R * N > m->skpart_cap) return false;
-            const PromptSkinnyArgs p{(const bf16_t*)W.frag, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+            PromptSkinnyArgs p{nullptr, (const bf16_t*)X, ldx, R, N, K, m->skpart};
+            skinny_weight(p, W, form);
             hipStream_t st = s;
             auto go = [st, p, ks] { launch_prompt_skinny(st, p, ks); };
-            const int64_t bytes = (int64_t)N * K * E + (int64_t)R * K * E + (int64_t)ks * R * N * 4;
+            const int64_t bytes = step_wbytes(form, N, K, E) + (int64_t)R * K * E + (int64_t)ks * R * N * 4;
             launch("linear", bytes, 2.0 * R * N * K, go);
+            if (form) m->prof.note("prompt_q", bytes);
             *ks_out = ks;
             return true;
         }
@@ -339,7 +376,7 @@ template <typename T> struct Run {
             }
             if (bs_linear(L.wqkv, L.bqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, m->qkv, d.nqkv(), nullptr, EPI_STORE)) return;
         } else if (!b.is_fast && !rows_distinct_slots && fm_tuning().prompt_qkv_slab &&
-                   prompt_slab(L.wqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, &kp)) {
+                   prompt_slab(L.wqkv, b.xnb, d.dim, R, d.nqkv(), d.dim, &kp, false)) {
             // a prompt chunk's QKV as K-slice slabs, summed by qk_rope_cache_kernel itself (no epilogue launch)
             b.qslab = m->skpart;
             b.qslab_kp = kp;
@@ -428,8 +465,8 @@ template <typename T> struct Run {
                     "bsacc: no SLABFIN wo plan");
         } else if (b.bs && bs_linear(L.wo, nullptr, m->att, d.nq(), R, d.dim, d.nq(), nullptr, d.dim, m->bsA, EPI_SLAB, &kp)) {
             finalize_norm(m->bsA, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, L.wo.scale);
-        } else if (!b.bs && prompt_slab(L.wo, m->att, d.nq(), R, d.dim, d.nq(), &kp)) {
-            finalize_norm(m->skpart, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, nullptr);
+        } else if (!b.bs && prompt_slab(L.wo, m->att, d.nq(), R, d.dim, d.nq(), &kp, true)) {
+            finalize_norm(m->skpart, kp, L.bo, b.xb, b.hb, L.fn, b.xnb, d.dim, R, L.wo.scale);
         } else {
             linear(L.wo, L.bo, m->att, d.nq(), R, d.dim, d.nq(), b.hb, d.dim, b.xb, d.dim, nullptr,
                    EPI_RESID, "linear");
@@ -482,8 +519,8 @@ template <typename T> struct Run {
             x_ss = true;
         } else if (b.bs && bs_linear(L.w2, nullptr, m->act, d.inter, R, d.dim, d.inter, nullptr, d.dim, m->bsB, EPI_SLAB, &kp)) {
             set_pending(m->bsB, kp, d.dim, R, b.hb, b.xb, L.w2.scale);
-        } else if (!b.bs && prompt_slab(L.w2, m->act, d.inter, R, d.dim, d.inter, &kp)) {
-            set_pending(m->skpart, kp, d.dim, R, b.hb, b.xb, nullptr);
+        } else if (!b.bs && prompt_slab(L.w2, m->act, d.inter, R, d.dim, d.inter, &kp, true)) {
+            set_pending(m->skpart, kp, d.dim, R, b.hb, b.xb, L.w2.scale);
         } else {
             linear(L.w2, nullptr, m->act, d.inter, R, d.dim, d.inter, b.xb, d.dim, b.hb, d.dim, nullptr,
                    EPI_RESID, "linear");

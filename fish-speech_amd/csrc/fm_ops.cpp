@@ -22,6 +22,8 @@
 //                   launch_bstream on bstream_plan's geometry, launch_finalize_norm, launch_prompt_skinny): outputs
 //                   are in/out arrays with spare rows / columns, the launch can be repeated on the same scratch,
 //                   and the ticket words left non-zero are counted (tests/test_gpu_linear_ops.py)
+//   fm_op_prompt_skinny_q  launch_prompt_skinny on weight-only int8 / int4 codes and on their bf16 fragment
+//                   copy (fm_tune prompt_skinny_q; tests/test_gpu_prompt_skinny_q.py)
 //   fm_op_sample    the decode sampler (launch_sample_radix: sample_fast_kernel / sample_radix_kernel and
 //                   their shared wide path) once on caller logits rows, slot table, RAS window and
 //                   forced columns; cols and the tap are in/out (tests/test_gpu_sampler_ops.py)
@@ -1280,6 +1282,99 @@ int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int
         FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
         StreamGuard g(device);
         prompt_skinny_op(g.s, w, x, ldx, R, N, K, *ks, act, out, out_rows, ldo, reps);
+    });
+}
+
+// weight-only int8 / int4 on launch_prompt_skinny: the model's own device quantizer and pack launchers, then the
+// same launch on the packed bf16 fragments of the quantised weights (y_bf16) and on the kernel's code-reading
+// form -- the step-granular codes alone (y_q).  Outputs in/out like fm_op_prompt_skinny's; with act the int8
+// row scales apply in the SwiGLU (int4 has none: its fragments hold the dequantised values).
+int fm_op_prompt_skinny_q(int device, int quant, int gs, const float* w, const float* x, int ldx, int R, int N, int K,
+                          int target, int act, float* y_q, float* y_bf16, int out_rows, int ldo, int reps, int* ks,
+                          int8_t* q_out, float* scale_out, float* zero_out) {
+    return fm_guard([&] {
+        FMCHECK(ks && w && x && y_q && y_bf16, "null argument");
+        FMCHECK(quant == FM_QUANT_INT8 || quant == FM_QUANT_INT4, "quant must be int8 or int4");
+        FMCHECK(N >= 16 && N % 16 == 0 && K >= 32 && K % 32 == 0 && target >= 1, "bad shape");
+        const bool q4 = quant == FM_QUANT_INT4;
+        FMCHECK(!q4 || (gs >= 128 && gs % 128 == 0 && K % 128 == 0 && K % gs == 0),
+                "the int4 code form needs a group size and K in whole 128-k units, K a multiple of the group size");
+        *ks = prompt_skinny_ks(N, K, target);
+        FMCHECK(*ks >= 1, "K is too short for a slice of 8 k-steps");
+        FMCHECK(R >= 1 && R <= 64 && ldx >= K && ldx % 8 == 0, "need 1 <= R <= 64 and 16-byte rows of ldx >= K");
+        FMCHECK(act ? (*ks == 1 && ldo >= N / 2 && out_rows >= R) : (ldo == N && out_rows >= *ks * R),
+                "direct SwiGLU: one slice, act [>= R][ldo >= N / 2]; else slabs [>= ks * R][N]");
+        FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
+        StreamGuard g(device);
+        DevBufs b(g.s);
+        const int ng = q4 ? K / gs : 1;
+        bf16_t* dw = b.upload<bf16_t>(w, (size_t)N * K);  // (N is whole tiles: no padding rows)
+        uint8_t* dq = (uint8_t*)b.alloc((size_t)N * K);
+        PromptSkinnyArgs p{};
+        p.x = b.upload<bf16_t>(x, (size_t)R * ldx);
+        p.ldx = ldx;
+        p.R = R;
+        p.N = N;
+        p.K = K;
+        void* pq = nullptr;       // the step-granular codes
+        uint32_t* sz4 = nullptr;  // int4: their (scale, zero) table
+        if (q4) {
+            uint32_t* dsz = (uint32_t*)b.alloc((size_t)N * ng * 4);
+            launch_quant4(g.s, dw, N, K, gs, dq, dsz);  // dw <- bf16(fma(q - 8, scale, zero))
+            pq = b.alloc((size_t)N * K / 2);
+            launch_pack_q4s(g.s, dq, N, K, (uint32_t*)pq);
+            sz4 = (uint32_t*)b.alloc((size_t)(N / 16) * (K / 128) * 16 * 4);
+            launch_pack_sz4(g.s, dsz, N, K, gs, sz4);
+            HIPCHK(hipGetLastError());
+            if (scale_out || zero_out) {
+                std::vector<uint32_t> hs((size_t)N * ng);
+                HIPCHK(hipMemcpyAsync(hs.data(), dsz, hs.size() * 4, hipMemcpyDeviceToHost, g.s));
+                HIPCHK(hipStreamSynchronize(g.s));
+                for (size_t i = 0; i < hs.size(); ++i) {
+                    const uint32_t us = hs[i] << 16, uz = hs[i] & 0xffff0000u;
+                    if (scale_out) memcpy(&scale_out[i], &us, 4);
+                    if (zero_out) memcpy(&zero_out[i], &uz, 4);
+                }
+            }
+        } else {
+            bf16_t* ds = (bf16_t*)b.alloc((size_t)N * 2);
+            launch_quant_rows<bf16_t>(g.s, dw, N, K, (int8_t*)dq, ds);  // dw <- bf16(q)
+            pq = b.alloc((size_t)N * K);
+            launch_pack_q8s(g.s, (const int8_t*)dq, N, K, (int8_t*)pq);
+            HIPCHK(hipGetLastError());
+            if (act) p.wscale = ds;
+            if (scale_out) download<bf16_t>(ds, (size_t)N, scale_out, g.s);
+        }
+        if (q_out) {
+            HIPCHK(hipMemcpyAsync(q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, g.s));
+            HIPCHK(hipStreamSynchronize(g.s));
+        }
+        bf16_t* pk = (bf16_t*)b.alloc((size_t)N * K * 2);
+        launch_pack<bf16_t>(g.s, dw, N, K, pk);
+        HIPCHK(hipGetLastError());
+        for (int form = 0; form < 2; ++form) {
+            float* out = form ? y_q : y_bf16;
+            InOut<float> slab(b, out, act ? 1 : (size_t)out_rows * N);
+            InOut<bf16_t> av(b, out, act ? (size_t)out_rows * ldo : 1);
+            PromptSkinnyArgs l = p;
+            l.slab = slab.d;  // (the launcher wants it set in the direct form too; the kernel does not write it then)
+            if (act) {
+                l.act = av.d;
+                l.lda = ldo;
+            }
+            if (!form) {
+                l.w = pk;
+            } else if (q4) {
+                l.q4s = (const uint32_t*)pq;
+                l.sz = sz4;
+            } else {
+                l.q8s = (const unsigned char*)pq;
+            }
+            for (int i = 0; i < reps; ++i) launch_prompt_skinny(g.s, l, *ks);
+            HIPCHK(hipGetLastError());
+            if (act) av.get(g.s);
+            else slab.get(g.s);
+        }
     });
 }
 

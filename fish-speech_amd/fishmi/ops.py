@@ -363,6 +363,30 @@ def prompt_skinny(w, x, out, target, act=False, reps=1, device=0):
     return int(ks[0])
 
 
+def prompt_skinny_q(w, x, y_q, y_bf16, quant, target, gs=128, act=False, reps=1, device=0):
+    """fm_op_prompt_skinny_q: w [N][K] (bf16-valued) quantised on the device (quant "int8": per row; "int4": groups
+    of gs), then launch_prompt_skinny on x [R][ldx >= K] once from the packed bf16 fragments of the quantised
+    weights (y_bf16) and once from the step-granular codes alone (y_q); both shaped as prompt_skinny's out and
+    filled in place.  Returns (ks, q [N][K] int8 codes, scale, zero): scale [N] and zero None for int8, both
+    [N][K / gs] for int4."""
+    w, x = _f(w), _f(x)
+    N, K = w.shape
+    R, ldx = x.shape
+    y_q, y_bf16 = _out(y_q), _out(y_bf16)
+    assert y_q.shape == y_bf16.shape
+    q4 = quant == "int4"
+    ks = np.zeros(1, np.int32)
+    q = np.zeros((N, K), np.int8)
+    sc = np.zeros((N, K // gs) if q4 else N, np.float32)
+    zr = np.zeros((N, K // gs), np.float32) if q4 else None
+    native.check(native.lib().fm_op_prompt_skinny_q(device, native.FM_QUANT_INT4 if q4 else native.FM_QUANT_INT8,
+                                                    int(gs), _p(w), _p(x), ldx, R, N, K, int(target), int(act),
+                                                    _p(y_q), _p(y_bf16), y_q.shape[0], y_q.shape[1], int(reps),
+                                                    native.i32p(ks), q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+                                                    _p(sc), _p(zr)))
+    return int(ks[0]), q, sc, zr
+
+
 def batched_linear_q4(w, x, epi, gs=128, device=0):
     """fm_op_batched_linear_q4: the batched decode linear (8 < R <= 32 rows of x, bf16) on the device-
     quantised int4 form of w [N][K] (groups of gs along K; gs and K multiples of 128), once streaming

@@ -251,6 +251,14 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    (scale, zero) words -- bit-identical outputs, 0.28x the weight bytes -- 0 the dequantised bf16
    copy; inert for every other model, under "int4_stream" 0, "bstream_acc" 0 and on the "bstream_chain"
    forms).
+   "prompt_skinny_q" 0|1|2, default 1 (weight-only int8 / int4 models in bf16 compute, linears of 33 .. 64
+   rows: a prompt chunk's, a batched frame's of 33 .. 64 slots): 1 the skinny prompt GEMM streams the
+   step-granular codes where the handle holds them (a compact handle, or one opened with more than 8 slots;
+   int4: a group size that is a multiple of 128), 0 it streams the bf16 copy of the quantised weights (int8:
+   the row scales applied in its epilogues) -- the two give the same bits -- and 2 keeps quantised linears
+   off the skinny GEMM, on the 16-row tile kernel every row count above 8 used before; a handle without
+   the step-granular copy runs 1 as 0, and a compact handle, which has no bf16 copy, runs 0 as 1.  Inert
+   for unquantised and fp32 models and at any other row count.
    "rowgemv" / "rowgemv_q4" bits, "row_copies" 0|1 (0: finalize keeps only the row-major weight
    copies those bits select).  "rowgemv" 0..127, default 123: bits 0-4 put wo / w2, wqkv, w1 || w3,
    the codebook head and the first layers' wqkv on the row-block GEMV; bit 5 (32): the first fast
@@ -415,6 +423,17 @@ int fm_op_finalize_norm(int device, int precision, const float* slab, int kparts
    SwiGLU of the row-interleaved w straight to out [R][ldo >= N / 2]. */
 int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int R, int N, int K, int target, int act,
                         float* out, int out_rows, int ldo, int reps, int* ks);
+/* Weight-only int8 / int4 on launch_prompt_skinny (fm_tune "prompt_skinny_q"): quantises the bf16-valued w [N][K]
+   on the device with the model's rule (quant FM_QUANT_INT8: per row; FM_QUANT_INT4: groups of gs along K, gs and K
+   multiples of 128, else FM_ERR_ARG), packs the bf16 fragments and the step-granular codes with the model's pack
+   launchers, and runs the launch once per form on the same x: y_bf16 from the fragments, y_q from the codes alone.
+   Shapes, target, act, out_rows, ldo, reps and ks as fm_op_prompt_skinny's; with act the int8 row scales apply in
+   the SwiGLU (gate and up are round(round(acc) * scale) first).  Both outputs are in/out.  q_out [N][K] (optional):
+   the codes (int4: 0 .. 15); scale_out: int8 [N] row scales, int4 [N][K / gs] group scales with zero_out
+   [N][K / gs] (optional). */
+int fm_op_prompt_skinny_q(int device, int quant, int gs, const float* w, const float* x, int ldx, int R, int N, int K,
+                          int target, int act, float* y_q, float* y_bf16, int out_rows, int ldo, int reps, int* ks,
+                          int8_t* q_out, float* scale_out, float* zero_out);
 /* launch_sample_radix once on caller operands (tests/test_gpu_sampler_ops.py): logits [R][ldl >= Nl]
    fp32, row r sampled with the parameters of slot row_slot[r] (the per-slot arrays have `slots`
    entries; seed is 64-bit).  slow != 0: column i < Nl - 1 is token sb + i and column Nl - 1 is im_end,
