@@ -54,10 +54,20 @@ template <typename T> struct ConvArgs {
     int rope_pos0 = 0, rope_nqk = 0, rope_hd = 0;
     const T* normw = nullptr;     // CE_NORM: the RMSNorm weight [Co] and eps
     float norm_eps = 0.f;
-    // split-K epilogue only (launch_conv_epi; CE_STORE with CE_BIAS / CE_RES, or CE_SWIGLU8): the row scales
-    // [Co] of a weight-only int8 LLM linear -- every channel is round(round(sum) * rscale[co]) before the
-    // bias (linear_epi).  Null for every codec call.
+    // the row scales [Co] of a weight-only int8 LLM linear -- every channel is round(round(sum) * rscale[co]) before
+    // the bias (linear_epi).  Null for every codec call.  Applied by the split-K epilogue (launch_conv_epi; CE_STORE
+    // with CE_BIAS / CE_RES, or CE_SWIGLU8),
+    // conv_splitk_epi_kernel, and the GEMM kernels' own epilogues of an unsplit call (flags CE_STORE / CE_BIAS / CE_RES).
     const T* rscale = nullptr;
+    // The code-reading forms of the GEMM kernels (weight-only int8 / int4 LLM linears on prompt chunks of more than
+    // 64 rows; bf16, one tap, one phase): w is null and the kernels rebuild every bf16 weight fragment, bit for bit,
+    // from the step-granular code copy -- q8s [ceil(Co/16)][Ci/32] x 512 B (launch_pack_q8s, Frag::dq8s; rscale set),
+    // or q4s (256 B per fragment, launch_pack_q4s) with the (scale, zero) table sz [tile][Ci/128][16 rows]
+    // (launch_pack_sz4, Frag::dq4s; Ci a multiple of 128).  The plan, the K slices and the epilogues are those of
+    // the same call on w, so the output bytes are too.
+    const unsigned char* q8s = nullptr;
+    const uint32_t* q4s = nullptr;
+    const uint32_t* sz = nullptr;
 };
 
 // One decoder ResidualUnit (modded_dac.py:599-620) in one launch, bf16, C in {96, 192, 384}:

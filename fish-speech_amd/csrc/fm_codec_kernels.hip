@@ -49,9 +49,17 @@ template <typename T> __device__ __forceinline__ int conv_shift(const ConvArgs<T
 }
 
 // block = 4 waves, block tile 64 time x 64 channels, wave tile 32 x 32 (2x2 MFMA 16x16x32)
-template <typename T>
+// WM, the weight mode (weight-only int8 / int4 LLM linears at R > 64 prompt rows, fm_tune prompt_gemm_q; bf16, one
+// tap, one phase).  0: the packed fragments of a.w.  1 (int8): a.w is null and a lane loads its 8 code bytes of
+// (tile, step) from the step-granular copy a.q8s [ceil(Co/16)][K/32] x 512 B (launch_pack_q8s) instead of its
+// 16-byte fragment; 2 (int4, K in whole 128-k units): its 4-byte word of a.q4s (256 B per fragment,
+// launch_pack_q4s) and the (scale, zero) word of (tile, unit step >> 2, row lane & 15) from a.sz (launch_pack_sz4).
+// Frag::dq8s / dq4s rebuild the bf16 fragment, bit for bit, right before the step's MFMAs -- linear_kernel's code
+// forms on this kernel's tiles.  Steps, slices and accumulators are mode 0's: the three modes write the same bytes.
+template <typename T, int WM = 0>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs<T> a) {
     using F = Frag<T>;
+    static_assert(WM == 0 || sizeof(T) == 2, "code-reading forms: bf16");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tq0 = blockIdx.x * 64 + (wave & 1) * 32;
     const int co0 = blockIdx.y * 64 + (wave >> 1) * 32;
@@ -79,8 +87,23 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs<T> a) {
         tap = kin ? tap : a.ntaps - 1;
         const int ci0 = kin ? kl - tap * a.Ci : 0;
         const int sh = conv_shift(a, tap);
-        typename F::f fa0 = F::load_w(wb + ((size_t)ct0 * S + s) * 512, lane);
-        typename F::f fa1 = F::load_w(wb + ((size_t)(c1 ? ct0 + 1 : ct0) * S + s) * 512, lane);
+        const size_t f0 = (size_t)ct0 * S + s, f1 = (size_t)(c1 ? ct0 + 1 : ct0) * S + s;
+        typename F::f fa0, fa1;
+        u32x2_t r8[2];
+        uint32_t r4[2], rz[2];
+        if constexpr (WM == 1) {
+            r8[0] = reinterpret_cast<const u32x2_t*>(a.q8s)[f0 * 64 + lane];
+            r8[1] = reinterpret_cast<const u32x2_t*>(a.q8s)[f1 * 64 + lane];
+        } else if constexpr (WM == 2) {
+            const int nu = S >> 2, u4 = s >> 2;
+            r4[0] = a.q4s[f0 * 64 + lane];
+            r4[1] = a.q4s[f1 * 64 + lane];
+            rz[0] = a.sz[((size_t)ct0 * nu + u4) * 16 + r];
+            rz[1] = a.sz[((size_t)(c1 ? ct0 + 1 : ct0) * nu + u4) * 16 + r];
+        } else {
+            fa0 = F::load_w(wb + f0 * 512, lane);
+            fa1 = F::load_w(wb + f1 * 512, lane);
+        }
         typename F::f fb[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -88,6 +111,13 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs<T> a) {
             const bool valid = kin && row >= a.lo && row < a.Lx;
             const int rc = row < a.lo ? a.lo : (row >= a.Lx ? a.Lx - 1 : row);
             fb[u] = F::load_masked(a.x + (ptrdiff_t)rc * a.ldx + ci0, valid);
+        }
+        if constexpr (WM == 1) {
+            fa0 = F::dq8s(r8[0]);
+            fa1 = F::dq8s(r8[1]);
+        } else if constexpr (WM == 2) {
+            fa0 = F::dq4s(r4[0], __uint_as_float(rz[0] << 16), __uint_as_float(rz[0] & 0xffff0000u));
+            fa1 = F::dq4s(r4[1], __uint_as_float(rz[1] << 16), __uint_as_float(rz[1] & 0xffff0000u));
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -125,6 +155,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs<T> a) {
                 const int co = co0 + 16 * c + 4 * (lane >> 4) + i;
                 if (co >= a.Co) continue;
                 float y = acc[c][u][i];
+                if (a.rscale) y = rnd<T>(rnd<T>(y) * ld(a.rscale, co));  // weight-only int8 (linear_epi)
                 if (fl & CE_BIAS) y += ld(a.bias, co);
                 y = rnd<T>(y);
                 if (fl & CE_GELU) y = rnd<T>(0.5f * y * (1.0f + erff(y * 0.70710678118654752f)));
@@ -614,14 +645,18 @@ __global__ void conv_weight_kernel(const float* __restrict__ w, int kind, int Ci
 // accumulator tile as T (bias, first rounding, GELU applied) in LDS -- a wave reads back only its own
 // rows.  Phase 2: 16-B chunks of 8 consecutive channels of one row per lane: residual / LayerScale,
 // tanh, the store and the next stage's Snake with 16-B accesses.
-template <typename T, int NCO>
+// a.rscale (weight-only int8 LLM linears, null for every codec call): round(round(acc) * rscale[co]) ahead of the bias.
+template <typename T, int NCO, int WM>
 __device__ __forceinline__ void cg_epilogue(const ConvArgs<T>& a, const f32x4_t (&acc)[NCO][2], T* et, int t0,
                                             int co0, int phase, int nct, int wave, int lane) {
     const int fl = a.flags;
     constexpr int EW = 16 * NCO + 8;  // LDS row stride (elements)
     float bsv[NCO][4];
     {
-        const T* bp = (fl & CE_BIAS) ? a.bias : a.w;
+        // (no bias: unconditional loads of at least Co elements that are there -- the weights, or in a code form,
+        // whose a.w is null, the row scales / the (scale, zero) table; never added)
+        const T* bp = (fl & CE_BIAS) ? a.bias
+                                     : (WM == 0 ? a.w : (WM == 1 ? a.rscale : reinterpret_cast<const T*>(a.sz)));
 #pragma unroll
         for (int c = 0; c < NCO; ++c)
 #pragma unroll
@@ -630,6 +665,11 @@ __device__ __forceinline__ void cg_epilogue(const ConvArgs<T>& a, const f32x4_t 
 #pragma unroll
     for (int c = 0; c < NCO; ++c) {
         if (c >= nct) break;
+        float rsv[4] = {1.f, 1.f, 1.f, 1.f};  // (loaded per tile: 4 registers, not 4 NCO, beside the accumulators)
+        if (a.rscale) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rsv[i] = ld(a.rscale, co0 + 16 * c + 4 * (lane >> 4) + i);
+        }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int tl = 32 * wave + 16 * u + (lane & 15), cl = 16 * c + 4 * (lane >> 4);
@@ -637,6 +677,7 @@ __device__ __forceinline__ void cg_epilogue(const ConvArgs<T>& a, const f32x4_t 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float y = acc[c][u][i];
+                if (a.rscale) y = rnd<T>(rnd<T>(y) * rsv[i]);  // (linear_epi's order)
                 if (fl & CE_BIAS) y += bsv[c][i];
                 y = rnd<T>(y);
                 if (fl & CE_GELU) y = rnd<T>(0.5f * y * (1.0f + erff(y * 0.70710678118654752f)));
@@ -686,9 +727,17 @@ __device__ __forceinline__ void cg_epilogue(const ConvArgs<T>& a, const f32x4_t 
 constexpr int CG2_BM = 128, CG2_XS = 40;
 // waves per SIMD the register budget targets: the second staging set costs 8 * (XCH + WCH) VGPRs
 constexpr int cg2_wpe(int esz, int nco) { return esz == 4 ? 2 : (nco == 8 ? 3 : 4); }
-template <typename T, int NCO>
+// WM, the weight mode (conv_gemm_kernel's: bf16, one tap, one phase).  1 / 2: the block stages the code bytes of
+// its NCO fragments per k-step -- NCO x 512 B (int8) or NCO x 256 B (int4) against NCO x 1 KiB -- and expands them
+// once per block where the staging set is written to LDS (sstore), not once per wave in mma_step: a 16-byte
+// chunk of int8 codes is two lanes' words and becomes two adjacent 16-byte lane fragments; a chunk of int4 codes
+// is four lanes' words, whose four (scale, zero) words (rows 4 i .. 4 i + 3 of one tile and unit) are one 16-byte
+// load issued with the staging loads.  LDS then holds mode 0's fragments; mma_step, the accumulators, the K
+// slices and the epilogues are mode 0's, so the three modes write the same bytes.
+template <typename T, int NCO, int WM = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(cg2_wpe(sizeof(T), NCO)))) void conv_gemm2_kernel(ConvArgs<T> a) {
     using F = Frag<T>;
+    static_assert(WM == 0 || sizeof(T) == 2, "code-reading forms: bf16");
     constexpr int XBUF = CG2_BM * CG2_XS, WBUF = NCO * 512;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_cg[];
     T* lds = reinterpret_cast<T*>(smem_cg);  // [2][XBUF + WBUF]
@@ -705,16 +754,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(cg2_wpe(siz
     const int nct = min(NCO, (a.Co - co0 + 15) >> 4);  // channel tiles present in this block
     constexpr int EC = 16 / (int)sizeof(T);             // elements per 16-B chunk
     constexpr int XCH = CG2_BM * 32 / EC / 256;          // X chunks per thread per step (2 bf16, 4 fp32)
-    constexpr int WCH_T = NCO * 512 / EC;                // W chunks per step
+    constexpr int WCH_T = WM == 0 ? NCO * 512 / EC : NCO * (WM == 1 ? 32 : 16);  // W chunks per step (16 B each)
     constexpr int WCH = (WCH_T + 255) / 256;
+    constexpr int TCH = WCH_T / NCO;                     // ... per channel tile
     using XR = u32x4_t[XCH];
     using WR = u32x4_t[WCH];
     using XM = uint32_t[XCH];
+    const int tile0 = co0 >> 4;
     // raw X chunks and their validity masks: the mask is applied when the chunk is written to LDS,
     // so no ALU op consumes a load before the step that stores it (that would drain vmcnt early)
     u32x4_t xr0[XCH], wr0[WCH], xr1[XCH], wr1[WCH];
     uint32_t xm0[XCH], xm1[XCH];
-    auto gload = [&](int s, XR& xr, XM& xm, WR& wr) {
+    u32x4_t wz0[WCH], wz1[WCH];  // WM 2: the chunks' (scale, zero) words
+    auto gload = [&](int s, XR& xr, XM& xm, WR& wr, WR& wz) {
         s = sb + (s < NS ? s : NS - 1);
         // the step's first tap once per wave (uniform), then at most one boundary inside the
         // 32-wide step (host: Ci >= 32) -- no per-lane integer division
@@ -741,13 +793,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(cg2_wpe(siz
             // tiles past nct are never read by the MFMA loop: clamped re-reads, no branch
             int c = tid + 256 * j;
             c = c < WCH_T ? c : WCH_T - 1;
-            int ct = c / (512 / EC);
-            const int e = c - ct * (512 / EC);
+            int ct = c / TCH;
+            const int e = c - ct * TCH;
             ct = ct < nct ? ct : nct - 1;
-            wr[j] = *reinterpret_cast<const u32x4_t*>(wb + ((size_t)ct * S + s) * 512 + e * EC);
+            if constexpr (WM == 0) {
+                wr[j] = *reinterpret_cast<const u32x4_t*>(wb + ((size_t)ct * S + s) * 512 + e * EC);
+            } else if constexpr (WM == 1) {  // lanes 2 e, 2 e + 1 of fragment (tile0 + ct, s)
+                wr[j] = *reinterpret_cast<const u32x4_t*>(a.q8s + ((size_t)(tile0 + ct) * S + s) * 512 + e * 16);
+            } else {                         // lanes 4 e .. 4 e + 3: rows 4 (e & 3) .. + 3 of the unit's table
+                wr[j] = *reinterpret_cast<const u32x4_t*>(a.q4s + ((size_t)(tile0 + ct) * S + s) * 64 + e * 4);
+                wz[j] = *reinterpret_cast<const u32x4_t*>(a.sz + ((size_t)(tile0 + ct) * (S >> 2) + (s >> 2)) * 16 + 4 * (e & 3));
+            }
         }
     };
-    auto sstore = [&](int buf, const XR& xr, const XM& xm, const WR& wr) {
+    auto sstore = [&](int buf, const XR& xr, const XM& xm, const WR& wr, const WR& wz) {
         T* xs = lds + (size_t)buf * (XBUF + WBUF);
         T* ws = xs + XBUF;
 #pragma unroll
@@ -760,7 +819,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(cg2_wpe(siz
 #pragma unroll
         for (int j = 0; j < WCH; ++j) {
             const int c = tid + 256 * j;
-            if (c < WCH_T) *reinterpret_cast<u32x4_t*>(ws + (size_t)c * EC) = wr[j];
+            if constexpr (WM == 0) {
+                if (c < WCH_T) *reinterpret_cast<u32x4_t*>(ws + (size_t)c * EC) = wr[j];
+            } else if constexpr (WM == 1) {  // chunk c -> lane fragments 2 c, 2 c + 1 of the staged set
+                if (c < WCH_T) {
+                    u32x4_t* d = reinterpret_cast<u32x4_t*>(ws + (size_t)c * 16);
+                    d[0] = F::dq8s((u32x2_t){wr[j][0], wr[j][1]});
+                    d[1] = F::dq8s((u32x2_t){wr[j][2], wr[j][3]});
+                }
+            } else {                         // chunk c -> lane fragments 4 c .. 4 c + 3
+                if (c < WCH_T) {
+                    u32x4_t* d = reinterpret_cast<u32x4_t*>(ws + (size_t)c * 32);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const uint32_t z = wz[j][i];
+                        d[i] = F::dq4s(wr[j][i], __uint_as_float(z << 16), __uint_as_float(z & 0xffff0000u));
+                    }
+                }
+            }
         }
     };
     f32x4_t acc[NCO][2];
@@ -782,21 +858,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(cg2_wpe(siz
         }
     };
     // step s: loads of s+2 into `nx`, MFMAs on LDS buffer s&1, step s+1 (held in `cur`) -> LDS
-    auto step = [&](int s, XR& nx, XM& nm, WR& nw, const XR& cur, const XM& cm, const WR& cw) {
-        gload(s + 2, nx, nm, nw);
+    auto step = [&](int s, XR& nx, XM& nm, WR& nw, WR& nz, const XR& cur, const XM& cm, const WR& cw, const WR& cz) {
+        gload(s + 2, nx, nm, nw, nz);
         mma_step(s & 1);
-        if (s + 1 < NS) sstore((s + 1) & 1, cur, cm, cw);
+        if (s + 1 < NS) sstore((s + 1) & 1, cur, cm, cw, cz);
         __syncthreads();
     };
-    gload(0, xr0, xm0, wr0);
-    gload(1, xr1, xm1, wr1);
-    sstore(0, xr0, xm0, wr0);
+    gload(0, xr0, xm0, wr0, wz0);
+    gload(1, xr1, xm1, wr1, wz1);
+    sstore(0, xr0, xm0, wr0, wz0);
     __syncthreads();
     for (int s = 0; s < NS; s += 4) {  // 4 steps per trip: the loop-header vmcnt drain every 4 steps
-        step(s, xr0, xm0, wr0, xr1, xm1, wr1);
-        if (s + 1 < NS) step(s + 1, xr1, xm1, wr1, xr0, xm0, wr0);
-        if (s + 2 < NS) step(s + 2, xr0, xm0, wr0, xr1, xm1, wr1);
-        if (s + 3 < NS) step(s + 3, xr1, xm1, wr1, xr0, xm0, wr0);
+        step(s, xr0, xm0, wr0, wz0, xr1, xm1, wr1, wz1);
+        if (s + 1 < NS) step(s + 1, xr1, xm1, wr1, wz1, xr0, xm0, wr0, wz0);
+        if (s + 2 < NS) step(s + 2, xr0, xm0, wr0, wz0, xr1, xm1, wr1, wz1);
+        if (s + 3 < NS) step(s + 3, xr1, xm1, wr1, wz1, xr0, xm0, wr0, wz0);
     }
     if (ks > 1) {  // raw fp32 partials [kz][phase][Lq][Co]: 4 consecutive channels per lane
 #pragma unroll
@@ -812,13 +888,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(cg2_wpe(siz
         }
         return;
     }
-    cg_epilogue<T, NCO>(a, acc, lds, t0, co0, phase, nct, wave, lane);
+    cg_epilogue<T, NCO, WM>(a, acc, lds, t0, co0, phase, nct, wave, lane);
 }
 
-template <typename T, int NCO> static void conv2_go(hipStream_t s, const ConvArgs<T>& a) {
+template <typename T, int NCO, int WM> static void conv2_go(hipStream_t s, const ConvArgs<T>& a) {
     const size_t lds = std::max(2 * ((size_t)CG2_BM * CG2_XS + NCO * 512), (size_t)CG2_BM * (16 * NCO + 8)) * sizeof(T);
     dim3 g(FM_CEIL(a.Lq, CG2_BM), FM_CEIL(a.Co, 16 * NCO), a.nphase * (a.ksplit > 1 ? a.ksplit : 1));
-    conv_gemm2_kernel<T, NCO><<<g, 256, lds, s>>>(a);
+    conv_gemm2_kernel<T, NCO, WM><<<g, 256, lds, s>>>(a);
 }
 
 
@@ -858,15 +934,24 @@ template <typename T> ConvPlan conv_plan(const ConvArgs<T>& a) {
     return p;
 }
 
-template <typename T> static void conv_go(hipStream_t s, const ConvArgs<T>& b, int kernel) {
+template <typename T, int WM> static void conv_go_wm(hipStream_t s, const ConvArgs<T>& b, int kernel) {
     if (kernel == CK_LDS8) {
-        conv2_go<T, 8>(s, b);
+        conv2_go<T, 8, WM>(s, b);
     } else if (kernel == CK_LDS6) {
-        conv2_go<T, 6>(s, b);
+        conv2_go<T, 6, WM>(s, b);
     } else {
         dim3 g(FM_CEIL(b.Lq, 64), FM_CEIL(b.Co, 64), b.nphase * (b.ksplit > 1 ? b.ksplit : 1));
-        conv_gemm_kernel<T><<<g, 256, 0, s>>>(b);
+        conv_gemm_kernel<T, WM><<<g, 256, 0, s>>>(b);
     }
+}
+// the weight mode of a call: the code pointer it carries (checked by launch_conv_gemm)
+template <typename T> static int conv_wm(const ConvArgs<T>& a) { return a.q4s ? 2 : (a.q8s ? 1 : 0); }
+template <typename T> static void conv_go(hipStream_t s, const ConvArgs<T>& b, int kernel) {
+    if constexpr (sizeof(T) == 2) {
+        if (conv_wm(b) == 2) return conv_go_wm<T, 2>(s, b, kernel);
+        if (conv_wm(b) == 1) return conv_go_wm<T, 1>(s, b, kernel);
+    }
+    conv_go_wm<T, 0>(s, b, kernel);
 }
 
 // A split-K layer (PackedW::ks > 1): K slices into fp32 slabs, then conv_splitk_epi_kernel; rows in
@@ -921,6 +1006,15 @@ template <typename T> void launch_conv_gemm(hipStream_t s, const ConvArgs<T>& a0
     // x is read in 16-byte chunks of 8 (bf16) / 4 (fp32) channels
     FMCHECK(a.x && ((uintptr_t)a.x & 15) == 0 && a.ldx >= a.Ci && a.ldx % 8 == 0,
             "conv: x 16-byte aligned, rows of ldx >= Ci elements, ldx a multiple of 8");
+    // exactly one weight form: the packed fragments, the int8 codes with their row scales, or the int4 codes with
+    // their (scale, zero) table -- the code forms bf16, one tap, one phase, K in whole k-steps (int4: 128-k units)
+    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const int wm = conv_wm(a);
+    FMCHECK(wm == 0 ? (a.w && !a.sz)
+                    : (sizeof(T) == 2 && !a.w && a.ntaps == 1 && a.nphase == 1 && a.Ci % 32 == 0 &&
+                       (wm == 1 ? (!a.sz && a.rscale && al16(a.q8s))
+                                : (!a.q8s && a.sz && !a.rscale && a.Ci % 128 == 0 && al16(a.q4s) && al16(a.sz)))),
+            "conv: one of w, q8s with rscale, or q4s with sz (bf16, one tap, one phase, K in whole steps / 128-k units)");
     a.shift0 = a.shift[0];
     a.shiftd = a.ntaps > 1 ? a.shift[1] - a.shift[0] : 0;
     for (int j = 0; j < a.ntaps; ++j) FMCHECK(a.shift[j] == a.shift0 + j * a.shiftd, "conv: tap shifts must be linear in the tap");

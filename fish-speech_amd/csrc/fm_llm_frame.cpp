@@ -40,15 +40,27 @@ template <typename T> struct Run {
 
     // Which weight form the skinny prompt GEMM streams for W (fm_tune prompt_skinny_q): 0 the packed bf16 fragments,
     // 1 the step-granular int8 codes, 2 the int4 codes with their (scale, zero) table; -1: none (a quantised linear
-    // at R > 64, in fp32, under prompt_skinny_q 2, or a compact one whose codes have no step-granular copy), and
-    // the caller's fallback reaches linear().  A handle with both prefers the codes under 1, its bf16 copy under 0;
-    // a compact handle has only the codes.
+    // at R > 64, which prompt_gemm asks gemm_form about instead, in fp32, under prompt_skinny_q 2, or a compact one
+    // whose codes have no step-granular copy), and the caller's fallback reaches linear().  A handle with both prefers
+    // the codes under 1, its bf16 copy under 0; a compact handle has only the codes.
     int skinny_form(const Linear& W, int R, int K) const {
         if (!W.q8) return 0;
         if (sizeof(T) != 2 || R > 64 || fm_tuning().prompt_skinny_q == 2) return -1;
         const int codes = W.sz ? ((W.q4s && K % 128 == 0) ? 2 : 0) : (W.q8s ? 1 : 0);
         if (codes && (!W.frag || fm_tuning().prompt_skinny_q == 1)) return codes;
         return W.frag ? 0 : -1;
+    }
+    // Which weight form the tiled prompt GEMMs (launch_conv_gemm) read for a quantised W at R > 64 rows (fm_tune
+    // prompt_gemm_q; bf16 handles): 0 the bf16 fragment copy (int8: with the row scales in the epilogues), 1 / 2 the
+    // step-granular int8 / int4 codes, -1 none -- linear(), the routing before.  A handle with the copy reads it
+    // under 1, as linear() does for it, and its codes, where it has them, under 2; a compact handle has only the
+    // codes and ignores 0.
+    int gemm_form(const Linear& W, int K) const {
+        if (sizeof(T) != 2) return -1;
+        const int codes = W.sz ? ((W.q4s && K % 128 == 0) ? 2 : 0) : (W.q8s ? 1 : 0);
+        if (!W.frag) return codes ? codes : -1;
+        if (fm_tuning().prompt_gemm_q == 0) return -1;
+        return fm_tuning().prompt_gemm_q == 2 && codes ? codes : 0;
     }
     // the skinny GEMM's weight operand of that form
     void skinny_weight(PromptSkinnyArgs& p, const Linear& W, int form) const {
@@ -70,7 +82,8 @@ template <typename T> struct Run {
     // The packed weight layout is the same; epilogues: round(acc + bias) and round(res + round(acc)).
     bool prompt_gemm(const Linear& W, const void* bias, const void* X, int ldx, int R, int N, int K, void* Y, int ldy,
                      const void* res, int ldr, int epi, const char* cls) {
-        const int form = skinny_form(W, R, K);
+        const bool tiled_q = W.q8 && R > 64;  // a quantised linear past the skinny GEMM's rows
+        const int form = tiled_q ? gemm_form(W, K) : skinny_form(W, R, K);
         if (R <= 32 || form < 0 || !fm_tuning().prompt_gemm ||
             (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU8) || N % 16 || K % 32 || N < 96 ||
             (epi == EPI_SWIGLU8 && (bias || N % 16)))
@@ -124,8 +137,25 @@ template <typename T> struct Run {
                 return true;
             }
         }
-        // (a quantised linear has the skinny path alone: the conv GEMMs stage bf16 fragments and know no row scale)
-        if (epi == EPI_SWIGLU8 || W.q8) return false;  // the conv GEMMs' own epilogues have no interleaved SwiGLU
+        // (a quantised linear of <= 64 rows has the skinny path alone)
+        if (epi == EPI_SWIGLU8 || (W.q8 && !tiled_q)) return false;  // the conv GEMMs' own epilogues have no interleaved SwiGLU
+        // A quantised linear at R > 64 (fm_tune prompt_gemm_q): the same launch with the bf16 model's K-split rule,
+        // on its bf16 copy (int8: rscale above, in whichever epilogue the plan runs) or on its step-granular codes,
+        // from which the kernels rebuild that copy's fragments -- the same bytes out either way.
+        if (tiled_q) {
+            if (form == 2) {
+                FMCHECK(W.q4s && W.sz, "prompt GEMM: int4 linear without its step-granular codes");
+                c.w = nullptr;
+                c.q4s = W.q4s;
+                c.sz = W.sz;
+            } else if (form == 1) {
+                FMCHECK(W.q8s && W.scale, "prompt GEMM: int8 linear without its step-granular codes");
+                c.w = nullptr;
+                c.q8s = W.q8s;
+            } else {
+                FMCHECK(W.frag, "prompt GEMM: quantised linear without its bf16 fragments");
+            }
+        }
         // split K (fp32 slabs + the conv split-K epilogue) until the 128 x 128 tiles number >=
         // prompt_ks_tiles (default 384)
         const long long t128 = (long long)FM_CEIL(R, 128) * FM_CEIL(N, 128);
@@ -137,6 +167,7 @@ template <typename T> struct Run {
         c.slab_cap = (size_t)m->skpart_cap;
         auto go = [st, c] { launch_conv_gemm<T>(st, c); };
         launch(cls, bytes, flops, go);
+        if (tiled_q) m->prof.note("prompt_gq", bytes);  // the quantised linears on the tiled route, counted apart as well
         return true;
     }
     // A prompt chunk's wo / w2 (32 < R <= 64, bf16) as raw K-slice partials in m->skpart ([ks][R][N], the

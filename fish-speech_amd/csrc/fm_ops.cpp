@@ -24,6 +24,8 @@
 //                   and the ticket words left non-zero are counted (tests/test_gpu_linear_ops.py)
 //   fm_op_prompt_skinny_q  launch_prompt_skinny on weight-only int8 / int4 codes and on their bf16 fragment
 //                   copy (fm_tune prompt_skinny_q; tests/test_gpu_prompt_skinny_q.py)
+//   fm_op_prompt_gemm_q  launch_conv_gemm, as the prompt pass calls it at more than 64 rows, on weight-only int8 /
+//                   int4 codes and on their bf16 fragment copy (fm_tune prompt_gemm_q; tests/test_gpu_prompt_gemm_q.py)
 //   fm_op_sample    the decode sampler (launch_sample_radix: sample_fast_kernel / sample_radix_kernel and
 //                   their shared wide path) once on caller logits rows, slot table, RAS window and
 //                   forced columns; cols and the tap are in/out (tests/test_gpu_sampler_ops.py)
@@ -37,6 +39,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "fm_codec.h"
 #include "fm_kernels.h"
 #include "fm_ops_util.h"
 #include "fm_runtime.h"
@@ -1374,6 +1377,108 @@ int fm_op_prompt_skinny_q(int device, int quant, int gs, const float* w, const f
             HIPCHK(hipGetLastError());
             if (act) av.get(g.s);
             else slab.get(g.s);
+        }
+    });
+}
+
+// weight-only int8 / int4 on the tiled prompt GEMMs (launch_conv_gemm as Run::prompt_gemm calls it for a linear of
+// more than 64 rows): the model's device quantizer and pack launchers, then the same call once on the packed bf16
+// fragments of the quantised weights (y_bf16; int8: the row scales as ConvArgs::rscale) and once on the step-granular
+// codes alone (y_q).  plan: what conv_plan picked for the call.
+int fm_op_prompt_gemm_q(int device, int quant, int gs, const float* w, const float* bias, const float* x, int ldx, int R,
+                        int N, int K, const float* res, int ldr, int ksplit, float* y_q, float* y_bf16, int out_rows,
+                        int ldo, int reps, int* plan, int8_t* q_out, float* scale_out, float* zero_out) {
+    return fm_guard([&] {
+        FMCHECK(plan && w && x && y_q && y_bf16, "null argument");
+        FMCHECK(quant == FM_QUANT_INT8 || quant == FM_QUANT_INT4, "quant must be int8 or int4");
+        FMCHECK(N >= 16 && N % 16 == 0 && K >= 32 && K % 32 == 0, "bad shape");
+        const bool q4 = quant == FM_QUANT_INT4;
+        FMCHECK(!q4 || (gs >= 128 && gs % 128 == 0 && K % 128 == 0 && K % gs == 0),
+                "the int4 code form needs a group size and K in whole 128-k units, K a multiple of the group size");
+        FMCHECK(R >= 1 && R <= 4096 && ldx >= K && ldx % 8 == 0, "need 1 <= R <= 4096 and 16-byte rows of ldx >= K");
+        FMCHECK(ldo >= N && out_rows >= R && (!res || ldr >= N), "output [>= R][ldo >= N], residual rows of ldr >= N");
+        FMCHECK(ksplit >= 1 && ksplit <= 64 && K / 32 >= ksplit, "ksplit 1..64, at least one k-step per slice");
+        FMCHECK(reps >= 1 && reps <= 8, "reps 1..8");
+        StreamGuard g(device);
+        DevBufs b(g.s);
+        const int ng = q4 ? K / gs : 1;
+        bf16_t* dw = b.upload<bf16_t>(w, (size_t)N * K);  // (N is whole tiles: no padding rows)
+        uint8_t* dq = (uint8_t*)b.alloc((size_t)N * K);
+        ConvArgs<bf16_t> c{};
+        c.x = b.upload<bf16_t>(x, (size_t)R * ldx);
+        c.ldx = ldx;
+        c.Ci = K;
+        c.Lq = R;
+        c.Lx = R;
+        c.Co = N;
+        c.ntaps = 1;
+        c.stride = 1;
+        c.nphase = 1;
+        c.bias = bias ? b.upload<bf16_t>(bias, (size_t)N) : nullptr;
+        c.res = res ? b.upload<bf16_t>(res, (size_t)R * ldr) : nullptr;
+        c.ldr = ldr;
+        c.ldo = ldo;
+        c.flags = CE_STORE | (bias ? CE_BIAS : 0) | (res ? CE_RES : 0);
+        if (ksplit > 1) {  // rows in whole 64-row blocks, so the call is one segment
+            c.ksplit = ksplit;
+            c.slab_cap = (size_t)ksplit * FM_CEIL(R, 64) * 64 * N;
+            c.slab = (float*)b.alloc(c.slab_cap * 4);
+        }
+        void* pq = nullptr;       // the step-granular codes
+        uint32_t* sz4 = nullptr;  // int4: their (scale, zero) table
+        if (q4) {
+            uint32_t* dsz = (uint32_t*)b.alloc((size_t)N * ng * 4);
+            launch_quant4(g.s, dw, N, K, gs, dq, dsz);  // dw <- bf16(fma(q - 8, scale, zero))
+            pq = b.alloc((size_t)N * K / 2);
+            launch_pack_q4s(g.s, dq, N, K, (uint32_t*)pq);
+            sz4 = (uint32_t*)b.alloc((size_t)(N / 16) * (K / 128) * 16 * 4);
+            launch_pack_sz4(g.s, dsz, N, K, gs, sz4);
+            HIPCHK(hipGetLastError());
+            if (scale_out || zero_out) {
+                std::vector<uint32_t> hs((size_t)N * ng);
+                HIPCHK(hipMemcpyAsync(hs.data(), dsz, hs.size() * 4, hipMemcpyDeviceToHost, g.s));
+                HIPCHK(hipStreamSynchronize(g.s));
+                for (size_t i = 0; i < hs.size(); ++i) {
+                    const uint32_t us = hs[i] << 16, uz = hs[i] & 0xffff0000u;
+                    if (scale_out) memcpy(&scale_out[i], &us, 4);
+                    if (zero_out) memcpy(&zero_out[i], &uz, 4);
+                }
+            }
+        } else {
+            bf16_t* ds = (bf16_t*)b.alloc((size_t)N * 2);
+            launch_quant_rows<bf16_t>(g.s, dw, N, K, (int8_t*)dq, ds);  // dw <- bf16(q)
+            pq = b.alloc((size_t)N * K);
+            launch_pack_q8s(g.s, (const int8_t*)dq, N, K, (int8_t*)pq);
+            HIPCHK(hipGetLastError());
+            c.rscale = ds;
+            if (scale_out) download<bf16_t>(ds, (size_t)N, scale_out, g.s);
+        }
+        if (q_out) {
+            HIPCHK(hipMemcpyAsync(q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, g.s));
+            HIPCHK(hipStreamSynchronize(g.s));
+        }
+        bf16_t* pk = (bf16_t*)b.alloc((size_t)N * K * 2);
+        launch_pack<bf16_t>(g.s, dw, N, K, pk);
+        HIPCHK(hipGetLastError());
+        for (int form = 0; form < 2; ++form) {
+            InOut<bf16_t> out(b, form ? y_q : y_bf16, (size_t)out_rows * ldo);
+            ConvArgs<bf16_t> l = c;
+            l.out = out.d;
+            if (!form) {
+                l.w = pk;
+            } else if (q4) {
+                l.q4s = (const uint32_t*)pq;
+                l.sz = sz4;
+            } else {
+                l.q8s = (const unsigned char*)pq;
+            }
+            const ConvPlan p = conv_plan(l);  // (a function of the shape, the flags and the alignment: the same for both forms)
+            const int pv[6] = {p.kernel, p.ksplit, p.nseg, p.epi, p.seg_rows, p.kernel_last};
+            FMCHECK(!form || memcmp(pv, plan, sizeof(pv)) == 0, "prompt GEMM: the code form planned another launch");
+            memcpy(plan, pv, sizeof(pv));
+            for (int i = 0; i < reps; ++i) launch_conv_gemm<bf16_t>(g.s, l);
+            HIPCHK(hipGetLastError());
+            out.get(g.s);
         }
     });
 }

@@ -19,7 +19,7 @@ template <typename... V> constexpr int fm_knob_set(V... v) { return (0 | ... | (
 
 // A compact handle (fm_llm_set_quant_compact: no bf16 copy of its quantised linears) ignores the knobs that would
 // pick a reader of that copy -- bstream 0, bstream_acc 0, bstream_chain 1, bstream_q8 0, bstream_q4 0, int4_stream 0
-// -- and keeps its default routing (prompt_skinny_q 0 it runs as 1); other handles in the process keep the knobs'
+// -- and keeps its default routing (prompt_skinny_q 0 and prompt_gemm_q 0 it runs as 1); other handles in the process keep the knobs'
 // meaning (include/fishmi.h, fm_tune).
 #ifdef FM_KNOB
 FM_KNOB(gemv_nt, 1, FM_BOOL)               // 1: non-temporal weight loads (each weight byte is read once a frame)
@@ -55,6 +55,10 @@ FM_KNOB(prompt_skinny_q, 1, FM_RANGE(0, 2))  // weight-only int8 / int4 (bf16 ha
                                            // codes where the handle has them (compact, or opened with > 8 slots; int4: group size a multiple of 128), 0 the
                                            // bf16 fragment copy (int8: with the row scales in the epilogues; a compact handle has none and keeps the codes);
                                            // 2: no skinny GEMM for quantised linears -- linear_kernel, as before (bit-identical 0 / 1; profiles/prompt_q.md)
+FM_KNOB(prompt_gemm_q, 1, FM_RANGE(0, 2))  // weight-only int8 / int4 (bf16 handles), linears of more than 64 prompt rows: 1 the tiled prompt GEMMs with the
+                                           // bf16 model's K split, reading what linear() reads for the handle -- the bf16 fragment copy (int8: the row scales
+                                           // in the epilogues), or a compact handle's step-granular codes; 2 the codes wherever the handle has them (> 8
+                                           // slots; for measurement); 0 linear_kernel, as before (a compact handle runs 0 as 1; bit-identical 1 / 2)
 FM_KNOB(prompt_ks_tiles, 384, FM_MIN(1))   // prompt GEMM: split K until ceil(R/128) ceil(N/128) ks reaches this ...
 FM_KNOB(prompt_ks_max, 8, FM_SET(1, 2, 4, 8))  // ... or ks this (fp32 slabs + the conv split-K epilogue)
 FM_KNOB(conv2, 1, FM_BOOL)                 // 1: codec GEMMs on the LDS-staged conv_gemm2_kernel, 0: conv_gemm_kernel

@@ -32,7 +32,7 @@ ABI_SYMBOLS = [
     "fm_op_embed", "fm_op_quant4", "fm_op_batched_linear_q8", "fm_op_batched_linear_q4", "fm_rope_table",
     "fm_op_linear", "fm_op_gemv", "fm_op_rowgemv", "fm_op_rowgemv_pair", "fm_op_bstream", "fm_op_finalize_norm", "fm_op_prompt_skinny", "fm_op_sample",
     "fm_llm_prefix_save", "fm_llm_prefix_load", "fm_llm_prefix_drop", "fm_llm_prefix_info", "fm_llm_prefill_batch_at",
-    "fm_llm_set_quant_compact", "fm_llm_memory_info", "fm_op_linear_q", "fm_op_prompt_skinny_q",
+    "fm_llm_set_quant_compact", "fm_llm_memory_info", "fm_op_linear_q", "fm_op_prompt_skinny_q", "fm_op_prompt_gemm_q",
     "fm_op_codec_conv", "fm_op_codec_resunit", "fm_op_codec_window_attn", "fm_op_codec_rope_qk", "fm_op_codec_dwconv_ln",
     "fm_op_codec_rvq_decode", "fm_op_codec_snake", "fm_op_codec_silu_mul", "fm_op_codec_wn_fold", "fm_op_codec_vq_encode",
 ]
@@ -188,6 +188,9 @@ def lib():
     L.fm_op_prompt_skinny.argtypes = [i32, pf32, pf32, i32, i32, i32, i32, i32, i32, pf32, i32, i32, i32, pi32]
     L.fm_op_prompt_skinny_q.argtypes = [i32, i32, i32, pf32, pf32, i32, i32, i32, i32, i32, i32, pf32, pf32, i32, i32, i32,
                                         pi32, ctypes.POINTER(ctypes.c_int8), pf32, pf32]
+    # (device, quant, gs, w, bias, x, ldx, R, N, K, res, ldr, ksplit, y_q, y_bf16, out_rows, ldo, reps, plan, q, scale, zero)
+    L.fm_op_prompt_gemm_q.argtypes = [i32, i32, i32, pf32, pf32, pf32, i32, i32, i32, i32, pf32, i32, i32, pf32, pf32, i32,
+                                      i32, i32, pi32, ctypes.POINTER(ctypes.c_int8), pf32, pf32]
     L.fm_op_sample.argtypes = [i32, i32, i32, pf32, i32, i32, i32, pi32, i32, pf32, pf32, pi32, pi32,
                                ctypes.POINTER(ctypes.c_uint64), pi32, pi32, i32, i32, i32, i32, i32, i32, pi32, i32,
                                pi32, pi32, i32, pf32, i32, pi32]

@@ -387,6 +387,34 @@ def prompt_skinny_q(w, x, y_q, y_bf16, quant, target, gs=128, act=False, reps=1,
     return int(ks[0]), q, sc, zr
 
 
+GEMM_PLAN_FIELDS = ("kernel", "ksplit", "nseg", "epi", "seg_rows", "kernel_last")
+CK_REG, CK_LDS6, CK_LDS8 = 0, 1, 2  # conv_plan's kernels: the register-tiled GEMM, the LDS-tiled one at 6 / 8 channel tiles
+
+
+def prompt_gemm_q(w, x, y_q, y_bf16, quant, gs=128, bias=None, res=None, ksplit=1, reps=1, device=0):
+    """fm_op_prompt_gemm_q: w [N][K] (bf16-valued) quantised on the device as prompt_skinny_q does, then the tiled
+    prompt GEMM (launch_conv_gemm, bf16) on x [R][ldx >= K] once from the packed bf16 fragments of the quantised
+    weights (y_bf16) and once from the step-granular codes alone (y_q): round(acc [* row scale] + bias), then
+    round(res + y) with res [R][ldr >= N]; ksplit K slices.  Both outputs [rows >= R][ldo >= N] are filled in place.
+    Returns (plan dict of GEMM_PLAN_FIELDS, q [N][K] int8 codes, scale, zero) -- the last three as prompt_skinny_q's."""
+    w, x, bias, res = _f(w), _f(x), _f(bias), _f(res)
+    N, K = w.shape
+    R, ldx = x.shape
+    y_q, y_bf16 = _out(y_q), _out(y_bf16)
+    assert y_q.shape == y_bf16.shape and (res is None or res.shape[0] == R)
+    q4 = quant == "int4"
+    plan = np.zeros(6, np.int32)
+    q = np.zeros((N, K), np.int8)
+    sc = np.zeros((N, K // gs) if q4 else N, np.float32)
+    zr = np.zeros((N, K // gs), np.float32) if q4 else None
+    native.check(native.lib().fm_op_prompt_gemm_q(device, native.FM_QUANT_INT4 if q4 else native.FM_QUANT_INT8, int(gs),
+                                                  _p(w), _p(bias), _p(x), ldx, R, N, K, _p(res),
+                                                  0 if res is None else res.shape[1], int(ksplit), _p(y_q), _p(y_bf16),
+                                                  y_q.shape[0], y_q.shape[1], int(reps), native.i32p(plan),
+                                                  q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), _p(sc), _p(zr)))
+    return dict(zip(GEMM_PLAN_FIELDS, (int(v) for v in plan))), q, sc, zr
+
+
 def batched_linear_q4(w, x, epi, gs=128, device=0):
     """fm_op_batched_linear_q4: the batched decode linear (8 < R <= 32 rows of x, bf16) on the device-
     quantised int4 form of w [N][K] (groups of gs along K; gs and K multiples of 128), once streaming

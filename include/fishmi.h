@@ -259,6 +259,12 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    off the skinny GEMM, on the 16-row tile kernel every row count above 8 used before; a handle without
    the step-granular copy runs 1 as 0, and a compact handle, which has no bf16 copy, runs 0 as 1.  Inert
    for unquantised and fp32 models and at any other row count.
+   "prompt_gemm_q" 0|1|2, default 1 (the same models, linears of more than 64 rows: a long prompt's chunks, a
+   batched prefill of more than 64 rows in all): 1 the tiled prompt GEMMs of the bf16 model, with its K split,
+   reading what the handle's linears read before -- the bf16 copy of the quantised weights (int8: the row
+   scales applied in the epilogues), or a compact handle's step-granular codes, from which the kernels rebuild
+   that copy's fragments; 2 the codes wherever the handle holds them (for measurement); 0 the 16-row tile
+   kernel, as before.  1 and 2 give the same bits; a compact handle runs 0 as 1.  Inert elsewhere.
    "rowgemv" / "rowgemv_q4" bits, "row_copies" 0|1 (0: finalize keeps only the row-major weight
    copies those bits select).  "rowgemv" 0..127, default 123: bits 0-4 put wo / w2, wqkv, w1 || w3,
    the codebook head and the first layers' wqkv on the row-block GEMV; bit 5 (32): the first fast
@@ -434,6 +440,17 @@ int fm_op_prompt_skinny(int device, const float* w, const float* x, int ldx, int
 int fm_op_prompt_skinny_q(int device, int quant, int gs, const float* w, const float* x, int ldx, int R, int N, int K,
                           int target, int act, float* y_q, float* y_bf16, int out_rows, int ldo, int reps, int* ks,
                           int8_t* q_out, float* scale_out, float* zero_out);
+/* Weight-only int8 / int4 on the tiled prompt GEMMs (fm_tune "prompt_gemm_q": launch_conv_gemm as the prompt pass calls
+   it for a linear of more than 64 rows): quantises and packs w [N][K] as fm_op_prompt_skinny_q does, and runs the call
+   once per form on the same rows x [R][ldx]: y_bf16 from the bf16 fragments of the quantised weights (int8: the row
+   scales applied in the epilogue), y_q from the step-granular codes alone.  y = round(acc [* scale] + bias), then
+   round(res + y) with res [R][ldr] (bias, res optional); ksplit K slices (1: the GEMM kernel's own epilogue), bf16.
+   Both outputs [out_rows >= R][ldo >= N] are in/out.  plan[6]: conv_plan's {kernel (0 the register-tiled kernel, 1 / 2
+   the LDS-tiled one at 6 / 8 channel tiles), ksplit, segments, epilogue kernel, rows per segment, kernel of the last
+   segment}.  q_out, scale_out, zero_out as fm_op_prompt_skinny_q's. */
+int fm_op_prompt_gemm_q(int device, int quant, int gs, const float* w, const float* bias, const float* x, int ldx, int R,
+                        int N, int K, const float* res, int ldr, int ksplit, float* y_q, float* y_bf16, int out_rows,
+                        int ldo, int reps, int* plan, int8_t* q_out, float* scale_out, float* zero_out);
 /* launch_sample_radix once on caller operands (tests/test_gpu_sampler_ops.py): logits [R][ldl >= Nl]
    fp32, row r sampled with the parameters of slot row_slot[r] (the per-slot arrays have `slots`
    entries; seed is 64-bit).  slow != 0: column i < Nl - 1 is token sb + i and column Nl - 1 is im_end,
