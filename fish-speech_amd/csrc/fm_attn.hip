@@ -482,7 +482,9 @@ __global__ __launch_bounds__(256) void attn_dec3_kernel(AttnDecArgs<T> a) {
     if (owner) {
 #pragma unroll
         for (int it = 0; it < 4; ++it)
-            if (j0 + 16 * wave + 4 * it + (lane >> 4) == pos)
+            // (>= pos: the positions past pos were loaded from the stale row too, clamped; their
+            // probability is 0, but 0 * a non-finite stale value is not)
+            if (j0 + 16 * wave + 4 * it + (lane >> 4) >= pos)
 #pragma unroll
                 for (int e = 0; e < 8; ++e) vreg[it][e] = vd + e < hd ? kv_new[1][vd + e] : 0.f;
     }

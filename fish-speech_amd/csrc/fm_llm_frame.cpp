@@ -239,17 +239,13 @@ template <typename T> struct Run {
     // where it is the faster of the two (B=1 frame 4.28 vs 4.52 ms)
     void attn_slow(const AttnDecArgs<T>& aa, int R) { attn_slow_on(s, aa, R); }
     static void attn_slow_on(hipStream_t s, const AttnDecArgs<T>& aa, int R) {
-        if (fm_tuning().attn_fd && attn_fd_ok(aa.hd, aa.nh / aa.nkv)) {
+        const AttnSlowPlan p = attn_slow_plan(R, aa.hd, aa.nh / aa.nkv, aa.cap);
+        if (p.kernel == 3) {
             AttnDecArgs<T> b = aa;
-            b.cap = std::max(16, R > GEMV_MAX_ROWS ? fm_tuning().fd_min_batched : fm_tuning().fd_min);
-            if (R <= GEMV_MAX_ROWS && fm_tuning().fd_nw > 4) {
-                b.nwb = fm_tuning().fd_nw;
-                b.cap = std::max(16, fm_tuning().fd_min16);
-            } else if (R > GEMV_MAX_ROWS && fm_tuning().fd_nw_batched > 4) {
-                b.nwb = fm_tuning().fd_nw_batched;
-            }
+            b.cap = p.cap;
+            b.nwb = p.nwb;
             launch_attn_fd<T>(s, b, R);
-        } else if (fm_tuning().attn3 && R > GEMV_MAX_ROWS && aa.hd % 32 == 0 && aa.hd <= 128 && aa.nh / aa.nkv <= 6)
+        } else if (p.kernel == 2)
             launch_attn_decode3<T>(s, aa, R);
         else
             launch_attn_decode2<T>(s, aa, R);
@@ -430,8 +426,7 @@ template <typename T> struct Run {
             AttnDecArgs<T> aa{(const T*)m->qkv, d.nqkv(), b.rslot, b.rpos, d.nh, d.nkv, d.hd, d.qk_norm, eps,
                               (const T*)L.qn, (const T*)L.kn, b.rope, (T*)b.kc, (T*)b.vc, b.sstride, b.loff, b.Sc,
                               m->maxsplit, scale, m->part};
-            aa.cap = attn2_cap(d.hd, d.nh / d.nkv, E);
-            if (fm_tuning().attn_cap_batched) aa.cap = std::min(aa.cap, fm_tuning().attn_cap_batched);
+            aa.cap = attn2_frame_cap(d.hd, d.nh / d.nkv, E, true);
             aa.maxsplit = FM_CEIL(b.Sc, aa.cap);
             aa.cnt = m->attn_cnt;
             aa.dbg = fm_tuning().dbg;
@@ -984,8 +979,7 @@ template <typename T> struct Run {
                               d.qk_norm, m->c.norm_eps, (const T*)c.L.qn, (const T*)c.L.kn, m->rope, (T*)m->kc,
                               (T*)m->vc, m->slot_stride, (size_t)c.layer * m->layer_stride, m->S,
                               m->maxsplit, 1.0f / sqrtf((float)d.hd), m->part};
-            aa.cap = attn2_cap(d.hd, d.nh / d.nkv, E);
-            if (fm_tuning().attn_cap) aa.cap = std::min(aa.cap, fm_tuning().attn_cap);
+            aa.cap = attn2_frame_cap(d.hd, d.nh / d.nkv, E, false);
             aa.maxsplit = FM_CEIL(m->S, aa.cap);
             aa.cnt = m->attn_cnt;
             aa.dbg = fm_tuning().dbg;

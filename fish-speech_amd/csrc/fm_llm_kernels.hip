@@ -898,9 +898,12 @@ __global__ __launch_bounds__(64) void fast_attn_kernel(FastAttnArgs<T> a) {
     const float den = wave_sum(ex);
     ps[lane] = rnd<T>(ex / den);
     __syncthreads();
+    // rows above cpos have probability 0 and are not read: a stale cache row there may hold anything
+    // (0 * inf, 0 * nan); the bits for finite rows are the same, the skipped terms being + (+-0)
+    const int jn = min(a.S, a.cpos + 1);
     for (int e = lane; e < hd; e += 64) {
         float o = 0.f;
-        for (int j = 0; j < a.S; ++j) o += ps[j] * ld(vc + (size_t)j * hd, e);
+        for (int j = 0; j < jn; ++j) o += ps[j] * ld(vc + (size_t)j * hd, e);
         st(a.out, (size_t)r * a.nh * hd + (size_t)h * hd + e, o);
     }
 }

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "fm_kernels.h"
 #include "fm_runtime.h"
 
@@ -11,6 +13,35 @@ static constexpr int ATTN_PIECE = 256;      // prompt rows per attention launch 
 static constexpr int ATTN_SPLIT = 64;
 static constexpr int GEMV_MAX_ROWS = 8;  // frames with <= 8 streams take the fused GEMV path
 static constexpr int KSB_MAX = 8;
+
+// attn_decode2's rows per block in a frame: the LDS budget (attn2_cap), capped by the attn_cap knob of the
+// small-batch frame or attn_cap_batched of the batched one (the frames and fm_op_decode_attn_ex's frame mode)
+inline int attn2_frame_cap(int hd, int g, size_t esz, bool batched) {
+    const int cap = attn2_cap(hd, g, esz), knob = batched ? fm_tuning().attn_cap_batched : fm_tuning().attn_cap;
+    return knob ? std::min(cap, knob) : cap;
+}
+// Which slow decode attention a frame of R rows launches, and with what geometry (the frame's
+// attn_slow_on and the per-op hook fm_op_decode_attn_ex both ask here).  kernel as fm_op_decode_attn
+// numbers them: 3 attn_fd, 2 attn_dec3, 0 attn_decode2.  attn_fd: nwb waves per block and splits of
+// at least cap positions, from the fd_* knobs; the other two keep the caller's cap (cap0).
+struct AttnSlowPlan {
+    int kernel, nwb, cap;
+};
+inline AttnSlowPlan attn_slow_plan(int R, int hd, int g, int cap0) {
+    const FmTuning& tu = fm_tuning();
+    if (tu.attn_fd && attn_fd_ok(hd, g)) {
+        AttnSlowPlan p{3, 4, std::max(16, R > GEMV_MAX_ROWS ? tu.fd_min_batched : tu.fd_min)};
+        if (R <= GEMV_MAX_ROWS && tu.fd_nw > 4) {
+            p.nwb = tu.fd_nw;
+            p.cap = std::max(16, tu.fd_min16);
+        } else if (R > GEMV_MAX_ROWS && tu.fd_nw_batched > 4) {
+            p.nwb = tu.fd_nw_batched;
+        }
+        return p;
+    }
+    if (tu.attn3 && R > GEMV_MAX_ROWS && hd % 32 == 0 && hd <= 128 && g <= 6) return {2, 4, cap0};
+    return {0, 4, cap0};
+}
 static constexpr int BS_KPARTS = 8;  // most K parts of a bstream slab (fm_bstream.hip)
 
 // split-K factor across blocks for a GEMV with N output rows: >= ~512 blocks when possible,

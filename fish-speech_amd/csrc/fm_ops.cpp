@@ -41,12 +41,21 @@
 
 #include "fm_codec.h"
 #include "fm_kernels.h"
+#include "fm_llm_model.h"
 #include "fm_ops_util.h"
 #include "fm_runtime.h"
 
 using namespace fm_ops_util;
 
 namespace {
+
+// a knob set for one launch and put back whatever happens in between (a launcher's FMCHECK throws)
+struct TuneScope {
+    int& knob;
+    const int keep;
+    TuneScope(int& k, int v) : knob(k), keep(k) { knob = v; }
+    ~TuneScope() { knob = keep; }
+};
 
 template <typename T>
 void rmsnorm_t(hipStream_t s, int mode, const float* x, const float* w, int R, int d, float eps, float* y) {
@@ -188,11 +197,10 @@ void prompt_attn_t(hipStream_t s, int kernel, const float* q, int R, int nh, int
     const int split = 64, maxsplit = FM_CEIL(S, split);
     AttnArgs<T> a{qd, rows, rows + R, kc, vc, (size_t)nkv * S * hd, 0, S, nh, nkv, hd, split, maxsplit,
                   1.0f / sqrtf((float)hd), (float*)b.alloc((size_t)R * nh * maxsplit * (hd + 2) * 4)};
-    FmTuning& tu = fm_tuning();
-    const int keep = tu.prefill_attn;
-    tu.prefill_attn = kernel;
-    launch_attn<T>(s, a, R, maxsplit, o, true);
-    tu.prefill_attn = keep;
+    {
+        const TuneScope knob(fm_tuning().prefill_attn, kernel);
+        launch_attn<T>(s, a, R, maxsplit, o, true);
+    }
     download<T>(o, (size_t)R * nh * hd, out, s);
 }
 
@@ -244,6 +252,348 @@ void decode_attn_t(hipStream_t s, int kernel, const float* qkv, int R, int nh, i
     download<T>(o, (size_t)R * nh * hd, out, s);
     download<T>(kc, (size_t)R * stride, kc_out, s);
     download<T>(vc, (size_t)R * stride, vc_out, s);
+}
+
+// ---- attention hooks with slot indirection, layers and the frame's launch forms (tests/test_gpu_attn_ops.py) ----
+int count_nonzero(const int* d, size_t n, hipStream_t s);
+// fp32 host array as is (K-part slabs)
+float* upload_raw(DevBufs& b, const float* h, size_t n) {
+    float* d = (float*)b.alloc(n * 4);
+    b.put(d, h, n * 4);
+    return d;
+}
+int* upload_i32(DevBufs& b, const int* h, size_t n) {
+    int* d = (int*)b.alloc(n * 4);
+    b.put(d, h, n * 4);
+    return d;
+}
+float* upload_rope(DevBufs& b, int S, int hd, float base) {
+    auto tab = rope_table_host(S, hd, base);
+    return upload_raw(b, tab.data(), tab.size());
+}
+
+struct DecodeAttnEx {
+    int kernel;
+    const float *qkv, *slab;
+    int kp;
+    const float* bias;
+    int R, nh, nkv, hd;
+    const float *qn, *kn;
+    int qk_norm;
+    float eps, base;
+    const int *row_slot, *pos;
+    int nslots, layers, layer;
+    float *kc, *vc;
+    int S, cap, nwb, frame, reps;
+    float* out;
+    int* info;
+};
+constexpr int PART_GUARD = 1024;  // sentinel words behind the split partials
+// one slow decode attention launch (or o.reps of them) over R rows in slots row_slot[r] of caller caches
+// [nslots][layers][nkv][S][hd], layer o.layer; o.frame: kernel, nwb and cap as a frame of R rows picks them
+template <typename T> void decode_attn_ex_t(hipStream_t s, const DecodeAttnEx& o) {
+    DevBufs b(s);
+    const int R = o.R, nh = o.nh, nkv = o.nkv, hd = o.hd, S = o.S, g = nh / nkv;
+    const int ld = (nh + 2 * nkv) * hd;
+    const T* raw = o.qkv ? b.upload<T>(o.qkv, (size_t)R * ld) : nullptr;
+    const float* slab = o.slab ? upload_raw(b, o.slab, (size_t)o.kp * R * ld) : nullptr;
+    const T* bias = o.bias ? b.upload<T>(o.bias, (size_t)ld) : nullptr;
+    T* qnd = o.qk_norm ? b.upload<T>(o.qn, (size_t)hd) : (T*)b.alloc((size_t)hd * sizeof(T));
+    T* knd = o.qk_norm ? b.upload<T>(o.kn, (size_t)hd) : (T*)b.alloc((size_t)hd * sizeof(T));
+    float* rope = upload_rope(b, S, hd, o.base);
+    const size_t layer_stride = (size_t)nkv * S * hd, slot_stride = (size_t)o.layers * layer_stride;
+    InOut<T> kc(b, o.kc, (size_t)o.nslots * slot_stride), vc(b, o.vc, (size_t)o.nslots * slot_stride);
+    T* out = (T*)b.alloc((size_t)R * nh * hd * sizeof(T));
+    std::vector<int> rs(2 * R);
+    for (int r = 0; r < R; ++r) {
+        rs[r] = o.row_slot[r];
+        rs[R + r] = o.pos[r];
+    }
+    int* rows = upload_i32(b, rs.data(), rs.size());
+    int kernel = o.kernel, nwb = o.nwb, cap = o.cap;
+    const int cap2 = attn2_cap(hd, g, sizeof(T));
+    if (o.frame) {  // as blk_attn / small_attn do
+        const AttnSlowPlan p = attn_slow_plan(R, hd, g, attn2_frame_cap(hd, g, sizeof(T), R > GEMV_MAX_ROWS));
+        kernel = p.kernel;
+        nwb = p.nwb;
+        cap = p.cap;
+    }
+    if (kernel == 0) cap = std::min(cap, cap2);
+    FMCHECK(!slab || kernel == 3, "the slab form of the QKV input needs attn_fd");
+    FMCHECK(kernel != 3 || attn_fd_ok(hd, g), "attn_fd: head_dim 32, 64 or 128 and at most 4 q heads per kv head");
+    FMCHECK(kernel != 2 || (hd % 32 == 0 && hd <= 128 && g <= 6), "attn_dec3: hd a multiple of 32 up to 128, g <= 6");
+    const int maxsplit = kernel == 3 ? std::min(FD_NSP, FM_CEIL(S, cap)) : (kernel == 2 ? FM_CEIL(S, 64) : FM_CEIL(S, cap));
+    AttnDecArgs<T> a{raw, ld, rows, rows + R, nh, nkv, hd, o.qk_norm, o.eps, qnd, knd, rope, kc.d, vc.d, slot_stride,
+                     (size_t)o.layer * layer_stride, S, maxsplit, 1.0f / sqrtf((float)hd), nullptr};
+    // partials exactly as fm_kernels.h sizes them, poisoned (an unwritten partial must not be read), then the guard
+    const size_t npart = (size_t)R * nh * maxsplit * (hd + 2);
+    a.part = (float*)b.alloc((npart + PART_GUARD) * 4);
+    HIPCHK(hipMemsetAsync(a.part, 0xff, npart * 4, s));
+    const std::vector<uint32_t> guard(PART_GUARD, 0x5a5a5a5au);
+    b.put(a.part + npart, guard.data(), PART_GUARD * 4);
+    a.cnt = (int*)b.alloc((size_t)R * nkv * 4);
+    a.out = out;
+    a.cap = cap;
+    a.nwb = nwb;
+    a.qslab = slab;
+    a.qslab_kp = o.kp;
+    a.qbias = bias;
+    for (int i = 0; i < o.reps; ++i) {
+        if (kernel == 3)
+            launch_attn_fd<T>(s, a, R);
+        else if (kernel == 2)
+            launch_attn_decode3<T>(s, a, R);
+        else
+            launch_attn_decode2<T>(s, a, R);
+        HIPCHK(hipGetLastError());
+    }
+    download<T>(out, (size_t)R * nh * hd, o.out, s);
+    kc.get(s);
+    vc.get(s);
+    std::vector<uint32_t> back(PART_GUARD);
+    HIPCHK(hipMemcpyAsync(back.data(), a.part + npart, PART_GUARD * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const int info[8] = {kernel, nwb, cap, maxsplit, count_nonzero(a.cnt, (size_t)R * nkv, s), back == guard, FD_NSP, cap2};
+    memcpy(o.info, info, sizeof(info));
+}
+
+struct SlotRows {
+    const int *row_slot, *row_pos;  // row_pos null: fixed_pos
+    int nslots, layers, layer;
+};
+// launch_qk_rope_cache on R rows (qkv, or kp slabs + bias): q out, caches in/out
+template <typename T>
+void qk_rope_cache_t(hipStream_t s, const float* qkv, const float* slabh, int kp, const float* biash, int R, int nh,
+                     int nkv, int hd, const float* qn, const float* kn, int qk_norm, float eps, float base,
+                     const SlotRows& sr, int fixed_pos, float* kch, float* vch, int S, float* q_out) {
+    DevBufs b(s);
+    const int ld = (nh + 2 * nkv) * hd;
+    const T* raw = qkv ? b.upload<T>(qkv, (size_t)R * ld) : nullptr;
+    const float* slab = slabh ? upload_raw(b, slabh, (size_t)kp * R * ld) : nullptr;
+    const T* bias = biash ? b.upload<T>(biash, (size_t)ld) : nullptr;
+    T* qnd = qk_norm ? b.upload<T>(qn, (size_t)hd) : (T*)b.alloc((size_t)hd * sizeof(T));
+    T* knd = qk_norm ? b.upload<T>(kn, (size_t)hd) : (T*)b.alloc((size_t)hd * sizeof(T));
+    float* rope = upload_rope(b, S, hd, base);
+    const size_t layer_stride = (size_t)nkv * S * hd, slot_stride = (size_t)sr.layers * layer_stride;
+    InOut<T> kc(b, kch, (size_t)sr.nslots * slot_stride), vc(b, vch, (size_t)sr.nslots * slot_stride);
+    T* q = (T*)b.alloc((size_t)R * nh * hd * sizeof(T));
+    std::vector<int> rs(2 * R, 0);
+    for (int r = 0; r < R; ++r) {
+        rs[r] = sr.row_slot[r];
+        if (sr.row_pos) rs[R + r] = sr.row_pos[r];
+    }
+    int* rows = upload_i32(b, rs.data(), rs.size());
+    QkArgs<T> a{raw, ld, rows, rows + R, fixed_pos, nh, nkv, hd, qk_norm, eps, qnd, knd, rope, q, kc.d, vc.d, slot_stride,
+                (size_t)sr.layer * layer_stride, S};
+    a.qslab = slab;
+    a.qslab_kp = kp;
+    a.qbias = bias;
+    launch_qk_rope_cache<T>(s, a, R);
+    HIPCHK(hipGetLastError());
+    download<T>(q, (size_t)R * nh * hd, q_out, s);
+    kc.get(s);
+    vc.get(s);
+}
+
+// launch_attn on R prompt rows with their own (slot, pos) over caller caches [nslots][layers][nkv][S][hd]
+template <typename T>
+void prompt_attn_ex_t(hipStream_t s, int kernel, const float* q, int R, int nh, int nkv, int hd, const SlotRows& sr,
+                      int one_slot, const float* kcache, const float* vcache, int S, float* out) {
+    DevBufs b(s);
+    T* qd = b.upload<T>(q, (size_t)R * nh * hd);
+    const size_t layer_stride = (size_t)nkv * S * hd, slot_stride = (size_t)sr.layers * layer_stride;
+    T* kc = b.upload<T>(kcache, (size_t)sr.nslots * slot_stride);
+    T* vc = b.upload<T>(vcache, (size_t)sr.nslots * slot_stride);
+    T* o = (T*)b.alloc((size_t)R * nh * hd * sizeof(T));
+    std::vector<int> rs(2 * R);
+    for (int r = 0; r < R; ++r) {
+        rs[r] = sr.row_slot[r];
+        rs[R + r] = sr.row_pos[r];
+    }
+    int* rows = upload_i32(b, rs.data(), rs.size());
+    const int split = ATTN_SPLIT, maxsplit = FM_CEIL(S, split);
+    const size_t npart = (size_t)R * nh * maxsplit * (hd + 2);
+    float* part = (float*)b.alloc(npart * 4);
+    HIPCHK(hipMemsetAsync(part, 0xff, npart * 4, s));  // an unwritten partial must not be read
+    AttnArgs<T> a{qd, rows, rows + R, kc, vc, slot_stride, (size_t)sr.layer * layer_stride, S, nh, nkv, hd, split, maxsplit,
+                  1.0f / sqrtf((float)hd), part};
+    {
+        const TuneScope knob(fm_tuning().prefill_attn, kernel);
+        launch_attn<T>(s, a, R, maxsplit, o, one_slot != 0);
+        HIPCHK(hipGetLastError());
+    }
+    download<T>(o, (size_t)R * nh * hd, out, s);
+}
+
+// the fast decoder's attention at codebook position cpos on R rows: kernel 0 fast_attn2, 1 fast_attn2 with noq,
+// 2 fast_attn_fused, 3 qk_rope_cache(fixed_pos) + fast_attn_kernel (the unfused pair); caches in/out
+template <typename T>
+void fast_attn_t(hipStream_t s, int kernel, const float* qkv, int R, int nh, int nkv, int hd, const float* qn,
+                 const float* kn, int qk_norm, float eps, float base, const SlotRows& sr, int cpos, float* kch, float* vch,
+                 int S, float* outh) {
+    DevBufs b(s);
+    const int ld = (nh + 2 * nkv) * hd;
+    const T* raw = b.upload<T>(qkv, (size_t)R * ld);
+    T* qnd = qk_norm ? b.upload<T>(qn, (size_t)hd) : (T*)b.alloc((size_t)hd * sizeof(T));
+    T* knd = qk_norm ? b.upload<T>(kn, (size_t)hd) : (T*)b.alloc((size_t)hd * sizeof(T));
+    float* rope = upload_rope(b, S, hd, base);
+    const size_t layer_stride = (size_t)nkv * S * hd, slot_stride = (size_t)sr.layers * layer_stride;
+    const size_t layer_off = (size_t)sr.layer * layer_stride;
+    InOut<T> kc(b, kch, (size_t)sr.nslots * slot_stride), vc(b, vch, (size_t)sr.nslots * slot_stride);
+    T* out = (T*)b.alloc((size_t)R * nh * hd * sizeof(T));
+    int* rows = upload_i32(b, sr.row_slot, (size_t)R);
+    const float scale = 1.0f / sqrtf((float)hd);
+    if (kernel == 3) {
+        T* q = (T*)b.alloc((size_t)R * nh * hd * sizeof(T));
+        QkArgs<T> qa{raw, ld, rows, nullptr, cpos, nh, nkv, hd, qk_norm, eps, qnd, knd, rope, q, kc.d, vc.d, slot_stride,
+                     layer_off, S};
+        launch_qk_rope_cache<T>(s, qa, R);
+        HIPCHK(hipGetLastError());
+        FastAttnArgs<T> fa{q, rows, kc.d, vc.d, slot_stride, layer_off, S, nh, nkv, hd, cpos, scale, out};
+        launch_fast_attn<T>(s, fa, R);
+    } else {
+        FastFusedArgs<T> a{raw, ld, rows, nh, nkv, hd, qk_norm, eps, qnd, knd, rope, kc.d, vc.d, slot_stride, layer_off, S,
+                           cpos, scale, out};
+        a.noq = kernel == 1;
+        if (kernel == 2)
+            launch_fast_attn_fused<T>(s, a, R);
+        else
+            launch_fast_attn2<T>(s, a, R);
+    }
+    HIPCHK(hipGetLastError());
+    download<T>(out, (size_t)R * nh * hd, outh, s);
+    kc.get(s);
+    vc.get(s);
+}
+
+// the batch-1 fast decoder's attention + wo: one launch_fattn_wo (fused), or the launches it replaces
+// (launch_fast_attn2 + launch_rowgemv FIN) on the same device operands
+struct FattnWoOp {
+    int quant, gs, fused;
+    const float *qkv, *qtab;
+    int qrows;
+    const int32_t* idx;
+    int idx_n, idx_col, nh, nkv, hd;
+    const float *qn, *kn;
+    int qk_norm;
+    float eps, base;
+    int slot, cpos, nslots, layers, layer;
+    float *kc, *vc;
+    int S;
+    const float *w, *bias, *res;
+    int res_rows, ldr;
+    const float* res0;
+    int N, kv0, pair, ilp, gen, pos0;
+    const uint32_t* xt_init;
+    float* y;
+    int* status;
+};
+void fattn_wo_op(hipStream_t s, const FattnWoOp& o) {
+    DevBufs b(s);
+    const int nh = o.nh, nkv = o.nkv, hd = o.hd, S = o.S, N = o.N, K = nh * hd, ld = (nh + 2 * nkv) * hd;
+    const int qm = o.quant == FM_QUANT_INT4 ? 2 : (o.quant == FM_QUANT_INT8 ? 1 : 0);
+    // "not dispatchable" is a status, not a launch: what small_path asks before it takes the fused launch
+    o.status[0] = fattn_wo_ok(nh, nkv, hd, o.cpos, N, K, qm) && (!(o.qtab || o.kv0) || fattn_wo_dead_ok(K, qm)) &&
+                  (!o.pair || rowgemv_pair_ok(-1, K, false));
+    o.status[1] = 0;
+    if (!o.status[0]) return;
+    RowGemvArgs r{};
+    const int Np = (N + 15) / 16 * 16;
+    bf16_t* wd = (bf16_t*)b.alloc((size_t)Np * K * 2);
+    HIPCHK(hipMemcpyAsync(wd, b.upload<bf16_t>(o.w, (size_t)N * K), (size_t)N * K * 2, hipMemcpyDeviceToDevice, s));
+    if (qm == 1) {  // the quantizers of fm_llm_set_quant / _int4 on the device, as rowgemv_op and fm_op_quant4 run them
+        int8_t* dq = (int8_t*)b.alloc((size_t)Np * K);
+        bf16_t* ds = (bf16_t*)b.alloc((size_t)Np * 2);
+        launch_quant_rows<bf16_t>(s, wd, N, K, dq, ds);
+        r.Wq = dq;
+        r.wscale = ds;
+    } else if (qm == 2) {
+        uint8_t* dq = (uint8_t*)b.alloc((size_t)Np * K);
+        uint32_t* dsz = (uint32_t*)b.alloc((size_t)Np * (K / o.gs) * 4);
+        uint32_t* words = (uint32_t*)b.alloc((size_t)Np * K / 2);
+        launch_quant4(s, wd, N, K, o.gs, dq, dsz);
+        launch_pack_q4_rows(s, dq, N, K, words);
+        r.Wq4 = words;
+        r.wsz = dsz;
+        r.gs = o.gs;
+    } else {
+        r.W = wd;
+    }
+    HIPCHK(hipGetLastError());
+    if (o.bias) r.bias = b.upload<bf16_t>(o.bias, (size_t)N);
+    const int rows = o.pair ? 2 : 1;
+    const bf16_t* raw = b.upload<bf16_t>(o.qkv, (size_t)rows * ld);
+    const bf16_t* qtab = o.qtab ? b.upload<bf16_t>(o.qtab, (size_t)o.qrows * ld) : nullptr;
+    const int32_t* idx = o.idx ? upload_i32(b, o.idx, (size_t)o.idx_n) : nullptr;
+    bf16_t* qnd = o.qk_norm ? b.upload<bf16_t>(o.qn, (size_t)hd) : (bf16_t*)b.alloc((size_t)hd * 2);
+    bf16_t* knd = o.qk_norm ? b.upload<bf16_t>(o.kn, (size_t)hd) : (bf16_t*)b.alloc((size_t)hd * 2);
+    float* rope = upload_rope(b, S, hd, o.base);
+    const size_t layer_stride = (size_t)nkv * S * hd, slot_stride = (size_t)o.layers * layer_stride;
+    InOut<bf16_t> kc(b, o.kc, (size_t)o.nslots * slot_stride), vc(b, o.vc, (size_t)o.nslots * slot_stride);
+    const int rs[2] = {o.slot, o.pos0};
+    int* rows_d = upload_i32(b, rs, 2);
+    bf16_t* att = (bf16_t*)b.alloc((size_t)K * 2);
+    FastFusedArgs<bf16_t> at{raw, ld, rows_d, nh, nkv, hd, o.qk_norm, o.eps, qnd, knd, rope, kc.d, vc.d, slot_stride,
+                             (size_t)o.layer * layer_stride, S, o.cpos, 1.0f / sqrtf((float)hd), att};
+    at.row_pos = rows_d + 1;
+    // residual(s): the table res [res_rows][ldr], row idx[idx_col] of it (clamped) when idx is given, else row 0
+    const bf16_t* res = b.upload<bf16_t>(o.res, (size_t)o.res_rows * o.ldr);
+    r.ldr = o.ldr;
+    r.residx = idx;
+    r.res_col = o.idx_col;
+    r.res_rows = o.res_rows;
+    r.N = N;
+    r.K = K;
+    InOut<bf16_t> y(b, o.y, (size_t)(o.pair == 1 ? 2 : 1) * N);
+    r.res = res;
+    r.res_out = y.d;
+    if (o.pair == 1) {  // row 0's residual as it stands, row 1's from the table
+        r.xr = 2;
+        r.res = b.upload<bf16_t>(o.res0, (size_t)N);
+        r.res1 = res;
+        r.res_out1 = y.d + N;
+    }
+    int* err = (int*)b.alloc(16);
+    if (o.fused) {
+        FattnWoArgs A{};
+        A.at = at;
+        A.wo = r;
+        A.wo.X = att;  // (unused: x comes from the tagged words)
+        A.xt = (uint32_t*)b.alloc((size_t)2 * K * 4);
+        if (o.xt_init) b.put(A.xt, o.xt_init, (size_t)2 * K * 4);
+        A.gen = o.gen;
+        A.err = err;
+        A.delay = fm_tuning().fw_delay;
+        A.cheap = fm_tuning().fw_cheap;
+        A.prio = fm_tuning().fw_prio;
+        A.ilp = o.ilp;
+        if (qtab) {
+            A.qtab = qtab;
+            A.qidx = idx;
+            A.qcol = o.idx_col;
+            A.qrows = o.qrows;
+        }
+        A.kv0 = o.kv0;
+        A.pair = o.pair;
+        launch_fattn_wo(s, A);  // one launch, never repeated: its waits are bounded and set err
+    } else {
+        FMCHECK(!o.pair, "the unfused composition runs one row");
+        if (qtab) {  // the QKV launch's output is the table row of the (clamped) index
+            const int iv = o.idx[o.idx_col], xi = iv < 0 ? 0 : (iv >= o.qrows ? o.qrows - 1 : iv);
+            at.qkv = qtab + (size_t)xi * ld;
+        }
+        at.noq = o.kv0;
+        launch_fast_attn2<bf16_t>(s, at, 1);
+        HIPCHK(hipGetLastError());
+        r.X = att;
+        launch_rowgemv(s, r, ROWGEMV_FIN);
+    }
+    HIPCHK(hipGetLastError());
+    y.get(s);
+    kc.get(s);
+    vc.get(s);
+    HIPCHK(hipMemcpyAsync(&o.status[1], err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
 }
 
 template <typename T>
@@ -779,6 +1129,149 @@ int fm_op_decode_attn(int device, int precision, int kernel, const float* qkv, i
         else
             decode_attn_t<float>(g.s, kernel, qkv, R, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, pos, kcache, vcache,
                                  S, min_split, out, kc_out, vc_out);
+    });
+}
+
+// rows in distinct slots of [0, nslots), positions (if given) inside the cache, a layer of the cache
+static void check_slot_rows(int R, const int* row_slot, const int* row_pos, int nslots, int layers, int layer, int S) {
+    FMCHECK(row_slot && nslots >= 1 && layers >= 1 && layer >= 0 && layer < layers, "bad slots / layers");
+    for (int r = 0; r < R; ++r) {
+        FMCHECK(row_slot[r] >= 0 && row_slot[r] < nslots, "row_slot outside the cache");
+        FMCHECK(!row_pos || (row_pos[r] >= 0 && row_pos[r] < S), "position outside the cache");
+    }
+}
+
+int fm_op_decode_attn_ex(int device, int precision, int kernel, const float* qkv, const float* slab, int kp,
+                         const float* bias, int R, int nh, int nkv, int hd, const float* qn, const float* kn,
+                         int qk_norm, float eps, float rope_base, const int* row_slot, const int* pos, int nslots,
+                         int layers, int layer, float* kcache, float* vcache, int S, int cap, int nwb, int frame,
+                         int reps, float* out, int* info) {
+    return fm_guard([&] {
+        FMCHECK((qkv != nullptr) != (slab != nullptr) && pos && kcache && vcache && out && info,
+                "need qkv or slab (one of them), positions, caches, out and info");
+        FMCHECK(!slab || (kp >= 1 && kp <= 16), "1 to 16 slab parts");
+        FMCHECK(!bias || slab, "a bias goes with the slab form");
+        FMCHECK(!qk_norm || (qn && kn), "qk_norm needs both norm weights");
+        FMCHECK(frame || kernel == 0 || kernel == 2 || kernel == 3,
+                "kernel must be 0 (attn_decode2), 2 (attn_dec3) or 3 (attn_fd)");
+        FMCHECK(R >= 1 && R <= 64 && nh >= 1 && nkv >= 1 && nh % nkv == 0 && nh / nkv <= 16, "bad rows / head counts");
+        FMCHECK(hd >= 32 && hd <= 128 && hd % 32 == 0, "head_dim a multiple of 32 up to 128");
+        FMCHECK(S >= 16 && S <= 65536 && reps >= 1 && reps <= 4, "bad S / reps");
+        FMCHECK(frame || (cap >= 16 && cap % 16 == 0 && (nwb == 4 || nwb == 8 || nwb == 16)), "bad cap / nwb");
+        check_slot_rows(R, row_slot, pos, nslots, layers, layer, S);
+        for (int r = 0; r < R; ++r)
+            for (int q = 0; q < r; ++q) FMCHECK(row_slot[q] != row_slot[r], "two rows in one slot");
+        StreamGuard g(device);
+        const DecodeAttnEx o{kernel, qkv, slab, kp, bias, R, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, row_slot, pos,
+                             nslots, layers, layer, kcache, vcache, S, cap, nwb, frame, reps, out, info};
+        if (precision == FM_PREC_BF16)
+            decode_attn_ex_t<bf16_t>(g.s, o);
+        else
+            decode_attn_ex_t<float>(g.s, o);
+    });
+}
+
+int fm_op_prompt_attn_ex(int device, int precision, int kernel, const float* q, int R, int nh, int nkv, int hd,
+                         const int* row_slot, const int* row_pos, int one_slot, int nslots, int layers, int layer,
+                         const float* kcache, const float* vcache, int S, float* out) {
+    return fm_guard([&] {
+        FMCHECK(q && row_pos && kcache && vcache && out, "null argument");
+        FMCHECK(kernel == 0 || kernel == 1, "kernel must be 0 (split + combine) or 1 (attn_prefill_kernel)");
+        FMCHECK(R >= 1 && R <= ATTN_PIECE && nh >= 1 && nkv >= 1 && nh % nkv == 0, "bad rows / head counts");
+        FMCHECK(hd >= 32 && hd <= 256 && hd % 32 == 0 && S >= 16 && S <= 65536, "bad head_dim / S");
+        check_slot_rows(R, row_slot, row_pos, nslots, layers, layer, S);
+        if (one_slot)
+            for (int r = 1; r < R; ++r)
+                FMCHECK(row_slot[r] == row_slot[0] && row_pos[r] == row_pos[0] + r, "one_slot: consecutive rows of one slot");
+        FMCHECK(kernel == 0 || (one_slot && precision == FM_PREC_BF16 && hd == 128 && nh / nkv <= 4),
+                "attn_prefill_kernel: rows of one slot, bf16, head_dim 128, at most 4 q heads per kv head");
+        StreamGuard g(device);
+        const SlotRows sr{row_slot, row_pos, nslots, layers, layer};
+        if (precision == FM_PREC_BF16)
+            prompt_attn_ex_t<bf16_t>(g.s, kernel, q, R, nh, nkv, hd, sr, one_slot, kcache, vcache, S, out);
+        else
+            prompt_attn_ex_t<float>(g.s, kernel, q, R, nh, nkv, hd, sr, one_slot, kcache, vcache, S, out);
+    });
+}
+
+int fm_op_qk_rope_cache(int device, int precision, const float* qkv, const float* slab, int kp, const float* bias, int R,
+                        int nh, int nkv, int hd, const float* qn, const float* kn, int qk_norm, float eps,
+                        float rope_base, const int* row_slot, const int* row_pos, int fixed_pos, int nslots, int layers,
+                        int layer, float* kcache, float* vcache, int S, float* q_out) {
+    return fm_guard([&] {
+        FMCHECK((qkv != nullptr) != (slab != nullptr) && kcache && vcache && q_out, "need qkv or slab (one of them), caches, q_out");
+        FMCHECK(!slab || (kp >= 1 && kp <= 16), "1 to 16 slab parts");
+        FMCHECK(!bias || slab, "a bias goes with the slab form");
+        FMCHECK(!qk_norm || (qn && kn), "qk_norm needs both norm weights");
+        FMCHECK(R >= 1 && R <= 1024 && nh >= 1 && nkv >= 1, "bad rows / head counts");
+        FMCHECK(hd >= 8 && hd <= 256 && hd % 8 == 0 && S >= 1 && S <= 65536, "bad head_dim / S");
+        FMCHECK((fixed_pos >= 0 && fixed_pos < S) || (fixed_pos < 0 && row_pos), "fixed_pos inside the cache, or row positions");
+        check_slot_rows(R, row_slot, fixed_pos >= 0 ? nullptr : row_pos, nslots, layers, layer, S);
+        StreamGuard g(device);
+        const SlotRows sr{row_slot, fixed_pos >= 0 ? nullptr : row_pos, nslots, layers, layer};
+        if (precision == FM_PREC_BF16)
+            qk_rope_cache_t<bf16_t>(g.s, qkv, slab, kp, bias, R, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, sr, fixed_pos,
+                                    kcache, vcache, S, q_out);
+        else
+            qk_rope_cache_t<float>(g.s, qkv, slab, kp, bias, R, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, sr, fixed_pos,
+                                   kcache, vcache, S, q_out);
+    });
+}
+
+int fm_op_fast_attn(int device, int precision, int kernel, const float* qkv, int R, int nh, int nkv, int hd,
+                    const float* qn, const float* kn, int qk_norm, float eps, float rope_base, const int* row_slot,
+                    int cpos, int nslots, int layers, int layer, float* kcache, float* vcache, int S, float* out) {
+    return fm_guard([&] {
+        FMCHECK(qkv && kcache && vcache && out, "null argument");
+        FMCHECK(!qk_norm || (qn && kn), "qk_norm needs both norm weights");
+        FMCHECK(kernel >= 0 && kernel <= 3,
+                "kernel must be 0 (fast_attn2), 1 (fast_attn2, noq), 2 (fast_attn_fused) or 3 (qk_rope_cache + fast_attn)");
+        FMCHECK(R >= 1 && R <= 64 && nh >= 1 && nkv >= 1 && nh % nkv == 0, "bad rows / head counts");
+        FMCHECK(hd >= 8 && hd <= 256 && hd % 8 == 0, "head_dim a multiple of 8 up to 256");
+        FMCHECK(S >= 1 && S <= 63 && cpos >= 0 && cpos < S, "1 to 63 codebooks, cpos among them");
+        FMCHECK(kernel > 1 || cpos < 16, "fast_attn2 positions are < 16");
+        FMCHECK(kernel != 1 || cpos == 0, "noq is the codebook-0 form");
+        FMCHECK(kernel != 2 || (size_t)2 * S * hd * 4 + (size_t)4 * hd * 4 + 1024 <= 64 * 1024, "fast_attn_fused: LDS tile too large");
+        check_slot_rows(R, row_slot, nullptr, nslots, layers, layer, S);
+        for (int r = 0; r < R; ++r)
+            for (int q = 0; q < r; ++q) FMCHECK(row_slot[q] != row_slot[r], "two rows in one slot");
+        StreamGuard g(device);
+        const SlotRows sr{row_slot, nullptr, nslots, layers, layer};
+        if (precision == FM_PREC_BF16)
+            fast_attn_t<bf16_t>(g.s, kernel, qkv, R, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, sr, cpos, kcache, vcache, S, out);
+        else
+            fast_attn_t<float>(g.s, kernel, qkv, R, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, sr, cpos, kcache, vcache, S, out);
+    });
+}
+
+int fm_op_fattn_wo(int device, int quant, int gs, int fused, const float* qkv, const float* qtab, int qrows,
+                   const int32_t* idx, int idx_n, int idx_col, int nh, int nkv, int hd, const float* qn, const float* kn,
+                   int qk_norm, float eps, float rope_base, int slot, int cpos, int nslots, int layers, int layer,
+                   float* kcache, float* vcache, int S, const float* w, const float* bias, const float* res,
+                   int res_rows, int ldr, const float* res0, int N, int kv0, int pair, int ilp, int gen, int pos0,
+                   const uint32_t* xt_init, float* y, int* status) {
+    return fm_guard([&] {
+        FMCHECK(qkv && kcache && vcache && w && res && y && status, "null argument");
+        FMCHECK(quant == FM_QUANT_NONE || quant == FM_QUANT_INT8 || quant == FM_QUANT_INT4, "bad quant");
+        FMCHECK(!qk_norm || (qn && kn), "qk_norm needs both norm weights");
+        FMCHECK(nh >= 1 && nkv >= 1 && nh % nkv == 0 && hd >= 8 && hd <= 128 && hd % 8 == 0, "bad heads / head_dim");
+        FMCHECK(S >= 1 && S <= 63 && cpos >= 0 && cpos < S && N >= 16 && N % 16 == 0, "bad S / cpos / N");
+        FMCHECK(quant == FM_QUANT_NONE || !bias, "the int8 / int4 row forms take no bias");
+        FMCHECK(quant != FM_QUANT_INT4 || (gs >= 8 && gs % 8 == 0 && (nh * hd) % gs == 0), "bad int4 group size");
+        FMCHECK(!idx || (idx_n >= 1 && idx_col >= 0 && idx_col < idx_n), "bad index column");
+        FMCHECK(res_rows >= 1 && ldr >= N && gen >= 1 && gen <= 40 && pos0 >= 0, "bad residual table / gen / position");
+        FMCHECK(!qtab || (idx && !kv0 && qrows >= 1 && qrows == res_rows), "the table form is gathered by the residual's index");
+        FMCHECK(!kv0 || (!idx && cpos == 0), "the K / V-only form runs at codebook 0, no gather");
+        FMCHECK(pair >= 0 && pair <= 2, "pair must be 0, 1 or 2");
+        FMCHECK(!pair || (fused && quant == FM_QUANT_NONE && !kv0 && cpos == 1 && (qtab != nullptr) == (idx != nullptr) &&
+                          (pair == 1 ? res0 != nullptr : !qtab)),
+                "pair form: fused, bf16, positions 0 and 1, row 0's residual (pair 1), no table in the last layer (pair 2)");
+        check_slot_rows(1, &slot, nullptr, nslots, layers, layer, S);
+        StreamGuard g(device);
+        const FattnWoOp o{quant, gs, fused, qkv, qtab, qrows, idx, idx_n, idx_col, nh, nkv, hd, qn, kn, qk_norm, eps,
+                          rope_base, slot, cpos, nslots, layers, layer, kcache, vcache, S, w, bias, res, res_rows, ldr,
+                          res0, N, kv0, pair, ilp, gen, pos0, xt_init, y, status};
+        fattn_wo_op(g.s, o);
     });
 }
 

@@ -98,6 +98,161 @@ def prompt_attn(q, nh, nkv, hd, pos0, kcache, vcache, precision="bf16", kernel="
     return out
 
 
+# ---- attention hooks on the model's cache layout [nslots][layers][nkv][S][hd] (tests/test_gpu_attn_ops.py) ----
+def _norm_w(qn, kn, hd):
+    qk = qn is not None
+    return (int(qk), np.ascontiguousarray(qn if qk else np.ones(hd), np.float32),
+            np.ascontiguousarray(kn if qk else np.ones(hd), np.float32))
+
+
+def _caches(kcache, vcache, nkv, hd):
+    kc = np.array(kcache, np.float32, order="C")  # copies: the hooks write them in place
+    vc = np.array(vcache, np.float32, order="C")
+    assert kc.ndim == 5 and kc.shape[2] == nkv and kc.shape[4] == hd and vc.shape == kc.shape, kc.shape
+    return kc, vc
+
+
+def _opt(a):
+    return None if a is None else native.f32p(a)
+
+
+def _raw_or_slab(qkv, slab, bias, ld):
+    """(raw, slab, kp, bias, R) as contiguous fp32 arrays (None where not given)."""
+    assert (qkv is None) != (slab is None)
+    raw = None if qkv is None else np.ascontiguousarray(qkv, np.float32)
+    sl = None if slab is None else np.ascontiguousarray(slab, np.float32)
+    bi = None if bias is None else np.ascontiguousarray(bias, np.float32).reshape(ld)
+    if raw is not None:
+        assert raw.ndim == 2 and raw.shape[1] == ld
+        return raw, None, 1, None, raw.shape[0]
+    assert sl.ndim == 3 and sl.shape[2] == ld
+    return None, sl, sl.shape[0], bi, sl.shape[1]
+
+
+def decode_attn_ex(nh, nkv, hd, row_slot, pos, kcache, vcache, rope_base, qkv=None, slab=None, bias=None, qn=None,
+                   kn=None, eps=1e-6, layer=0, precision="bf16", kernel="fd", cap=32, nwb=4, frame=False, reps=1,
+                   device=0):
+    """fm_op_decode_attn_ex: the slow decode attention on rows in slots row_slot of caches (nslots, layers, nkv, S, hd),
+    from qkv (R, ld) or slab (kp, R, ld) + bias.  frame=True: kernel / nwb / cap as a frame of R rows launches them.
+    Returns (out (R, nh, hd), kcache, vcache, info) with info = dict(kernel, nwb, cap, splits, tickets, guard_ok,
+    fd_nsp, cap2)."""
+    ld = (nh + 2 * nkv) * hd
+    raw, sl, kp, bi, R = _raw_or_slab(qkv, slab, bias, ld)
+    kc, vc = _caches(kcache, vcache, nkv, hd)
+    nslots, layers, _, S, _ = kc.shape
+    rs = np.ascontiguousarray(row_slot, np.int32)
+    p = np.ascontiguousarray(pos, np.int32)
+    assert rs.shape == (R,) and p.shape == (R,)
+    qk, qn_, kn_ = _norm_w(qn, kn, hd)
+    out = np.zeros((R, nh, hd), np.float32)
+    info = np.zeros(8, np.int32)
+    native.check(native.lib().fm_op_decode_attn_ex(
+        device, _prec(precision), ATTN_KERNELS[kernel], _opt(raw), _opt(sl), kp, _opt(bi), R, nh, nkv, hd,
+        native.f32p(qn_), native.f32p(kn_), qk, float(eps), float(rope_base), native.i32p(rs), native.i32p(p), nslots,
+        layers, int(layer), native.f32p(kc), native.f32p(vc), S, int(cap), int(nwb), int(frame), int(reps),
+        native.f32p(out), native.i32p(info)))
+    names = ("kernel", "nwb", "cap", "splits", "tickets", "guard_ok", "fd_nsp", "cap2")
+    d = dict(zip(names, (int(v) for v in info)))
+    d["kernel"] = {v: k for k, v in ATTN_KERNELS.items()}[d["kernel"]]
+    return out, kc, vc, d
+
+
+def prompt_attn_ex(q, nh, nkv, hd, row_slot, row_pos, kcache, vcache, one_slot, layer=0, precision="bf16",
+                   kernel="split", device=0):
+    """fm_op_prompt_attn_ex: prompt rows q (R, nh*hd) with their own (slot, position) over caches (nslots, layers,
+    nkv, S, hd); one_slot=False is the many-slot split + combine route."""
+    qq = np.ascontiguousarray(q, np.float32)
+    R = qq.shape[0]
+    kc, vc = _caches(kcache, vcache, nkv, hd)
+    nslots, layers, _, S, _ = kc.shape
+    rs = np.ascontiguousarray(row_slot, np.int32)
+    rp = np.ascontiguousarray(row_pos, np.int32)
+    assert qq.shape == (R, nh * hd) and rs.shape == (R,) and rp.shape == (R,)
+    out = np.zeros((R, nh, hd), np.float32)
+    native.check(native.lib().fm_op_prompt_attn_ex(
+        device, _prec(precision), {"split": 0, "flash": 1}[kernel], native.f32p(qq), R, nh, nkv, hd, native.i32p(rs),
+        native.i32p(rp), int(one_slot), nslots, layers, int(layer), native.f32p(kc), native.f32p(vc), S,
+        native.f32p(out)))
+    return out
+
+
+def qk_rope_cache(nh, nkv, hd, row_slot, kcache, vcache, rope_base, row_pos=None, fixed_pos=-1, qkv=None, slab=None,
+                  bias=None, qn=None, kn=None, eps=1e-6, layer=0, precision="bf16", device=0):
+    """fm_op_qk_rope_cache: the prefill's QK-norm + RoPE + cache write.  Returns (q (R, nh, hd), kcache, vcache)."""
+    ld = (nh + 2 * nkv) * hd
+    raw, sl, kp, bi, R = _raw_or_slab(qkv, slab, bias, ld)
+    kc, vc = _caches(kcache, vcache, nkv, hd)
+    nslots, layers, _, S, _ = kc.shape
+    rs = np.ascontiguousarray(row_slot, np.int32)
+    rp = np.ascontiguousarray(row_pos if row_pos is not None else np.zeros(R), np.int32)
+    assert rs.shape == (R,) and rp.shape == (R,) and (fixed_pos >= 0 or row_pos is not None)
+    qk, qn_, kn_ = _norm_w(qn, kn, hd)
+    q = np.zeros((R, nh, hd), np.float32)
+    native.check(native.lib().fm_op_qk_rope_cache(
+        device, _prec(precision), _opt(raw), _opt(sl), kp, _opt(bi), R, nh, nkv, hd, native.f32p(qn_), native.f32p(kn_),
+        qk, float(eps), float(rope_base), native.i32p(rs), native.i32p(rp), int(fixed_pos), nslots, layers, int(layer),
+        native.f32p(kc), native.f32p(vc), S, native.f32p(q)))
+    return q, kc, vc
+
+
+FAST_ATTN_KERNELS = {"attn2": 0, "attn2_noq": 1, "fused": 2, "unfused": 3}
+
+
+def fast_attn(qkv, nh, nkv, hd, row_slot, cpos, kcache, vcache, rope_base, qn=None, kn=None, eps=1e-6, layer=0,
+              precision="bf16", kernel="attn2", device=0):
+    """fm_op_fast_attn: the fast decoder's attention at codebook position cpos on rows in slots row_slot of caches
+    (nslots, layers, nkv, S = num_codebooks, hd).  kernel: "attn2" fast_attn2_kernel, "attn2_noq" its K/V-only form
+    (cpos 0), "fused" fast_attn_fused_kernel, "unfused" qk_rope_cache(fixed_pos) + fast_attn_kernel.
+    Returns (out (R, nh, hd), kcache, vcache)."""
+    raw = np.ascontiguousarray(qkv, np.float32)
+    R = raw.shape[0]
+    assert raw.shape == (R, (nh + 2 * nkv) * hd)
+    kc, vc = _caches(kcache, vcache, nkv, hd)
+    nslots, layers, _, S, _ = kc.shape
+    rs = np.ascontiguousarray(row_slot, np.int32)
+    assert rs.shape == (R,)
+    qk, qn_, kn_ = _norm_w(qn, kn, hd)
+    out = np.zeros((R, nh, hd), np.float32)
+    native.check(native.lib().fm_op_fast_attn(
+        device, _prec(precision), FAST_ATTN_KERNELS[kernel], native.f32p(raw), R, nh, nkv, hd, native.f32p(qn_),
+        native.f32p(kn_), qk, float(eps), float(rope_base), native.i32p(rs), int(cpos), nslots, layers, int(layer),
+        native.f32p(kc), native.f32p(vc), S, native.f32p(out)))
+    return out, kc, vc
+
+
+def fattn_wo(qkv, nh, nkv, hd, slot, cpos, kcache, vcache, rope_base, w, res, bias=None, qn=None, kn=None, eps=1e-6,
+             layer=0, quant=0, gs=128, fused=True, qtab=None, idx=None, idx_col=0, res0=None, kv0=False, pair=0, ilp=1,
+             gen=1, pos0=0, xt_init=None, device=0):
+    """fm_op_fattn_wo: the batch-1 fast decoder's attention + wo in one launch (fused) or as fast_attn2 + row GEMV.
+    qkv (1 or 2, ld); w (N, nh*hd); res (res_rows, ldr) the residual table (row idx[idx_col], or row 0).  Returns
+    (y (N,) or (2, N) for pair 1, kcache, vcache, ok, err): ok False = not dispatchable, nothing was launched."""
+    raw = np.ascontiguousarray(qkv, np.float32).reshape(-1, (nh + 2 * nkv) * hd)
+    assert raw.shape[0] == (2 if pair else 1)
+    kc, vc = _caches(kcache, vcache, nkv, hd)
+    nslots, layers, _, S, _ = kc.shape
+    ww = np.ascontiguousarray(w, np.float32)
+    N = ww.shape[0]
+    assert ww.shape == (N, nh * hd)
+    rr = np.ascontiguousarray(res, np.float32).reshape(-1, np.shape(res)[-1])
+    qt = None if qtab is None else np.ascontiguousarray(qtab, np.float32)
+    ix = None if idx is None else np.ascontiguousarray(idx, np.int32)
+    bi = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    r0 = None if res0 is None else np.ascontiguousarray(res0, np.float32)
+    xt = None if xt_init is None else np.ascontiguousarray(xt_init, np.uint32)
+    assert xt is None or xt.shape == (2 * nh * hd,)
+    qk, qn_, kn_ = _norm_w(qn, kn, hd)
+    y = np.zeros((2, N) if pair == 1 else (N,), np.float32)
+    status = np.zeros(2, np.int32)
+    native.check(native.lib().fm_op_fattn_wo(
+        device, int(quant), int(gs), int(fused), native.f32p(raw), _opt(qt), 0 if qt is None else qt.shape[0],
+        None if ix is None else native.i32p(ix), 0 if ix is None else ix.size, int(idx_col), nh, nkv, hd,
+        native.f32p(qn_), native.f32p(kn_), qk, float(eps), float(rope_base), int(slot), int(cpos), nslots, layers,
+        int(layer), native.f32p(kc), native.f32p(vc), S, native.f32p(ww), _opt(bi), native.f32p(rr), rr.shape[0],
+        rr.shape[1], _opt(r0), N, int(kv0), int(pair), int(ilp), int(gen), int(pos0),
+        None if xt is None else xt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), native.f32p(y), native.i32p(status)))
+    return y, kc, vc, bool(status[0]), int(status[1])
+
+
 def embed(tok, emb, cbemb, num_codebooks, codebook_size, semantic_begin_id, semantic_end_id, scale,
           precision="bf16", device=0):
     """tok: (R, C+1) rows (row r = one position's [text/semantic token, codes...])."""

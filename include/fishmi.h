@@ -339,6 +339,55 @@ int fm_op_decode_attn(int device, int precision, int kernel, const float* qkv, i
    per kv head).  out [R][nh * hd]. */
 int fm_op_prompt_attn(int device, int precision, int kernel, const float* q, int R, int nh, int nkv, int hd, int pos0,
                       const float* kcache, const float* vcache, int S, float* out);
+/* Attention hooks with the cache as the model lays it out (tests/test_gpu_attn_ops.py): kcache / vcache are
+   [nslots][layers][nkv][S][hd], row r works on slot row_slot[r] (distinct where the kernel writes the cache) and
+   layer `layer`; the caches are in/out where the kernel writes them, so the caller sees every word of them.
+
+   fm_op_decode_attn_ex: fm_op_decode_attn with the launch forms of the frame.  Input qkv [R][ld], ld = (nh + 2 nkv) hd,
+   or (attn_fd only) slab [kp][R][ld] fp32 K-part slabs + optional bias [ld], read as round(sum + bias).  attn_fd runs
+   with nwb (4, 8, 16) waves per block and splits of at least cap positions; attn_decode2 with min(cap, its LDS
+   budget) rows per block.  frame != 0: kernel, nwb and cap are what a decode frame of R rows launches under the
+   current fm_tune knobs (kernel, cap, nwb arguments ignored).  reps launches on the same scratch.  The split
+   partials are allocated at the documented size, poisoned, with a guard region behind them.
+   info[8] out: {kernel run, nwb, cap, splits (grid z), ticket words left non-zero, guard intact (1 / 0), FD_NSP (most
+   attn_fd splits), attn_decode2's LDS-budget cap}. */
+int fm_op_decode_attn_ex(int device, int precision, int kernel, const float* qkv, const float* slab, int kp,
+                         const float* bias, int R, int nh, int nkv, int hd, const float* qn, const float* kn,
+                         int qk_norm, float eps, float rope_base, const int* row_slot, const int* pos, int nslots,
+                         int layers, int layer, float* kcache, float* vcache, int S, int cap, int nwb, int frame,
+                         int reps, float* out, int* info);
+/* fm_op_prompt_attn on rows with their own (slot, position): one_slot != 0 says they are consecutive rows of one
+   slot (what attn_prefill_kernel, kernel 1, needs); one_slot == 0 is the many-slot split + combine route. */
+int fm_op_prompt_attn_ex(int device, int precision, int kernel, const float* q, int R, int nh, int nkv, int hd,
+                         const int* row_slot, const int* row_pos, int one_slot, int nslots, int layers, int layer,
+                         const float* kcache, const float* vcache, int S, float* out);
+/* The prefill's QK-norm + RoPE + cache write (qk_rope_cache_kernel) on R rows at row_pos[r], or all at fixed_pos
+   (>= 0; the fast decoder's form); input qkv or slabs + bias as fm_op_decode_attn_ex.  q_out [R][nh * hd]. */
+int fm_op_qk_rope_cache(int device, int precision, const float* qkv, const float* slab, int kp, const float* bias, int R,
+                        int nh, int nkv, int hd, const float* qn, const float* kn, int qk_norm, float eps,
+                        float rope_base, const int* row_slot, const int* row_pos, int fixed_pos, int nslots, int layers,
+                        int layer, float* kcache, float* vcache, int S, float* q_out);
+/* The fast decoder's attention (llama.py:947-975) at codebook position cpos of S = num_codebooks on R rows:
+   kernel 0 = fast_attn2, 1 = fast_attn2 with noq (cpos 0: the Q part of qkv is not read), 2 = fast_attn_fused,
+   3 = qk_rope_cache(fixed_pos) + fast_attn_kernel (the unfused pair).  out [R][nh * hd]. */
+int fm_op_fast_attn(int device, int precision, int kernel, const float* qkv, int R, int nh, int nkv, int hd,
+                    const float* qn, const float* kn, int qk_norm, float eps, float rope_base, const int* row_slot,
+                    int cpos, int nslots, int layers, int layer, float* kcache, float* vcache, int S, float* out);
+/* The batch-1 fast decoder's attention + wo at codebook position cpos of slot `slot` (bf16 attention; wo in bf16,
+   int8 or int4: quant FM_QUANT_*, gs the int4 group size).  fused != 0: ONE launch_fattn_wo; fused == 0: the launches
+   it replaces on the same device operands (fast_attn2 + the row GEMV, FIN).  qkv [1 or (pair) 2][ld]; qtab
+   [qrows][ld] or NULL: the QKV table, row idx[idx_col] clamped into it; idx also gathers the residual row of res
+   [res_rows][ldr] (NULL: row 0); kv0: the K / V-only form of codebook 0 (the Q part of qkv is not read); pair 1 / 2:
+   codebooks 0 and 1 in one launch (res0 [N]: row 0's residual for pair 1; y [2][N]), else y [N]; ilp: fm_tune
+   fattn_ilp; gen (1..40) and pos0 make the hand-off tag; xt_init [2 nh hd] or NULL pre-fills the tagged words.
+   w [N][nh hd], bias [N] or NULL.  status[2] out: {dispatchable (fattn_wo_ok, fattn_wo_dead_ok for the table and
+   K / V-only forms, the pair form's depth: 0 = nothing was launched), the err word after the launch}. */
+int fm_op_fattn_wo(int device, int quant, int gs, int fused, const float* qkv, const float* qtab, int qrows,
+                   const int32_t* idx, int idx_n, int idx_col, int nh, int nkv, int hd, const float* qn, const float* kn,
+                   int qk_norm, float eps, float rope_base, int slot, int cpos, int nslots, int layers, int layer,
+                   float* kcache, float* vcache, int S, const float* w, const float* bias, const float* res,
+                   int res_rows, int ldr, const float* res0, int N, int kv0, int pair, int ilp, int gen, int pos0,
+                   const uint32_t* xt_init, float* y, int* status);
 /* Dual-AR input embedding (llama.py:399-420): tok R x (C+1) row-major, x R x dim. */
 int fm_op_embed(int device, int precision, const int32_t* tok, int R, const float* emb, int vocab,
                 const float* cbemb, int dim, int num_codebooks, int codebook_size, int semantic_begin_id,

@@ -14,7 +14,11 @@ within 4 fp32 ulp per element: the mean of squares is summed in a different orde
 vectorised CPU reduction (and torch.rms_norm's fused kernel for the QK-norm), so 1/rms differs in
 its last bits and fp32 bit-exactness is not reachable there (measured on MI355X: RMSNorm 84.8%
 and QK-norm 75% of elements bit-exact, max 3 ulp; RoPE and the embedding 100% bit-exact).  The
-share of bit-exact elements is printed and asserted from below."""
+share of bit-exact elements is printed and asserted from below.
+
+The attention kernels' launch forms (waves per block, the frame's own plan, slot and layer indirection, the slab
+input, the fast decoder's kernels) on steered and poisoned operands are in tests/test_gpu_attn_ops.py; the two
+attention tests here stay as the N(0,1) baseline."""
 import numpy as np
 import pytest
 
