@@ -609,35 +609,45 @@ template <typename T> __device__ __forceinline__ typename Frag<T>::f frag_f32(co
 // NW waves per block (4, 8 or 16): 16 NW positions per pass.  The batch-1 launches use wide blocks
 // and long splits, so below fd_min16 cached positions one block per kv head needs no cross-block
 // combine.
-template <typename T, int HD, int NW>
+// GM (1, 2 or FD_GM) q heads of a kv head per block (fm_tune fd_hpb at R <= 8, FD_GM elsewhere): head
+// group hg = blockIdx.z / maxsplit, split sp = blockIdx.z % maxsplit, so the linear block index
+// modulo nkv is still kvh (R = 1: the XCD whose L2 kv_prefetch filled).  A head's scores (MFMA row
+// 4 x its index in the group), softmax (its 16-lane row), PV, wave fold and split combine never meet
+// another head's values: every output bit is the same under each GM.  Every group's owner block
+// prepares the new k / v in its LDS; group 0's alone stores them.  One ticket per (row, kv head,
+// group): a.cnt holds [R][nh] words.
+template <typename T, int HD, int NW, int GM>
 __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
+    static_assert(GM == 1 || GM == 2 || GM == FD_GM, "1, 2 or every q head of the kv head");
     static_assert(HD % 32 == 0 && HD <= 128, "head_dim a multiple of 32 up to 128");
     constexpr int NT = NW * 64, FD_TILE = 16 * NW;
     constexpr int VL = 8 * (int)sizeof(T) / 16;     // 16-B loads per V slice
     constexpr int half = HD / 2;
-    __shared__ __attribute__((aligned(16))) float q_s[FD_GM][HD];
+    __shared__ __attribute__((aligned(16))) float q_s[GM][HD];
     __shared__ __attribute__((aligned(16))) float kv_new[2][HD];
-    __shared__ __attribute__((aligned(16))) float wml[NW][FD_GM][2];
+    __shared__ __attribute__((aligned(16))) float wml[NW][GM][2];
     // PV partials [wave][V position group][head][dim]; 16 waves fold the 4 groups by shuffles first
     constexpr int OG = NW > 4 ? 1 : 4;
-    __shared__ __attribute__((aligned(16))) float ored[NW][OG][FD_GM][HD];
+    __shared__ __attribute__((aligned(16))) float ored[NW][OG][GM][HD];
     __shared__ int flag;
     unsigned long long tz[7] = {0, 0, 0, 0, 0, 0, 0};
     DBG_TS(tz, 0)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l16 = lane & 15, qq = lane >> 4;
-    const int r = blockIdx.x, kvh = blockIdx.y, sp = blockIdx.z;
-    const int g = a.nh / a.nkv, nitem = g + 2;
+    const int r = blockIdx.x, kvh = blockIdx.y;
+    const int hg = GM == FD_GM ? 0 : (int)blockIdx.z / a.maxsplit, sp = (int)blockIdx.z - hg * a.maxsplit;
+    // this block's q heads: h0 .. h0 + g of the model's (g < GM in a ragged last group)
+    const int g = min(GM, a.nh / a.nkv - hg * GM), h0 = kvh * (a.nh / a.nkv) + hg * GM, nitem = g + 2;
     // ---- round trip 1: slot, pos and this wave's raw rows (q heads, then new k, new v); the raw
     // loads do not depend on pos and go out with it (clamped, unconditional)
     const int slot = a.row_slot[r];
     const int pos = a.row_pos[r];
-    constexpr int NI = (2 + FD_GM + NW - 1) / NW;  // q heads + new k + new v over the waves
+    constexpr int NI = (2 + GM + NW - 1) / NW;  // q heads + new k + new v over the waves
     float x0[NI], x1[NI];
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int it = wave + NW * i;
-        const int row = it < g ? kvh * g + it : (it == g ? a.nh + kvh : a.nh + a.nkv + kvh);
+        const int row = it < g ? h0 + it : (it == g ? a.nh + kvh : a.nh + a.nkv + kvh);
         const bool ok = it < nitem && lane < half;
         float v0, v1;
         raw_pair<T>(a.qkv, a.ldqkv, a.qslab, a.qslab_kp, gridDim.x, a.qbias, r,
@@ -646,7 +656,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
         x1[i] = ok ? v1 : 0.f;
     }
     const int npos = pos + 1;
-    int nsp = min((int)gridDim.z, (npos + a.cap - 1) / a.cap);
+    int nsp = min(a.maxsplit, (npos + a.cap - 1) / a.cap);
     const int chunk = ((npos + nsp - 1) / nsp + 15) & ~15;
     nsp = (npos + chunk - 1) / chunk;
     if (sp >= nsp) return;
@@ -705,16 +715,18 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
                 q_s[it][2 * lane] = y0;
                 q_s[it][2 * lane + 1] = y1;
                 if (a.qdbg && sp == 0) {  // per-op test hook only
-                    float* qdp = a.qdbg + ((size_t)r * a.nh + kvh * g + it) * HD;
+                    float* qdp = a.qdbg + ((size_t)r * a.nh + h0 + it) * HD;
                     qdp[2 * lane] = y0;
                     qdp[2 * lane + 1] = y1;
                 }
             } else {
                 kv_new[isk ? 0 : 1][2 * lane] = y0;
                 kv_new[isk ? 0 : 1][2 * lane + 1] = y1;
-                T* dst = (isk ? kc : vc) + (size_t)pos * HD;
-                st(dst, 2 * lane, y0);
-                st(dst, 2 * lane + 1, y1);
+                if (hg == 0) {  // one writer per (row, kv head)
+                    T* dst = (isk ? kc : vc) + (size_t)pos * HD;
+                    st(dst, 2 * lane, y0);
+                    st(dst, 2 * lane + 1, y1);
+                }
             }
         }
     }
@@ -729,16 +741,16 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
     for (int ks = 0; ks < NKS; ++ks) {
         float qv[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) qv[e] = qrow ? q_s[qh][32 * ks + 8 * qq + e] : 0.f;
+        for (int e = 0; e < 8; ++e) qv[e] = qrow ? q_s[qh < GM ? qh : 0][32 * ks + 8 * qq + e] : 0.f;
         qa[ks] = frag_f32<T>(qv);
     }
     // ---- passes: S = Q K^T of the wave's 16 positions on one MFMA chain (lane (l16, qq): head qq,
     // position l16), online softmax per head = per 16-lane row (DPP), P through the wave's LDS rows,
     // P V on the VALU in fp32 (lane: positions 4 it + qq, dims vd, every head)
-    __shared__ __attribute__((aligned(16))) float p_s[NW][16][FD_GM];
-    float m_run = -INFINITY, l_run = 0.f, o[FD_GM][8];
+    __shared__ __attribute__((aligned(16))) float p_s[NW][16][GM];
+    float m_run = -INFINITY, l_run = 0.f, o[GM][8];
 #pragma unroll
-    for (int h = 0; h < FD_GM; ++h)
+    for (int h = 0; h < GM; ++h)
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[h][e] = 0.f;
     const int npass = (jend - j0 + FD_TILE - 1) / FD_TILE;
@@ -779,9 +791,9 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
             const float p = kval ? expf(sv - mnew) : 0.f;
             m_run = mnew;
             l_run = l_run * alpha + p;
-            p_s[wave][l16][qq] = p;
+            if (GM == FD_GM || qq < GM) p_s[wave][l16][qq] = p;
 #pragma unroll
-            for (int h = 0; h < FD_GM; ++h) {
+            for (int h = 0; h < GM; ++h) {
                 if (h >= g) break;
                 const float ah = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(alpha), 16 * h));
 #pragma unroll
@@ -791,9 +803,18 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
         __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const f32x4_t pv = *reinterpret_cast<const f32x4_t*>(&p_s[wave][4 * it + qq][0]);
+            float pv[GM];
+            if constexpr (GM == 4) {
+                const f32x4_t t = *reinterpret_cast<const f32x4_t*>(&p_s[wave][4 * it + qq][0]);
+                pv[0] = t[0], pv[1] = t[1], pv[2] = t[2], pv[3] = t[3];
+            } else if constexpr (GM == 2) {
+                const float2 t = *reinterpret_cast<const float2*>(&p_s[wave][4 * it + qq][0]);
+                pv[0] = t.x, pv[1] = t.y;
+            } else {
+                pv[0] = p_s[wave][4 * it + qq][0];
+            }
 #pragma unroll
-            for (int h = 0; h < FD_GM; ++h) {
+            for (int h = 0; h < GM; ++h) {
                 if (h >= g) break;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[h][e] += pv[h] * vf[it][e];
@@ -802,6 +823,10 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
         __builtin_amdgcn_wave_barrier();  // p_s is rewritten by the next pass
     }
     DBG_TS(tz, 2)
+    // (developer stamps: every wave's pass end, so that the record separates the passes of the
+    // block's slowest wave from the fold; thread 0's own stamps hold its wait for that wave)
+    __shared__ unsigned long long wend[NW];
+    if (a.dbg && lane == 0) wend[wave] = __builtin_amdgcn_s_memrealtime();
     // ---- fold the block's waves: PV partials of the 4 V position groups through LDS (no
     // cross-row shuffles), (max, sum) per wave and head
     const float lrow = row_sum16(l_run);  // row qq: head qq's sum
@@ -810,7 +835,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
         wml[wave][qq][1] = lrow;
     }
 #pragma unroll
-    for (int h = 0; h < FD_GM; ++h) {
+    for (int h = 0; h < GM; ++h) {
         if (h >= g) break;
         if constexpr (OG == 1) {
 #pragma unroll
@@ -842,9 +867,9 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
                 O += sc * ored[w][0][h][e];
         }
         if (single) {
-            st(a.out + (size_t)r * a.nh * HD + (size_t)(kvh * g + h) * HD, e, O / L);
+            st(a.out + (size_t)r * a.nh * HD + (size_t)(h0 + h) * HD, e, O / L);
         } else {  // write-through (sc1): read back by the combining block without a fence
-            float* pp = a.part + (((size_t)r * a.nh + (size_t)kvh * g + h) * a.maxsplit + sp) * (HD + 2);
+            float* pp = a.part + (((size_t)r * a.nh + h0 + h) * a.maxsplit + sp) * (HD + 2);
             __hip_atomic_store(pp + 2 + e, O, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (e == 0) {
                 __hip_atomic_store(pp, M, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -854,32 +879,34 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
     }
     if (a.dbg && threadIdx.x == 0) {
         tz[4] = __builtin_amdgcn_s_memrealtime();
+        for (int w = 0; w < NW; ++w) tz[6] = wend[w] > tz[6] ? wend[w] : tz[6];  // the last wave's pass end
         dbg_record(a.dbg, 0xFFFC, (unsigned)(nsp << 16 | (jend - j0)), tz);
     }
     if (single) return;
-    // ---- split combine by the last-arriving block of (row, kv head): sc1 partial stores drained by
+    // ---- split combine by the last-arriving block of (row, kv head, head group): sc1 partial stores drained by
     // every wave, a relaxed agent ticket, sc1 loads in the combiner (MI355X_MICROARCH.md hand-off
     // table, first row; no release / acquire fence)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-        const int t = __hip_atomic_fetch_add(a.cnt + (size_t)r * a.nkv + kvh, 1, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
+        int* tk = a.cnt + (size_t)r * a.nh + kvh * (a.nh / a.nkv) + hg;
+        const int t = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         flag = t == nsp - 1;
-        if (t == nsp - 1) __hip_atomic_store(a.cnt + (size_t)r * a.nkv + kvh, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t == nsp - 1) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
     if (!flag) return;
     DBG_TS(tz, 5)
     // lane q of a 16-lane group holds split q; group grp owns PP consecutive (dim pair) items of one
-    // head.  Every load is unconditional (split index clamped) and issued before any is used.
-    constexpr int PP = FD_GM * HD * 8 / NT;
+    // head (fewer items than groups: one each, the groups past them leave).  Every load is
+    // unconditional (split index clamped) and issued before any is used.
+    constexpr int PP = GM * HD * 8 / NT > 0 ? GM * HD * 8 / NT : 1;
     const int q = l16, grp = threadIdx.x >> 4;
     const int k0 = grp * PP, h = k0 / half, e0 = 2 * (k0 - h * half);
     if (h >= g) return;  // whole 16-lane groups
     const int qc = q < nsp ? q : nsp - 1;
     const unsigned long long* pp = reinterpret_cast<const unsigned long long*>(
-        a.part + (((size_t)r * a.nh + (size_t)kvh * g + h) * a.maxsplit + qc) * (HD + 2));
+        a.part + (((size_t)r * a.nh + h0 + h) * a.maxsplit + qc) * (HD + 2));
     const unsigned long long ml = __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     unsigned long long ov[PP];
 #pragma unroll
@@ -893,7 +920,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fd_kernel(AttnDecArgs<T> a) {
     float L = w * lq;
 #pragma unroll
     for (int m = 1; m < 16; m <<= 1) L += __shfl_xor(L, m);
-    T* out = a.out + (size_t)r * a.nh * HD + (size_t)(kvh * g + h) * HD + e0;
+    T* out = a.out + (size_t)r * a.nh * HD + (size_t)(h0 + h) * HD + e0;
 #pragma unroll
     for (int j = 0; j < PP; ++j) {
         float o0 = w * __uint_as_float((unsigned)ov[j]), o1 = w * __uint_as_float((unsigned)(ov[j] >> 32));
@@ -1732,33 +1759,33 @@ template <typename T> void launch_attn_decode2(hipStream_t s, const AttnDecArgs<
     }
     attn_decode2_kernel<T><<<g1, 512, attn2_lds_bytes(a.hd, a.nh / a.nkv, a.cap, sizeof(T)), s>>>(a);
 }
+template <typename T, int NW, int GM> static void attn_fd_go(hipStream_t s, const AttnDecArgs<T>& a, int R) {
+    const dim3 grid(R, a.nkv, a.maxsplit * FM_CEIL(a.nh / a.nkv, GM));
+    switch (a.hd) {
+        case 32: attn_fd_kernel<T, 32, NW, GM><<<grid, NW * 64, 0, s>>>(a); break;
+        case 64: attn_fd_kernel<T, 64, NW, GM><<<grid, NW * 64, 0, s>>>(a); break;
+        default: attn_fd_kernel<T, 128, NW, GM><<<grid, NW * 64, 0, s>>>(a); break;
+    }
+}
+template <typename T, int NW> static void attn_fd_hpb(hipStream_t s, const AttnDecArgs<T>& a, int R) {
+    switch (a.hpb) {
+        case 1: attn_fd_go<T, NW, 1>(s, a, R); break;
+        case 2: attn_fd_go<T, NW, 2>(s, a, R); break;
+        default: attn_fd_go<T, NW, FD_GM>(s, a, R); break;
+    }
+}
 template <typename T> void launch_attn_fd(hipStream_t s, const AttnDecArgs<T>& a0, int R) {
     FMCHECK(attn_fd_ok(a0.hd, a0.nh / a0.nkv), "attn_fd: head_dim 32, 64 or 128 and at most 4 q heads per kv head");
     FMCHECK(a0.cap >= 16 && a0.cnt && a0.part && a0.out, "attn_fd: min split >= 16, tickets, partials and output set");
+    FMCHECK(a0.hpb == 1 || a0.hpb == 2 || a0.hpb == FD_GM, "attn_fd: 1, 2 or 4 q heads per block");
     AttnDecArgs<T> a = a0;
     a.maxsplit = std::min(FD_NSP, FM_CEIL(a.S, a.cap));
-    const dim3 grid(R, a.nkv, a.maxsplit);
-    if (a.nwb == 16) {
-        switch (a.hd) {
-            case 32: attn_fd_kernel<T, 32, 16><<<grid, 1024, 0, s>>>(a); break;
-            case 64: attn_fd_kernel<T, 64, 16><<<grid, 1024, 0, s>>>(a); break;
-            default: attn_fd_kernel<T, 128, 16><<<grid, 1024, 0, s>>>(a); break;
-        }
-        return;
-    }
-    if (a.nwb == 8) {
-        switch (a.hd) {
-            case 32: attn_fd_kernel<T, 32, 8><<<grid, 512, 0, s>>>(a); break;
-            case 64: attn_fd_kernel<T, 64, 8><<<grid, 512, 0, s>>>(a); break;
-            default: attn_fd_kernel<T, 128, 8><<<grid, 512, 0, s>>>(a); break;
-        }
-        return;
-    }
-    switch (a.hd) {
-        case 32: attn_fd_kernel<T, 32, 4><<<grid, 256, 0, s>>>(a); break;
-        case 64: attn_fd_kernel<T, 64, 4><<<grid, 256, 0, s>>>(a); break;
-        default: attn_fd_kernel<T, 128, 4><<<grid, 256, 0, s>>>(a); break;
-    }
+    if (a.nwb == 16)
+        attn_fd_hpb<T, 16>(s, a, R);
+    else if (a.nwb == 8)
+        attn_fd_hpb<T, 8>(s, a, R);
+    else
+        attn_fd_hpb<T, 4>(s, a, R);
 }
 template <typename T> void launch_attn_decode3(hipStream_t s, const AttnDecArgs<T>& a0, int R) {
     FMCHECK(a0.hd % 32 == 0 && a0.hd <= 128 && a0.nh % a0.nkv == 0 && a0.nh / a0.nkv <= 6,

@@ -521,11 +521,12 @@ template <typename T> struct AttnDecArgs {
     float* part;         // [R][nh][maxsplit][hd+2]
     // attn_decode2 only
     int cap;             // rows per block
-    int* cnt;            // [R][nkv] arrival tickets (zeroed at allocation, reset by the last block)
+    int* cnt;            // arrival tickets [R][nkv] (attn_fd: [R][nh]), zeroed at allocation, reset by the last block
     T* out;              // [R][nh*hd]
     unsigned long long* dbg;  // developer timestamps (fm_tune "debug_ts")
     float* qdbg = nullptr;    // per-op test hook (fm_op_qk_rope): q after qk-norm + RoPE [R][nh][hd]
     int nwb = 4;              // attn_fd: waves per block (4, 8 or 16; 16 nwb positions per pass)
+    int hpb = 4;              // attn_fd: q heads of a kv head per block (1, 2, or 4 = all of them; fm_tune fd_hpb)
     const float* qslab = nullptr;  // as FastFusedArgs: K-part slabs of the QKV projection (attn_fd)
     int qslab_kp = 1;
     const T* qbias = nullptr;
@@ -549,7 +550,8 @@ inline int attn2_cap(int hd, int g, size_t esz) {
 // maxsplit set by the launcher (ceil(S / 64)); a.part must hold [R][nh][ceil(S / 64)][hd + 2]
 // flash-decode attention (fm_attn.hip attn_fd_kernel), every batch size: splits of at least a.cap
 // (>= 16) positions, at most FD_NSP per (row, kv head); maxsplit set by the launcher; a.part must
-// hold [R][nh][min(FD_NSP, ceil(S / cap))][hd + 2], a.cnt [R][nkv] zeroed tickets
+// hold [R][nh][min(FD_NSP, ceil(S / cap))][hd + 2], a.cnt [R][nh] zeroed tickets (one per row, kv head
+// and group of a.hpb q heads)
 constexpr int FD_NSP = 16;
 inline bool attn_fd_ok(int hd, int g) { return (hd == 32 || hd == 64 || hd == 128) && g >= 1 && g <= 4; }
 template <typename T> void launch_attn_fd(hipStream_t s, const AttnDecArgs<T>& a, int R);

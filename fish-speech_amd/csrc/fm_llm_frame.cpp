@@ -244,6 +244,7 @@ template <typename T> struct Run {
             AttnDecArgs<T> b = aa;
             b.cap = p.cap;
             b.nwb = p.nwb;
+            b.hpb = p.hpb;
             launch_attn_fd<T>(s, b, R);
         } else if (p.kernel == 2)
             launch_attn_decode3<T>(s, aa, R);

@@ -23,14 +23,18 @@ inline int attn2_frame_cap(int hd, int g, size_t esz, bool batched) {
 // Which slow decode attention a frame of R rows launches, and with what geometry (the frame's
 // attn_slow_on and the per-op hook fm_op_decode_attn_ex both ask here).  kernel as fm_op_decode_attn
 // numbers them: 3 attn_fd, 2 attn_dec3, 0 attn_decode2.  attn_fd: nwb waves per block and splits of
-// at least cap positions, from the fd_* knobs; the other two keep the caller's cap (cap0).
+// at least cap positions, hpb q heads of a kv head per block, from the fd_* knobs; the other two keep
+// the caller's cap (cap0).
 struct AttnSlowPlan {
     int kernel, nwb, cap;
+    int hpb = 4;
 };
+// attn_fd's q heads per block on R rows: fm_tune fd_hpb up to 8 rows, every head of the kv head past them
+inline int fd_hpb_rows(int R) { return R <= GEMV_MAX_ROWS ? fm_tuning().fd_hpb : 4; }
 inline AttnSlowPlan attn_slow_plan(int R, int hd, int g, int cap0) {
     const FmTuning& tu = fm_tuning();
     if (tu.attn_fd && attn_fd_ok(hd, g)) {
-        AttnSlowPlan p{3, 4, std::max(16, R > GEMV_MAX_ROWS ? tu.fd_min_batched : tu.fd_min)};
+        AttnSlowPlan p{3, 4, std::max(16, R > GEMV_MAX_ROWS ? tu.fd_min_batched : tu.fd_min), fd_hpb_rows(R)};
         if (R <= GEMV_MAX_ROWS && tu.fd_nw > 4) {
             p.nwb = tu.fd_nw;
             p.cap = std::max(16, tu.fd_min16);

@@ -538,7 +538,10 @@ void finalize(fm_llm* m) {
     m->maxsplit = FM_CEIL(m->S, ATTN_SPLIT);
     const int Rpart = std::max(m->max_slots, ATTN_PIECE);  // decode rows, or one prompt attention piece
     m->part = (float*)m->dalloc((size_t)Rpart * d.nh * std::max(m->maxsplit, FM_CEIL(m->S, 16)) * (d.hd + 2) * 4, false);
-    m->attn_cnt = (int*)m->dalloc((size_t)R * d.nkv * sizeof(int));  // tickets: zeroed
+    // tickets, zeroed: [rows][nkv] for attn_decode2 / attn_dec3 (rows of a chunk), [rows][nh] for attn_fd (one per row,
+    // kv head and group of fd_hpb q heads; its rows are distinct slots, at most max_slots)
+    const size_t ncnt = std::max((size_t)R * d.nkv, (size_t)m->max_slots * d.nh);
+    m->attn_cnt = (int*)m->dalloc(ncnt * sizeof(int));
     m->ssX = (float*)m->dalloc((size_t)(dmax / 16) * std::min(n, 32) * 4);  // batched chain: up to 32 rows
     m->ssH = (float*)m->dalloc((size_t)(dmax / 16) * std::min(n, 32) * 4);
     {
@@ -550,7 +553,7 @@ void finalize(fm_llm* m) {
         m->skpart_cap = 16ll << 20;  // 64 MiB of partial tiles (prompt GEMM slabs: 256 rows x 2 x 19456)
         m->skpart = (float*)m->dalloc((size_t)m->skpart_cap * sizeof(float), false);
     }
-    HIPCHK(hipMemsetAsync(m->attn_cnt, 0, (size_t)R * d.nkv * sizeof(int), m->stream));
+    HIPCHK(hipMemsetAsync(m->attn_cnt, 0, ncnt * sizeof(int), m->stream));
     m->slabA = (float*)m->dalloc((size_t)KSB_MAX * std::min(n, GEMV_MAX_ROWS) * dmax * 4);
     m->slabB = (float*)m->dalloc((size_t)KSB_MAX * std::min(n, GEMV_MAX_ROWS) * dmax * 4);
     if (n > GEMV_MAX_ROWS) {  // [BS_KPARTS][32][dmax] fp32 each

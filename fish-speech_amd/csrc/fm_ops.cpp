@@ -148,7 +148,7 @@ void qk_rope_t(hipStream_t s, int kernel, const float* qkv, int nh, int nkv, int
         a.cap = attn2_cap(hd, nh / nkv, sizeof(T));
         a.maxsplit = FM_CEIL(S, std::min(a.cap, 16));  // covers both kernels' split counts
         a.part = (float*)b.alloc((size_t)nh * a.maxsplit * (hd + 2) * 4);
-        a.cnt = (int*)b.alloc((size_t)nkv * 4);
+        a.cnt = (int*)b.alloc((size_t)nh * 4);
         a.out = out;
         a.qdbg = qd;
         // kernel 0: attn_decode2 (the B <= 8 decode path), 2: attn_dec3 (the batched frame)
@@ -158,6 +158,7 @@ void qk_rope_t(hipStream_t s, int kernel, const float* qkv, int nh, int nkv, int
             FMCHECK(attn_fd_ok(hd, nh / nkv), "attn_fd: head_dim 32, 64 or 128, at most 4 q heads per kv head");
             a.cap = std::max(16, fm_tuning().fd_min16);
             a.nwb = fm_tuning().fd_nw;
+            a.hpb = fd_hpb_rows(1);
             a.maxsplit = FM_CEIL(S, a.cap);
             launch_attn_fd<T>(s, a, 1);
         } else {
@@ -234,11 +235,12 @@ void decode_attn_t(hipStream_t s, int kernel, const float* qkv, int R, int nh, i
     const int g = nh / nkv;
     a.maxsplit = FM_CEIL(S, 16);
     a.part = (float*)b.alloc((size_t)R * nh * a.maxsplit * (hd + 2) * 4);
-    a.cnt = (int*)b.alloc((size_t)R * nkv * 4);
+    a.cnt = (int*)b.alloc((size_t)R * nh * 4);
     a.out = o;
     if (kernel == 3) {
         FMCHECK(attn_fd_ok(hd, g), "attn_fd: head_dim 32, 64 or 128 and at most 4 q heads per kv head");
         a.cap = min_split;
+        a.hpb = fd_hpb_rows(R);
         launch_attn_fd<T>(s, a, R);
     } else if (kernel == 2) {
         FMCHECK(hd % 32 == 0 && hd <= 128 && g <= 6, "attn_dec3: hd a multiple of 32 up to 128, g <= 6");
@@ -310,13 +312,14 @@ template <typename T> void decode_attn_ex_t(hipStream_t s, const DecodeAttnEx& o
         rs[R + r] = o.pos[r];
     }
     int* rows = upload_i32(b, rs.data(), rs.size());
-    int kernel = o.kernel, nwb = o.nwb, cap = o.cap;
+    int kernel = o.kernel, nwb = o.nwb, cap = o.cap, hpb = fd_hpb_rows(R);  // (fd_hpb holds without o.frame too)
     const int cap2 = attn2_cap(hd, g, sizeof(T));
     if (o.frame) {  // as blk_attn / small_attn do
         const AttnSlowPlan p = attn_slow_plan(R, hd, g, attn2_frame_cap(hd, g, sizeof(T), R > GEMV_MAX_ROWS));
         kernel = p.kernel;
         nwb = p.nwb;
         cap = p.cap;
+        hpb = p.hpb;
     }
     if (kernel == 0) cap = std::min(cap, cap2);
     FMCHECK(!slab || kernel == 3, "the slab form of the QKV input needs attn_fd");
@@ -331,10 +334,11 @@ template <typename T> void decode_attn_ex_t(hipStream_t s, const DecodeAttnEx& o
     HIPCHK(hipMemsetAsync(a.part, 0xff, npart * 4, s));
     const std::vector<uint32_t> guard(PART_GUARD, 0x5a5a5a5au);
     b.put(a.part + npart, guard.data(), PART_GUARD * 4);
-    a.cnt = (int*)b.alloc((size_t)R * nkv * 4);
+    a.cnt = (int*)b.alloc((size_t)R * nh * 4);  // attn_fd: a ticket per (row, kv head, head group)
     a.out = out;
     a.cap = cap;
     a.nwb = nwb;
+    a.hpb = hpb;
     a.qslab = slab;
     a.qslab_kp = o.kp;
     a.qbias = bias;
@@ -353,7 +357,7 @@ template <typename T> void decode_attn_ex_t(hipStream_t s, const DecodeAttnEx& o
     std::vector<uint32_t> back(PART_GUARD);
     HIPCHK(hipMemcpyAsync(back.data(), a.part + npart, PART_GUARD * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    const int info[8] = {kernel, nwb, cap, maxsplit, count_nonzero(a.cnt, (size_t)R * nkv, s), back == guard, FD_NSP, cap2};
+    const int info[8] = {kernel, nwb, cap, maxsplit, count_nonzero(a.cnt, (size_t)R * nh, s), back == guard, FD_NSP, cap2};
     memcpy(o.info, info, sizeof(info));
 }
 

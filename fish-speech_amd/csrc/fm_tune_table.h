@@ -43,6 +43,8 @@ FM_KNOB(fin_ksb, 0, FM_RANGE(0, 8))        // batch-1 wo / w2 (EPI_SLABFIN) spli
 FM_KNOB(fd_nw_batched, 4, FM_SET(4, 8, 16))  // attn_fd at R > 8: waves per block (4, 8 or 16)
 FM_KNOB(fd_min16, 256, FM_MULT16)          // ... and splits of at least this many positions (8 or 16 waves; below it
                                            // one block per kv head, no cross-block combine)
+FM_KNOB(fd_hpb, 1, FM_SET(1, 2, 4))        // attn_fd at R <= 8: q heads of a kv head per block (4: all of them, one block per kv head and
+                                           // split); fewer spread the same arithmetic over more CUs (bit-identical)
 FM_KNOB(prefill_attn, 1, FM_BOOL)          // 1: prompt-chunk attention on attn_prefill_kernel (bf16, head_dim 128, flash form)
 FM_KNOB(prompt_gemm, 1, FM_BOOL)           // 1: prompt-chunk linears (R > 32) on the codec's LDS-tiled GEMM kernels
 FM_KNOB(prompt_skinny, 1, FM_BOOL)         // prompt linears at 32 < R <= 64 rows (bf16) on prompt_skinny_kernel ...

@@ -59,6 +59,11 @@ for B, lens in cases:
                           f"rt1+qprep {d[:, 0].mean():.2f} passes {d[:, 1].mean():.2f} fold {d[:, 2].mean():.2f} "
                           f"store {d[:, 3].mean():.2f} us; block {(fd[:, 5] - fd[:, 1]).mean() / 100:.2f} us; "
                           f"fold pre-barrier {(fd[:, 6] - fd[:, 3]).mean() / 100:.2f} us", flush=True)
+                    # every wave stamps its own pass end; thread 0 records the latest: the passes as the block's
+                    # slowest wave ends them, and what of thread 0's "fold" is left after that wave
+                    print(f"    per-wave: passes to the last wave {(fd[:, 7] - fd[:, 2]).mean() / 100:.2f} us, "
+                          f"fold after it {(fd[:, 4] - fd[:, 7]).mean() / 100:.2f} us "
+                          f"(thread 0 waited {(fd[:, 7] - fd[:, 3]).mean() / 100:.2f} us)", flush=True)
                 cmb = rec[(rec[:, 0] >> 32) == 0xFFFB].astype(np.float64)
                 if len(cmb):
                     print(f"    combiner: stored->ticket {np.mean(cmb[:, 6] - cmb[:, 5]) / 100:.2f} us, "
