@@ -70,7 +70,7 @@ static void upload_frame_rows(fm_llm* m, const int32_t* slots, int n) {
 // host's stream sync, a timed-out hand-off wait (a hang avoided) resets the counters and fails
 static void chain_err_async(fm_llm* m) {
     if (fm_tuning().gemv_chain || fm_tuning().fin_split > 1 ||
-        (m->fxt && fm_tuning().fattn_wo))
+        (m->fxt && fm_tuning().fattn_wo) || (m->sxt && fm_tuning().slow_attn_wo))
         HIPCHK(hipMemcpyAsync(m->h_chain_err, m->chain_err, sizeof(int), hipMemcpyDeviceToHost, m->stream));
 }
 static void chain_err_check(fm_llm* m) {
@@ -80,7 +80,7 @@ static void chain_err_check(fm_llm* m) {
     HIPCHK(hipMemset(m->chain_err, 0, 16 * sizeof(int)));
     if (m->fin_cnt) HIPCHK(hipMemset(m->fin_cnt, 0, (size_t)std::max(m->max_slots, 64) * 2 * sizeof(int)));
     throw FmError{FM_ERR_STATE,
-                  "in-launch hand-off wait timed out (gemv chain / split finalize / fused fast "
+                  "in-launch hand-off wait timed out (gemv chain / split finalize / fused fast or slow "
                   "attention + wo; counters reset)"};
 }
 

@@ -903,12 +903,26 @@ template <typename T> struct Run {
         bool tab;       // rowgemv bit 5 / fast_dead_q bit 0: the first fast layer at codebook > 0 inside fw: its q|k|v row comes from the table, no QKV launch
         bool kv0;       // rowgemv bit 6 / fast_dead_q bit 1: codebook 0: only K / V are projected (row path; int8: the tile path) and the attention reads no Q (one position: output = v)
         bool kv_only;   // the layer ends after its K / V cache write (fm_tune fast_tail: its output would be discarded)
+        bool sw;        // slow model: attention + wo as one launch (slow_attn_wo_kernel), no attention launch (fm_tune slow_attn_wo)
     };
+    // fm_tune slow_attn_wo: one bf16 unquantised row of the slow stack whose attention is attn_fd at 8 waves and one q
+    // head per block and whose wo runs on the row-block GEMV (so gemv_chain is off), at instantiated shapes; two layers
+    // at least, so that consecutive writers of the tagged words always differ in tag, and at most 40 (the tag's
+    // launch indices).  Anywhere else the layer keeps its two launches.
+    bool slow_attn_wo_live(const Small& c, bool rf) const {
+        const StackDims& d = c.d;
+        if (!(sizeof(T) == 2 && !c.is_fast && c.n == 1 && rf && !m->quant && fm_tuning().slow_attn_wo && m->sxt &&
+              !fm_tuning().gemv_chain && d.n_layer >= 2 && d.n_layer <= 40 && !c.L.wo.rm_scale && !c.L.wo.rm_sz))
+            return false;
+        const AttnSlowPlan ap = attn_slow_plan(1, d.hd, d.nh / d.nkv, attn2_frame_cap(d.hd, d.nh / d.nkv, E, false));
+        return ap.kernel == 3 && ap.nwb == 8 && ap.hpb == 1 && slow_attn_wo_ok(d.nh, d.nkv, d.hd, d.dim, d.nq());
+    }
     SmallPath small_path(const Small& c, bool kv_only) const {
         const StackDims& d = c.d;
         SmallPath p{};
         p.kv_only = kv_only;
         p.rf = row_fin(c.n);
+        p.sw = !kv_only && slow_attn_wo_live(c, p.rf);
         const int fq = m->qmode();
         // (fw_any: the fused launch is this layer's form, whether or not this pass ends before it)
         const bool fw_any = c.is_fast && p.rf && fm_tuning().fattn_wo && m->fxt && m->fdm.n_layer * m->C >= 2 &&
@@ -971,20 +985,27 @@ template <typename T> struct Run {
         }
     }
     // attention launch (none where wo does it: fw, att_wo)
+    // the slow model's decode attention operands at this layer (the attention launch, slow_attn_wo)
+    AttnDecArgs<T> small_slow_args(const Small& c) const {
+        const StackDims& d = c.d;
+        AttnDecArgs<T> aa{(const T*)m->qkv, d.nqkv(), m->frame_slot, m->frame_pos, d.nh, d.nkv, d.hd,
+                          d.qk_norm, m->c.norm_eps, (const T*)c.L.qn, (const T*)c.L.kn, m->rope, (T*)m->kc,
+                          (T*)m->vc, m->slot_stride, (size_t)c.layer * m->layer_stride, m->S,
+                          m->maxsplit, 1.0f / sqrtf((float)d.hd), m->part};
+        aa.cap = attn2_frame_cap(d.hd, d.nh / d.nkv, E, false);
+        aa.maxsplit = FM_CEIL(m->S, aa.cap);
+        aa.cnt = m->attn_cnt;
+        aa.dbg = fm_tuning().dbg;
+        aa.out = (T*)m->att;
+        return aa;
+    }
     void small_attn(const Small& c, const SmallPath& p) {
         const StackDims& d = c.d;
         const int n = c.n;
         hipStream_t st = s;
+        if (p.sw) return;
         if (!c.is_fast) {
-            AttnDecArgs<T> aa{(const T*)m->qkv, d.nqkv(), m->frame_slot, m->frame_pos, d.nh, d.nkv, d.hd,
-                              d.qk_norm, m->c.norm_eps, (const T*)c.L.qn, (const T*)c.L.kn, m->rope, (T*)m->kc,
-                              (T*)m->vc, m->slot_stride, (size_t)c.layer * m->layer_stride, m->S,
-                              m->maxsplit, 1.0f / sqrtf((float)d.hd), m->part};
-            aa.cap = attn2_frame_cap(d.hd, d.nh / d.nkv, E, false);
-            aa.maxsplit = FM_CEIL(m->S, aa.cap);
-            aa.cnt = m->attn_cnt;
-            aa.dbg = fm_tuning().dbg;
-            aa.out = (T*)m->att;
+            const AttnDecArgs<T> aa = small_slow_args(c);
             auto go = [st, aa, n] { attn_slow_on(st, aa, n); };
             m->prof.record("attn_slow", 0, go);  // the slow model's launches alone (fm_llm_kernel_bench)
             launch("attn", 0, 0, go);
@@ -1032,6 +1053,30 @@ template <typename T> struct Run {
             }
             r.N = d.dim;
             r.K = d.nq();
+            if (p.sw) {  // the slow attention blocks and wo's row blocks as one launch
+                SlowAttnWoArgs W{};
+                if constexpr (sizeof(T) == 2) {  // (p.sw is a bf16 frame's only: slow_attn_wo_live)
+                    W.at = small_slow_args(c);
+                    W.at.cap = attn_slow_plan(1, d.hd, d.nh / d.nkv, W.at.cap).cap;
+                }
+                W.wo = r;
+                W.xt = m->sxt;
+                // <= 40 (slow_attn_wo_live).  Consecutive launches of one stream always differ in tag.  A first layer
+                // follows the last layer of the frame before it, which may be another slot's: the two tags meet only
+                // where 41 (p' - p) = n_layer - 1 (mod 65535) -- S2-Pro's 36 layers: slots 15985 positions apart, past
+                // any max_seq_len here; 25 layers: 1599 apart (the fast launches' formula has the same property)
+                W.gen = 1 + c.layer;
+                W.err = m->chain_err;
+                W.rp = fm_tuning().slow_attn_wo == 2 ? 4 : 2;
+                W.delay_pct = fm_tuning().slow_aw_delay;
+                W.sleep = fm_tuning().slow_aw_sleep;
+                W.cheap = fm_tuning().slow_aw_cheap;
+                hipStream_t st = s;
+                auto go = [st, W] { launch_slow_attn_wo(st, W); };
+                // a class of its own (attention + GEMV), booked with wo's weight bytes
+                launch("slow_attn_wo", rowgemv_wbytes(r), 2.0 * r.N * r.K, go);
+                return;
+            }
             if (!p.fw) {
                 rowgemv(r, ROWGEMV_FIN);
                 return;

@@ -206,7 +206,8 @@ struct fm_llm {
     bool row_qkv_ok = false;                //                         ... and wqkv
     bool row_w13_ok = false;                //                         ... and w1 || w3
     uint32_t* fxt = nullptr;                // fused fast attention + wo: tagged attention words [nh * hd]
-    int32_t* fiota = nullptr;               // [16]: fiota[c] = c - 1 (the fast KV prefetch's last cached row)
+    uint32_t* sxt = nullptr;                // fused slow attention + wo: tagged attention words [nh * hd] (its own buffer)
+    int32_t* fiota = nullptr;              // [16]: fiota[c] = c - 1 (the fast KV prefetch's last cached row)
     // fm_tune rowgemv bit 5: the first fast layer's raw q|k|v row of every code [cb][fast nqkv] (bf16, unquantised
     // models; ensure_qkv0), valid while qkv0_epoch is the tuning epoch it was built under
     void* qkv0 = nullptr;

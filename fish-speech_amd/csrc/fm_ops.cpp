@@ -600,6 +600,111 @@ void fattn_wo_op(hipStream_t s, const FattnWoOp& o) {
     HIPCHK(hipStreamSynchronize(s));
 }
 
+// the batch-1 slow layers' attention + wo at nrun (slot, position) pairs, one after the other on the same device
+// operands: one launch_slow_attn_wo each (fused), or the two launches it replaces (launch_attn_fd as attn_slow_plan
+// runs it at one row + launch_rowgemv FIN).  The tagged-word buffer lives through the call, so a run finds the words
+// its predecessors left
+struct SlowAttnWoOp {
+    int fused, rp;
+    const float* qkv;
+    int nh, nkv, hd;
+    const float *qn, *kn;
+    int qk_norm;
+    float eps, base;
+    const int32_t *slots, *pos, *gens;
+    int nrun, restore, nslots, layers, layer;
+    const float *kc, *vc;
+    int S;
+    const float *w, *bias, *res;
+    int N;
+    const uint32_t* xt_init;
+    float *y, *krows, *vrows;
+    int* status;
+};
+void slow_attn_wo_op(hipStream_t s, const SlowAttnWoOp& o) {
+    DevBufs b(s);
+    const int nh = o.nh, nkv = o.nkv, hd = o.hd, S = o.S, N = o.N, K = nh * hd, ld = (nh + 2 * nkv) * hd, g = nh / nkv;
+    const AttnSlowPlan ap = attn_slow_plan(1, hd, g, attn2_frame_cap(hd, g, 2, false));
+    // "not dispatchable" is a status, not a launch: what small_path asks before it takes the fused launch
+    o.status[0] = ap.kernel == 3 && ap.nwb == 8 && ap.hpb == 1 && slow_attn_wo_ok(nh, nkv, hd, N, K) && !fm_tuning().gemv_chain;
+    o.status[1] = 0;
+    if (o.fused && !o.status[0]) return;
+    FMCHECK(ap.kernel == 3, "the unfused composition runs attn_fd");
+    RowGemvArgs r{};
+    r.W = b.upload<bf16_t>(o.w, (size_t)N * K);
+    if (o.bias) r.bias = b.upload<bf16_t>(o.bias, (size_t)N);
+    r.res = b.upload<bf16_t>(o.res, (size_t)N);
+    r.ldr = N;
+    r.N = N;
+    r.K = K;
+    const bf16_t* raw = b.upload<bf16_t>(o.qkv, (size_t)o.nrun * ld);
+    bf16_t* qnd = o.qk_norm ? b.upload<bf16_t>(o.qn, (size_t)hd) : (bf16_t*)b.alloc((size_t)hd * 2);
+    bf16_t* knd = o.qk_norm ? b.upload<bf16_t>(o.kn, (size_t)hd) : (bf16_t*)b.alloc((size_t)hd * 2);
+    float* rope = upload_rope(b, S, hd, o.base);
+    const size_t layer_stride = (size_t)nkv * S * hd, slot_stride = (size_t)o.layers * layer_stride;
+    const size_t cn = (size_t)o.nslots * slot_stride, layer_off = (size_t)o.layer * layer_stride;
+    const bf16_t *kc0 = b.upload<bf16_t>(o.kc, cn), *vc0 = b.upload<bf16_t>(o.vc, cn);
+    bf16_t *kc = (bf16_t*)b.alloc(cn * 2), *vc = (bf16_t*)b.alloc(cn * 2);
+    HIPCHK(hipMemcpyAsync(kc, kc0, cn * 2, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(vc, vc0, cn * 2, hipMemcpyDeviceToDevice, s));
+    int* rows_d = (int*)b.alloc(8);
+    bf16_t* att = (bf16_t*)b.alloc((size_t)K * 2);
+    bf16_t* yd = (bf16_t*)b.alloc((size_t)o.nrun * N * 2);
+    bf16_t *kr = (bf16_t*)b.alloc((size_t)o.nrun * nkv * hd * 2), *vr = (bf16_t*)b.alloc((size_t)o.nrun * nkv * hd * 2);
+    uint32_t* xt = (uint32_t*)b.alloc((size_t)K * 4);
+    if (o.xt_init) b.put(xt, o.xt_init, (size_t)K * 4);
+    int* err = (int*)b.alloc(16);
+    AttnDecArgs<bf16_t> at{raw, ld, rows_d, rows_d + 1, nh, nkv, hd, o.qk_norm, o.eps, qnd, knd, rope, kc, vc, slot_stride,
+                           layer_off, S, 1, 1.0f / sqrtf((float)hd), nullptr};
+    at.cap = ap.cap;
+    at.nwb = ap.nwb;
+    at.hpb = ap.hpb;
+    at.maxsplit = std::min(FD_NSP, FM_CEIL(S, at.cap));
+    at.part = (float*)b.alloc((size_t)nh * at.maxsplit * (hd + 2) * 4);
+    at.cnt = (int*)b.alloc((size_t)nh * 4);
+    at.out = att;
+    for (int i = 0; i < o.nrun; ++i) {
+        if (o.restore && i) {
+            HIPCHK(hipMemcpyAsync(kc, kc0, cn * 2, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(vc, vc0, cn * 2, hipMemcpyDeviceToDevice, s));
+        }
+        const int rs[2] = {o.slots[i], o.pos[i]};
+        b.put(rows_d, rs, 8);
+        at.qkv = raw + (size_t)i * ld;
+        r.res_out = yd + (size_t)i * N;
+        r.X = att;
+        if (o.fused) {
+            SlowAttnWoArgs A{};
+            A.at = at;
+            A.wo = r;  // (X: unused, x comes from the tagged words)
+            A.xt = xt;
+            A.gen = o.gens[i];
+            A.err = err;
+            A.rp = o.rp;
+            A.delay_pct = fm_tuning().slow_aw_delay;
+            A.sleep = fm_tuning().slow_aw_sleep;
+            A.cheap = fm_tuning().slow_aw_cheap;
+            launch_slow_attn_wo(s, A);  // one launch, never repeated: its waits are bounded and set err
+        } else {
+            launch_attn_fd<bf16_t>(s, at, 1);
+            HIPCHK(hipGetLastError());
+            launch_rowgemv(s, r, ROWGEMV_FIN);
+        }
+        HIPCHK(hipGetLastError());
+        // the K / V rows this run wrote: position pos[i] of every kv head of (slot, layer)
+        const size_t row0 = (size_t)o.slots[i] * slot_stride + layer_off + (size_t)o.pos[i] * hd;
+        HIPCHK(hipMemcpy2DAsync(kr + (size_t)i * nkv * hd, (size_t)hd * 2, kc + row0, (size_t)S * hd * 2, (size_t)hd * 2, nkv,
+                                hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(vr + (size_t)i * nkv * hd, (size_t)hd * 2, vc + row0, (size_t)S * hd * 2, (size_t)hd * 2, nkv,
+                                hipMemcpyDeviceToDevice, s));
+    }
+    download<bf16_t>(yd, (size_t)o.nrun * N, o.y, s);
+    download<bf16_t>(kr, (size_t)o.nrun * nkv * hd, o.krows, s);
+    download<bf16_t>(vr, (size_t)o.nrun * nkv * hd, o.vrows, s);
+    HIPCHK(hipMemcpyAsync(&o.status[1], err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+}
+
 template <typename T>
 void embed_t(hipStream_t s, const int32_t* tok, int R, const float* emb, int V, const float* cbemb, int d, int C,
              int cb, int sb, int se, int scale, float* x) {
@@ -1276,6 +1381,28 @@ int fm_op_fattn_wo(int device, int quant, int gs, int fused, const float* qkv, c
                           rope_base, slot, cpos, nslots, layers, layer, kcache, vcache, S, w, bias, res, res_rows, ldr,
                           res0, N, kv0, pair, ilp, gen, pos0, xt_init, y, status};
         fattn_wo_op(g.s, o);
+    });
+}
+
+int fm_op_slow_attn_wo(int device, int fused, int rp, const float* qkv, int nh, int nkv, int hd, const float* qn,
+                       const float* kn, int qk_norm, float eps, float rope_base, const int32_t* slots, const int32_t* pos,
+                       const int32_t* gens, int nrun, int restore, int nslots, int layers, int layer, const float* kcache,
+                       const float* vcache, int S, const float* w, const float* bias, const float* res, int N,
+                       const uint32_t* xt_init, float* y, float* k_rows, float* v_rows, int* status) {
+    return fm_guard([&] {
+        FMCHECK(qkv && slots && pos && gens && kcache && vcache && w && res && y && k_rows && v_rows && status, "null argument");
+        FMCHECK(!qk_norm || (qn && kn), "qk_norm needs both norm weights");
+        FMCHECK(nh >= 1 && nkv >= 1 && nh % nkv == 0 && hd >= 8 && hd <= 128 && hd % 8 == 0, "bad heads / head_dim");
+        FMCHECK(S >= 16 && S % 16 == 0 && S <= 65536 && N >= 16 && N % 16 == 0 && nrun >= 1 && nrun <= 4096, "bad S / N / runs");
+        FMCHECK(rp == 2 || rp == 4, "rp must be 2 or 4");
+        for (int i = 0; i < nrun; ++i) {
+            FMCHECK(pos[i] >= 0 && pos[i] < S && gens[i] >= 1 && gens[i] <= 40, "bad position / gen");
+            check_slot_rows(1, &slots[i], nullptr, nslots, layers, layer, S);
+        }
+        StreamGuard g(device);
+        const SlowAttnWoOp o{fused, rp, qkv, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, slots, pos, gens, nrun, restore,
+                             nslots, layers, layer, kcache, vcache, S, w, bias, res, N, xt_init, y, k_rows, v_rows, status};
+        slow_attn_wo_op(g.s, o);
     });
 }
 

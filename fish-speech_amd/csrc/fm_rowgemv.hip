@@ -27,6 +27,7 @@
 #include "fm_common.h"
 #include "fm_kernels.h"
 #include "fm_runtime.h"
+#include "fm_attn_fd_dev.h"
 #include <type_traits>
 
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2_t;
@@ -93,9 +94,16 @@ template <int QM> struct RowT {
 // operands are RowGemvArgs::X1 / res1 / res_out1 / Y1 (TX: the second K words of xt); G gathers row 1's residual
 // only.  One accumulator set, one RMSNorm statistic and one epilogue thread per (x row, weight row): every output
 // is the one-row form's operations on the same inputs in the same order.
-template <int U, int RP, bool PRENORM, int EPI, bool G, int QM, bool TX, int XR = 1>
+// TxPoll (NG 2 only; speed, never correctness -- every full read checks every tag): delay, 10-ns ticks from the wave's
+// start to its first read of x; sleep, the s_sleep argument between reads (1, 4 or 16); cheap, one word per 128
+// elements of the wave's range is polled until current before the first full read.
+struct TxPoll {
+    unsigned delay = 0;
+    int sleep = 1, cheap = 0;
+};
+template <int U, int RP, bool PRENORM, int EPI, bool G, int QM, bool TX, int XR = 1, int NG = 1>
 __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk, const uint32_t* xt, const uint32_t gen,
-                                             int* err) {
+                                             int* err, const TxPoll pw = TxPoll{}) {
     static_assert(!TX || (!PRENORM && EPI == 1), "tagged x: the residual form only");
     static_assert(XR == 1 || (XR == 2 && QM == 0 && EPI <= 1 && (!G || EPI == 1)), "two x rows: bf16 STORE / FIN");
     constexpr bool FIN = EPI == 1;
@@ -106,8 +114,13 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     // deep runs (w2): row 1's x chunk is loaded into the registers row 0's chunk leaves, after its dot products, so
     // the two-row form keeps the one-row form's register budget (no scratch under waves_per_eu 5)
     constexpr bool LATE = XR == 2 && !TX && !PRENORM && U >= 10;
-    __shared__ float red[XR * (4 * RP + 8)];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    static_assert(NG == 1 || (NG == 2 && TX), "two row blocks per 512-thread block: the tagged-x form only");
+    // NG 2 (slow_attn_wo_kernel): a 512-thread block holds two independent 4-wave groups, each one row block with its
+    // own red slice; tid is the thread's index in its group (NG 1: threadIdx.x itself)
+    __shared__ float red_s[NG][XR * (4 * RP + 8)];
+    const unsigned tid = NG == 1 ? threadIdx.x : threadIdx.x & 255u;
+    float(&red)[XR * (4 * RP + 8)] = red_s[NG == 1 ? 0 : threadIdx.x >> 8];
+    const int lane = tid & 63, wave = tid >> 6;
     const int n0 = blk * RP;
     const int nch = a.K / R::CE;
     const int wa = (wave * nch) >> 2, nmy = (((wave + 1) * nch) >> 2) - wa;
@@ -115,8 +128,8 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     const unsigned long long ts0 = a.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
     // first round trip, unconditional (a load under a branch drains vmcnt): the epilogue's residual,
     // bias and (int8) scale elements of row n0 + (thread % RP), then x (and the norm weight)
-    const int er = n0 + (int)(threadIdx.x % RP);
-    const int ex = XR == 2 ? (int)((threadIdx.x / RP) & 1) : 0;  // the x row this thread finishes
+    const int er = n0 + (int)(tid % RP);
+    const int ex = XR == 2 ? (int)((tid / RP) & 1) : 0;  // the x row this thread finishes
     int ri = 0, xi = 0;
     if constexpr (G && FIN) {
         const int32_t iv = a.residx[a.res_col];
@@ -185,12 +198,37 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     }
     asm volatile("" ::: "memory");
     unsigned long long tsw = 0, tsx = 0;  // TX developer stamps: weights issued, x words current
-    unsigned polls = 0;
+    unsigned polls = 0, cpolls = 0;  // full reads of x; NG 2: one-word polls ahead of them (the record's aux: polls | cpolls << 16)
     if constexpr (TX) {
         if (a.dbg) tsw = __builtin_amdgcn_s_memrealtime();
         // EPL tagged words per lane per chunk (sc1 loads, 16 B each), re-read until all are current
         const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc((void*)xt, (short)0, XR * a.K * 4, 0x00020000);
         u32x4_t xw[XR][U][EPL / 4];
+        auto nap = [&] {
+            if constexpr (NG == 2) {
+                if (pw.sleep >= 16) __builtin_amdgcn_s_sleep(16);
+                else if (pw.sleep >= 4) __builtin_amdgcn_s_sleep(4);
+                else __builtin_amdgcn_s_sleep(1);
+            } else {
+                __builtin_amdgcn_s_sleep(1);
+            }
+        };
+        if constexpr (NG == 2) {
+            // the producer runs for microseconds: no read of x before pw.delay (time-bounded), then one word per 128
+            // elements until those are current (bounded; the full reads below decide and report a timeout)
+            const unsigned long long tw0 = __builtin_amdgcn_s_memrealtime();
+            while (pw.delay && (unsigned)(__builtin_amdgcn_s_memrealtime() - tw0) < pw.delay) __builtin_amdgcn_s_sleep(8);
+            if (pw.cheap) {
+                const int ng = nmy * (R::CE / 128);
+                const int wi = (wa * R::CE + 128 * (lane < ng ? lane : 0) + 127) * 4;
+                for (unsigned it = 0; it < (1u << 14); ++it) {
+                    cpolls = it + 1;
+                    const uint32_t w = __builtin_amdgcn_raw_buffer_load_b32(xr, wi, 0, 16);
+                    if (__all((w & 0xffffu) == gen)) break;
+                    nap();
+                }
+            }
+        }
         for (unsigned it = 0;; ++it) {
             polls = it + 1;
 #pragma unroll
@@ -217,7 +255,7 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
                 if (lane == 0) __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
             }
-            __builtin_amdgcn_s_sleep(1);
+            nap();
         }
         if (a.dbg) tsx = __builtin_amdgcn_s_memrealtime();
 #pragma unroll
@@ -399,8 +437,8 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         if (lane == 0) red[4 * RP + 4 + wave] = v;
     }
     __syncthreads();
-    if ((int)threadIdx.x < XR * RP) {
-        const int t = XR == 2 ? (int)(threadIdx.x % RP) : (int)threadIdx.x;
+    if ((int)tid < XR * RP) {
+        const int t = XR == 2 ? (int)(tid % RP) : (int)tid;
         const float* rd = red + 4 * RP * ex;
         float v = ((rd[t] + rd[RP + t]) + rd[2 * RP + t]) + rd[3 * RP + t];
         if constexpr (QM == 1) {
@@ -424,12 +462,22 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
             a.Y[er] = f2bf(v);
         }
     }
-    if (a.dbg && threadIdx.x == 0) {  // one record per x row: a record stands for one block's work on one row
+    if (a.dbg && tid == 0) {  // one record per x row: a record stands for one block's work on one row
 #pragma unroll
         for (int x = 0; x < XR; ++x) {
             if constexpr (TX) {  // (wave 0) start, weights issued, x words current, dot products done, end; aux = reads of x
                 const unsigned long long t[7] = {ts0, tsw, tsx, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0};
-                dbg_record(a.dbg, 0xFFF8u, polls, t);
+                dbg_record(a.dbg, 0xFFF8u, polls | (cpolls << 16), t);
+                // NG 2, the slow wo: a row-block record (0xFFFA) per row pair as well, so that the count of row-block
+                // records in a frame stays what the wo launch it replaces left (tests/test_gpu_rowgemv.py counts them).
+                // They are not rowgemv_kernel blocks: their span {start, dot products done, end} holds the wait for the
+                // attention, and a probe that times 0xFFFA records (scripts/ts_probe.py) reads that wait as stream time;
+                // aux bit 31 marks them
+                if constexpr (NG == 2) {
+                    const unsigned long long tr[7] = {ts0, ts1, t[4], 0, 0, 0, 0};
+#pragma unroll
+                    for (int p = 0; p < RP / 2; ++p) dbg_record(a.dbg, 0xFFFAu, 0x80000000u | (unsigned)(blk * (RP / 2) + p), tr);
+                }
             } else {
                 const unsigned long long t[7] = {ts0, ts1, __builtin_amdgcn_s_memrealtime(), 0, 0, 0, 0};
                 dbg_record(a.dbg, 0xFFFAu, (unsigned)blk, t);
@@ -1118,4 +1166,76 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
     if (qm == 2) go(std::integral_constant<int, 2>{});
     else if (qm == 1) go(std::integral_constant<int, 1>{});
     else go(std::integral_constant<int, 0>{});
+}
+
+// =========================================================================================
+// Slow-model attention + wo in ONE launch (batch 1, bf16, unquantised; fm_tune slow_attn_wo).
+//
+// The same arrangement as fattn_wo_kernel with the slow decode attention as the producer.  Linear block indices
+// 0 .. nh * maxsplit - 1 are attn_fd's blocks at 8 waves and one q head per block -- index b is block
+// (0, b % nkv, b / nkv) of attn_fd_kernel's grid, so kvh stays the fastest-varying index and a block lands on the
+// XCD it lands on in the stand-alone launch (kv_prefetch's L2).  They run attn_fd_body unchanged but for the final
+// store, which goes out as tagged write-through words.  They never wait for another block: a split past nsp leaves
+// after its first round trip and the combine is done by the last arriver.  The remaining blocks are wo's: two
+// independent 4-wave groups per 512-thread block, each the TX row block of rowgemv_body on RP rows (its own red
+// slice; per output row the operations of rowgemv_kernel<U, 2, false, 1, false, 0> in their order, which do not
+// depend on RP).  A wo group issues its whole weight run, then re-reads its x words until every tag is current.
+// It waits on attention blocks only, which have lower block indices and are dispatched first; every wait is
+// bounded and sets *err.
+template <int U, int HD, int RP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
+void slow_attn_wo_kernel(SlowAttnWoArgs A) {
+    const AttnDecArgs<bf16_t>& at = A.at;
+    // the tag: fattn_wo_kernel's formula on the slow launches' own indices and their own buffer
+    const uint32_t gen = ((uint32_t)at.row_pos[0] * 41u + (uint32_t)A.gen) % 65535u + 1u;
+    const int natt = at.nh * at.maxsplit;
+    if ((int)blockIdx.x < natt) {
+        const int b = blockIdx.x;
+        attn_fd_body<bf16_t, HD, 8, 1, true>(at, 0, b % at.nkv, b / at.nkv, 1, A.xt, gen);
+        return;
+    }
+    // the first read of x waits for a share of the attention's duration as the position gives it: about 3 us of round
+    // trips and fold, 12 ns per position of the block's split, 1.8 us of ticket and combine past one split (10-ns ticks;
+    // profiles/slow_attn_wo_probe.txt)
+    TxPoll pw;
+    if (RP == 4 && A.delay_pct) {
+        const int npos = at.row_pos[0] + 1;
+        const int nsp = min(at.maxsplit, (npos + at.cap - 1) / at.cap);
+        const int chunk = ((npos + nsp - 1) / nsp + 15) & ~15;
+        pw.delay = (unsigned)(A.delay_pct * (300 + chunk * 12 / 10 + (nsp > 1 ? 180 : 0)) / 100);
+    }
+    pw.sleep = A.sleep;
+    pw.cheap = A.cheap;
+    rowgemv_body<U, RP, false, 1, false, 0, true, 1, 2>(A.wo, 2 * ((int)blockIdx.x - natt) + (int)(threadIdx.x >> 8), A.xt, gen,
+                                                        A.err, pw);
+}
+
+// the instantiated forms: head_dim 128, at most 4 q heads per kv head, wo rows in whole blocks of both forms (8 rows),
+// depths 2 and 4 (S2-Pro: 32 / 8 heads x 128, K 4096: depth 4)
+bool slow_attn_wo_ok(int nh, int nkv, int hd, int N, int K) {
+    const int U = rowgemv_u(K, 0);
+    return nkv > 0 && nh % nkv == 0 && attn_fd_ok(hd, nh / nkv) && hd == 128 && K == nh * hd && N > 0 && N % 8 == 0 &&
+           (U == 2 || U == 4);
+}
+
+void launch_slow_attn_wo(hipStream_t s, const SlowAttnWoArgs& A0) {
+    SlowAttnWoArgs A = A0;
+    AttnDecArgs<bf16_t>& at = A.at;
+    at.dbg = A.wo.dbg = fm_tuning().dbg;
+    if (A.sleep < 1) A.sleep = 1;
+    FMCHECK(A.delay_pct >= 0 && A.delay_pct <= 300, "fused slow attention + wo: first-read delay of 0 .. 300 per cent");
+    FMCHECK(slow_attn_wo_ok(at.nh, at.nkv, at.hd, A.wo.N, A.wo.K) && A.xt && A.err && A.gen > 0 && A.gen <= 40 && at.row_pos &&
+                at.row_slot && at.cap >= 16 && at.cnt && at.part && !at.qslab && (A.rp == 2 || A.rp == 4) && A.wo.W && A.wo.X &&
+                !A.wo.Wq && !A.wo.Wq4 && A.wo.res && A.wo.res_out && !A.wo.residx && A.wo.xr != 2,
+            "fused slow attention + wo: shapes, tag and buffers");
+    at.maxsplit = std::min(FD_NSP, FM_CEIL(at.S, at.cap));
+    at.nwb = 8;
+    at.hpb = 1;
+    const dim3 grid(at.nh * at.maxsplit + A.wo.N / (2 * A.rp)), block(512);
+    const int U = rowgemv_u(A.wo.K, 0);
+#define SW(u, hd)                                                                   \
+    (A.rp == 4 ? slow_attn_wo_kernel<u, hd, 4><<<grid, block, 0, s>>>(A) : slow_attn_wo_kernel<u, hd, 2><<<grid, block, 0, s>>>(A))
+    if (U == 2) SW(2, 128);
+    else SW(4, 128);
+#undef SW
 }

@@ -129,4 +129,14 @@ FM_KNOB(fast_dead_q, 1, FM_RANGE(0, 3))    // weight-only int8 / int4 handles on
                                            // QKV at codebooks >= 1 read from the table, bit 1 K / V only at codebook 0 -- batch 1, inside the fused fast
                                            // attention + wo, models without an o-bias (bit-identical).  S2-Pro frame, int8 /
                                            // int4: bit 0 -69 / -59 us (2.3 / 2.0 %); bit 1 -1.2 / -8.0 us, inside three times the baseline's spread: off
+FM_KNOB(slow_attn_wo, 2, FM_RANGE(0, 2))   // batch-1 bf16 unquantised slow layers: attention + wo as one launch (fm_rowgemv.hip slow_attn_wo_kernel) where
+                                           // attn_slow_plan gives attn_fd at 8 waves and fd_hpb 1, wo runs on the row-block GEMV and gemv_chain is off.
+                                           // 1: two 2-row wo blocks per 512-thread block (S2-Pro frame 58 .. 101 us slower: its last 128 blocks start
+                                           // after the attention), 2: two 4-row ones (the whole grid resident; 46 us, 1.24 %, faster with the two knobs below);
+                                           // 0, and anywhere else, the two launches (bit-identical)
+FM_KNOB(slow_aw_delay, 40, FM_RANGE(0, 300))  // slow_attn_wo 2: a wo wave's first read of x waits this per cent of the attention's duration as estimated
+                                           // from the position (SlowAttnWoArgs::delay_pct; 0: reads from the start; 40: -15 us per frame, 75 and up lose)
+FM_KNOB(slow_aw_sleep, 1, FM_SET(1, 4, 16))  // slow_attn_wo: s_sleep argument between a wo wave's reads of x (1, 4 or 16; no difference measured)
+FM_KNOB(slow_aw_cheap, 1, FM_BOOL)         // slow_attn_wo: 1: a wo wave polls one word per 128 elements of its range before its full reads (8 cache
+                                           // lines per poll, not 32; -27 us per frame)
 #endif

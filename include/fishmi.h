@@ -388,6 +388,19 @@ int fm_op_fattn_wo(int device, int quant, int gs, int fused, const float* qkv, c
                    float* kcache, float* vcache, int S, const float* w, const float* bias, const float* res,
                    int res_rows, int ldr, const float* res0, int N, int kv0, int pair, int ilp, int gen, int pos0,
                    const uint32_t* xt_init, float* y, int* status);
+/* The batch-1 slow layers' attention + wo (bf16) at nrun (slots[i], pos[i]) pairs of one layer, run one after the
+   other on the same device operands and the same tagged-word buffer.  fused != 0: ONE launch_slow_attn_wo each (rp 2
+   or 4 wo rows per 4-wave group: fm_tune slow_attn_wo 1 / 2); fused == 0: the launches it replaces (attn_fd as the
+   batch-1 frame runs it + the row GEMV, FIN).  qkv [nrun][ld]; gens[i] (1..40) with pos[i] makes run i's hand-off
+   tag; restore != 0: every run starts from the caller's cache contents, else from what the runs before it left;
+   xt_init [nh hd] or NULL pre-fills the tagged words.  w [N][nh hd], bias [N] or NULL, res [N].  Out: y [nrun][N],
+   k_rows / v_rows [nrun][nkv][hd] (the cache rows at pos[i] after run i), status[2] = {dispatchable as the frame asks
+   (0 with fused: nothing was launched), the err word after the last run}. */
+int fm_op_slow_attn_wo(int device, int fused, int rp, const float* qkv, int nh, int nkv, int hd, const float* qn,
+                       const float* kn, int qk_norm, float eps, float rope_base, const int32_t* slots, const int32_t* pos,
+                       const int32_t* gens, int nrun, int restore, int nslots, int layers, int layer, const float* kcache,
+                       const float* vcache, int S, const float* w, const float* bias, const float* res, int N,
+                       const uint32_t* xt_init, float* y, float* k_rows, float* v_rows, int* status);
 /* Dual-AR input embedding (llama.py:399-420): tok R x (C+1) row-major, x R x dim. */
 int fm_op_embed(int device, int precision, const int32_t* tok, int R, const float* emb, int vocab,
                 const float* cbemb, int dim, int num_codebooks, int codebook_size, int semantic_begin_id,

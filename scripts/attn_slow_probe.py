@@ -21,6 +21,9 @@ for st in settings:
 cfg = DualARConfig._from_fish_qwen3_omni(S2_PRO_CONFIG)
 cfg.im_end_id = S2_PRO_IM_END_ID
 cfg.max_seq_len = 4096
+# the attention launch alone: under fm_tune slow_attn_wo 1 / 2 a batch-1 bf16 frame has no attention launch of its
+# own (it runs inside slow_attn_wo_kernel; kernel_bench "slow_attn_wo" replays those), and no "attn_slow" record
+native.tune("slow_attn_wo", 0)
 rng = np.random.default_rng(1)
 sp = DualARModel.sampling(temperature=0.7, top_p=0.9, top_k=30, seed=0, mask_im_end=True)
 cases = [(1, (60, 120, 180, 250, 500, 1000, 3000)), (32, (150, 400))]

@@ -34,7 +34,7 @@ m.close()
 native.tune("debug_ts", 0)
 tag = rec[:, 0] >> 32
 smp = rec[tag == 0xFFFF]
-row = rec[tag == 0xFFFA]  # rowgemv_kernel blocks: {tag | blk, start, streamed, end, ...}
+row = rec[(tag == 0xFFFA) & ((rec[:, 0] & 0x80000000) == 0)]  # rowgemv_kernel blocks: {tag | blk, start, streamed, end, ...} (bit 31: slow_attn_wo's stand-ins)
 print(f"{len(smp)} sampler launches, {len(row)} row-GEMV block records")
 names = ["values in", "wave max", "threshold", "candidates", "ranks", "draw + store"]
 ph = np.diff(smp[:, 1:8], axis=1) / 100.0  # us

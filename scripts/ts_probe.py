@@ -49,7 +49,8 @@ for tag, name, labels in ((0xFFFE, "fast_attn2", ("load", "prep", "scores", "pv+
         aux = a[:, 0].astype(np.int64) & 0xFFFFFFFF
         print(f"{name} phases (us):", " ".join(f"{l} {v:.2f}" for l, v in zip(labels, d)),
               "| blocks", len(a), "aux mean", round(float(aux.mean()), 1))
-rg = rec[(rec[:, 0] >> 32) == 0xFFFA].astype(np.float64)
+# (aux bit 31: the fused slow attention + wo's stand-in records, whose span holds the wait for the attention)
+rg = rec[((rec[:, 0] >> 32) == 0xFFFA) & ((rec[:, 0] & 0x80000000) == 0)].astype(np.float64)
 if len(rg):
     # row-pair GEMV (fm_rowgemv.hip): launches split at gaps > 5 us between block starts
     st = rg[np.argsort(rg[:, 1])]
