@@ -555,8 +555,9 @@ inline int attn2_cap(int hd, int g, size_t esz) {
 constexpr int FD_NSP = 16;
 inline bool attn_fd_ok(int hd, int g) { return (hd == 32 || hd == 64 || hd == 128) && g >= 1 && g <= 4; }
 template <typename T> void launch_attn_fd(hipStream_t s, const AttnDecArgs<T>& a, int R);
-// batch-1 slow-model attention + wo in one launch (fm_rowgemv.hip slow_attn_wo_kernel; bf16, unquantised; fm_tune
-// slow_attn_wo).  The lowest at.nh * maxsplit linear block indices are attn_fd's blocks at 8 waves and one q head per
+// batch-1 slow-model attention + wo in one launch (fm_rowgemv.hip slow_attn_wo_kernel; bf16 compute: unquantised
+// weights under fm_tune slow_attn_wo, weight-only int8 / int4 codes under slow_attn_wo_q -- wo.Wq + wscale or wo.Wq4 +
+// wsz + gs select the form, as in launch_fattn_wo, and take no bias).  The lowest at.nh * maxsplit linear block indices are attn_fd's blocks at 8 waves and one q head per
 // block (at.cap = the minimum split, as launch_attn_fd takes it; the launcher sets maxsplit, nwb and hpb), storing
 // their output as tagged words (bf16 << 16 | gen) into xt [nh * hd] instead of at.out; the remaining blocks hold two
 // 4-wave wo row blocks of rp rows each (RowGemvArgs FIN, plain residual; X is only a valid dummy address).  gen: the
@@ -567,14 +568,15 @@ struct SlowAttnWoArgs {
     uint32_t* xt;
     int gen;
     int* err;
-    int rp;  // wo rows per 4-wave group: 2 (fm_tune slow_attn_wo 1) or 4 (slow_attn_wo 2)
+    int rp;  // wo rows per 4-wave group: 2 (fm_tune slow_attn_wo / slow_attn_wo_q 1) or 4 (2)
     // how the wo waves wait (speed only): delay_pct, per cent of the attention's duration as estimated from the
     // position, before a wave's first read of x (rp 4 only: its whole grid starts together; fm_tune slow_aw_delay);
     // sleep, the s_sleep argument between reads (slow_aw_sleep); cheap, one word per 128 elements polled ahead of
     // the full reads (slow_aw_cheap)
     int delay_pct, sleep, cheap;
 };
-bool slow_attn_wo_ok(int nh, int nkv, int hd, int N, int K);
+// qm: 0 bf16 weights, 1 int8 codes, 2 int4 code words (512-k chunks: the depth is rowgemv_u(K, qm))
+bool slow_attn_wo_ok(int nh, int nkv, int hd, int N, int K, int qm = 0);
 void launch_slow_attn_wo(hipStream_t s, const SlowAttnWoArgs& a);
 template <typename T> void launch_attn_decode3(hipStream_t s, const AttnDecArgs<T>& a, int R);
 template <typename T> void launch_fast_attn_fused(hipStream_t s, const FastFusedArgs<T>& a, int R);

@@ -70,7 +70,7 @@ static void upload_frame_rows(fm_llm* m, const int32_t* slots, int n) {
 // host's stream sync, a timed-out hand-off wait (a hang avoided) resets the counters and fails
 static void chain_err_async(fm_llm* m) {
     if (fm_tuning().gemv_chain || fm_tuning().fin_split > 1 ||
-        (m->fxt && fm_tuning().fattn_wo) || (m->sxt && fm_tuning().slow_attn_wo))
+        (m->fxt && fm_tuning().fattn_wo) || (m->sxt && (m->quant ? fm_tuning().slow_attn_wo_q : fm_tuning().slow_attn_wo)))
         HIPCHK(hipMemcpyAsync(m->h_chain_err, m->chain_err, sizeof(int), hipMemcpyDeviceToHost, m->stream));
 }
 static void chain_err_check(fm_llm* m) {

@@ -903,19 +903,26 @@ template <typename T> struct Run {
         bool tab;       // rowgemv bit 5 / fast_dead_q bit 0: the first fast layer at codebook > 0 inside fw: its q|k|v row comes from the table, no QKV launch
         bool kv0;       // rowgemv bit 6 / fast_dead_q bit 1: codebook 0: only K / V are projected (row path; int8: the tile path) and the attention reads no Q (one position: output = v)
         bool kv_only;   // the layer ends after its K / V cache write (fm_tune fast_tail: its output would be discarded)
-        bool sw;        // slow model: attention + wo as one launch (slow_attn_wo_kernel), no attention launch (fm_tune slow_attn_wo)
+        bool sw;        // slow model: attention + wo as one launch (slow_attn_wo_kernel), no attention launch (fm_tune slow_attn_wo / slow_attn_wo_q)
     };
     // fm_tune slow_attn_wo: one bf16 unquantised row of the slow stack whose attention is attn_fd at 8 waves and one q
     // head per block and whose wo runs on the row-block GEMV (so gemv_chain is off), at instantiated shapes; two layers
     // at least, so that consecutive writers of the tagged words always differ in tag, and at most 40 (the tag's
     // launch indices).  Anywhere else the layer keeps its two launches.
+    // fm_tune slow_attn_wo_q: the same on weight-only int8 / int4 handles (compact ones too: the row GEMV's row-major
+    // codes are not what compact frees), wo's row blocks on the codes with their row scales / group (scale, zero) rows;
+    // a layer with an o-bias keeps its two launches (the code forms take none).  Each knob is inert on the other's handles.
+    int slow_attn_wo_knob() const { return m->quant ? fm_tuning().slow_attn_wo_q : fm_tuning().slow_attn_wo; }
     bool slow_attn_wo_live(const Small& c, bool rf) const {
         const StackDims& d = c.d;
-        if (!(sizeof(T) == 2 && !c.is_fast && c.n == 1 && rf && !m->quant && fm_tuning().slow_attn_wo && m->sxt &&
-              !fm_tuning().gemv_chain && d.n_layer >= 2 && d.n_layer <= 40 && !c.L.wo.rm_scale && !c.L.wo.rm_sz))
+        const int qm = m->qmode();
+        const Linear& wo = c.L.wo;
+        const bool form = qm == 2 ? wo.rm_sz && !c.L.bo : (qm == 1 ? wo.rm_scale && !c.L.bo : !m->quant && !wo.rm_scale && !wo.rm_sz);
+        if (!(sizeof(T) == 2 && !c.is_fast && c.n == 1 && rf && form && slow_attn_wo_knob() && m->sxt &&
+              !fm_tuning().gemv_chain && d.n_layer >= 2 && d.n_layer <= 40))
             return false;
         const AttnSlowPlan ap = attn_slow_plan(1, d.hd, d.nh / d.nkv, attn2_frame_cap(d.hd, d.nh / d.nkv, E, false));
-        return ap.kernel == 3 && ap.nwb == 8 && ap.hpb == 1 && slow_attn_wo_ok(d.nh, d.nkv, d.hd, d.dim, d.nq());
+        return ap.kernel == 3 && ap.nwb == 8 && ap.hpb == 1 && slow_attn_wo_ok(d.nh, d.nkv, d.hd, d.dim, d.nq(), qm);
     }
     SmallPath small_path(const Small& c, bool kv_only) const {
         const StackDims& d = c.d;
@@ -1067,14 +1074,14 @@ template <typename T> struct Run {
                 // any max_seq_len here; 25 layers: 1599 apart (the fast launches' formula has the same property)
                 W.gen = 1 + c.layer;
                 W.err = m->chain_err;
-                W.rp = fm_tuning().slow_attn_wo == 2 ? 4 : 2;
+                W.rp = slow_attn_wo_knob() == 2 ? 4 : 2;
                 W.delay_pct = fm_tuning().slow_aw_delay;
                 W.sleep = fm_tuning().slow_aw_sleep;
                 W.cheap = fm_tuning().slow_aw_cheap;
                 hipStream_t st = s;
                 auto go = [st, W] { launch_slow_attn_wo(st, W); };
-                // a class of its own (attention + GEMV), booked with wo's weight bytes
-                launch("slow_attn_wo", rowgemv_wbytes(r), 2.0 * r.N * r.K, go);
+                // a class of its own (attention + GEMV), booked with wo's weight bytes; the code forms in theirs
+                launch(m->quant ? "slow_attn_wo_q" : "slow_attn_wo", rowgemv_wbytes(r), 2.0 * r.N * r.K, go);
                 return;
             }
             if (!p.fw) {

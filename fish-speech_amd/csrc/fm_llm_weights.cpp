@@ -471,9 +471,9 @@ void finalize(fm_llm* m) {
         // (two rows: fm_tune fast_pair publishes codebook positions 0 and 1 in one launch)
         m->fxt = (uint32_t*)m->dalloc(2 * (size_t)m->fdm.nh * m->fdm.hd * sizeof(uint32_t));  // tags 0: never current
     // fm_tune slow_attn_wo: the slow layers' tagged attention words, one row (tags 0: never current), on the handles
-    // whose batch-1 frame can take the fused launch
-    if (m->prec == FM_PREC_BF16 && !m->quant && m->sd.n_layer >= 2 && m->sd.n_layer <= 40 &&
-        slow_attn_wo_ok(m->sd.nh, m->sd.nkv, m->sd.hd, m->sd.dim, m->sd.nq()))
+    // whose batch-1 frame can take the fused launch (weight-only int8 / int4 ones under slow_attn_wo_q: the form of their codes)
+    if (m->prec == FM_PREC_BF16 && (!m->quant || m->qmode()) && m->sd.n_layer >= 2 && m->sd.n_layer <= 40 &&
+        slow_attn_wo_ok(m->sd.nh, m->sd.nkv, m->sd.hd, m->sd.dim, m->sd.nq(), m->qmode()))
         m->sxt = (uint32_t*)m->dalloc((size_t)m->sd.nq() * sizeof(uint32_t));
     m->emb = W(m, "embeddings.weight");
     m->cbemb = W(m, "codebook_embeddings.weight");

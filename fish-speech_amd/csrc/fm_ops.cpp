@@ -603,8 +603,12 @@ void fattn_wo_op(hipStream_t s, const FattnWoOp& o) {
 // the batch-1 slow layers' attention + wo at nrun (slot, position) pairs, one after the other on the same device
 // operands: one launch_slow_attn_wo each (fused), or the two launches it replaces (launch_attn_fd as attn_slow_plan
 // runs it at one row + launch_rowgemv FIN).  The tagged-word buffer lives through the call, so a run finds the words
-// its predecessors left
+// its predecessors left.  quant (fm_op_slow_attn_wo_q): w is quantised and packed on the device first, by the model's
+// rule and pack launchers as fattn_wo_op does, and both compositions run on the row-major codes
 struct SlowAttnWoOp {
+    int quant, gs;
+    int8_t* q_out;
+    float *scale_out, *zero_out;
     int fused, rp;
     const float* qkv;
     int nh, nkv, hd;
@@ -626,12 +630,53 @@ void slow_attn_wo_op(hipStream_t s, const SlowAttnWoOp& o) {
     const int nh = o.nh, nkv = o.nkv, hd = o.hd, S = o.S, N = o.N, K = nh * hd, ld = (nh + 2 * nkv) * hd, g = nh / nkv;
     const AttnSlowPlan ap = attn_slow_plan(1, hd, g, attn2_frame_cap(hd, g, 2, false));
     // "not dispatchable" is a status, not a launch: what small_path asks before it takes the fused launch
-    o.status[0] = ap.kernel == 3 && ap.nwb == 8 && ap.hpb == 1 && slow_attn_wo_ok(nh, nkv, hd, N, K) && !fm_tuning().gemv_chain;
+    const int qm = o.quant == FM_QUANT_INT4 ? 2 : (o.quant == FM_QUANT_INT8 ? 1 : 0);
+    o.status[0] = ap.kernel == 3 && ap.nwb == 8 && ap.hpb == 1 && slow_attn_wo_ok(nh, nkv, hd, N, K, qm) && !fm_tuning().gemv_chain;
     o.status[1] = 0;
     if (o.fused && !o.status[0]) return;
     FMCHECK(ap.kernel == 3, "the unfused composition runs attn_fd");
     RowGemvArgs r{};
-    r.W = b.upload<bf16_t>(o.w, (size_t)N * K);
+    bf16_t* wd = b.upload<bf16_t>(o.w, (size_t)N * K);
+    if (qm == 1) {  // the quantizers of fm_llm_set_quant / _int4 on the device, as rowgemv_op and fm_op_quant4 run them
+        int8_t* dq = (int8_t*)b.alloc((size_t)N * K);
+        bf16_t* ds = (bf16_t*)b.alloc((size_t)N * 2);
+        launch_quant_rows<bf16_t>(s, wd, N, K, dq, ds);
+        HIPCHK(hipGetLastError());
+        r.Wq = dq;
+        r.wscale = ds;
+        if (o.q_out) {
+            HIPCHK(hipMemcpyAsync(o.q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        if (o.scale_out) download<bf16_t>(ds, (size_t)N, o.scale_out, s);
+    } else if (qm == 2) {
+        const int ng = K / o.gs;
+        uint8_t* dq = (uint8_t*)b.alloc((size_t)N * K);
+        uint32_t* dsz = (uint32_t*)b.alloc((size_t)N * ng * 4);
+        uint32_t* words = (uint32_t*)b.alloc((size_t)N * K / 2);
+        launch_quant4(s, wd, N, K, o.gs, dq, dsz);
+        launch_pack_q4_rows(s, dq, N, K, words);
+        HIPCHK(hipGetLastError());
+        r.Wq4 = words;
+        r.wsz = dsz;
+        r.gs = o.gs;
+        if (o.q_out) {
+            HIPCHK(hipMemcpyAsync(o.q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        if (o.scale_out || o.zero_out) {  // one word per (row, group): scale in the low half, zero in the high one
+            std::vector<uint32_t> hs((size_t)N * ng);
+            HIPCHK(hipMemcpyAsync(hs.data(), dsz, hs.size() * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (size_t i = 0; i < hs.size(); ++i) {
+                const uint32_t us = hs[i] << 16, uz = hs[i] & 0xffff0000u;
+                if (o.scale_out) memcpy(&o.scale_out[i], &us, 4);
+                if (o.zero_out) memcpy(&o.zero_out[i], &uz, 4);
+            }
+        }
+    } else {
+        r.W = wd;
+    }
     if (o.bias) r.bias = b.upload<bf16_t>(o.bias, (size_t)N);
     r.res = b.upload<bf16_t>(o.res, (size_t)N);
     r.ldr = N;
@@ -1400,8 +1445,39 @@ int fm_op_slow_attn_wo(int device, int fused, int rp, const float* qkv, int nh, 
             check_slot_rows(1, &slots[i], nullptr, nslots, layers, layer, S);
         }
         StreamGuard g(device);
-        const SlowAttnWoOp o{fused, rp, qkv, nh, nkv, hd, qn, kn, qk_norm, eps, rope_base, slots, pos, gens, nrun, restore,
-                             nslots, layers, layer, kcache, vcache, S, w, bias, res, N, xt_init, y, k_rows, v_rows, status};
+        const SlowAttnWoOp o{FM_QUANT_NONE, 0, nullptr, nullptr, nullptr, fused, rp, qkv, nh, nkv, hd, qn, kn, qk_norm, eps,
+                             rope_base, slots, pos, gens, nrun, restore, nslots, layers, layer, kcache, vcache, S, w, bias,
+                             res, N, xt_init, y, k_rows, v_rows, status};
+        slow_attn_wo_op(g.s, o);
+    });
+}
+
+int fm_op_slow_attn_wo_q(int device, int quant, int gs, int fused, int rp, const float* qkv, int nh, int nkv, int hd,
+                         const float* qn, const float* kn, int qk_norm, float eps, float rope_base, const int32_t* slots,
+                         const int32_t* pos, const int32_t* gens, int nrun, int restore, int nslots, int layers, int layer,
+                         const float* kcache, const float* vcache, int S, const float* w, const float* bias,
+                         const float* res, int N, const uint32_t* xt_init, float* y, float* k_rows, float* v_rows,
+                         int* status, int8_t* q_out, float* scale_out, float* zero_out) {
+    return fm_guard([&] {
+        FMCHECK(qkv && slots && pos && gens && kcache && vcache && w && res && y && k_rows && v_rows && status, "null argument");
+        FMCHECK(quant == FM_QUANT_INT8 || quant == FM_QUANT_INT4, "quant must be int8 or int4");
+        FMCHECK(!bias, "the int8 / int4 row forms take no bias");
+        FMCHECK(!qk_norm || (qn && kn), "qk_norm needs both norm weights");
+        FMCHECK(nh >= 1 && nkv >= 1 && nh % nkv == 0 && hd >= 8 && hd <= 128 && hd % 8 == 0, "bad heads / head_dim");
+        FMCHECK(S >= 16 && S % 16 == 0 && S <= 65536 && N >= 16 && N % 16 == 0 && nrun >= 1 && nrun <= 4096, "bad S / N / runs");
+        FMCHECK(rp == 2 || rp == 4, "rp must be 2 or 4");
+        // what launch_rowgemv asks of the code forms: K in whole 512-k chunks at an instantiated depth, int4 groups of
+        // whole 8-code words that divide K
+        FMCHECK(rowgemv_u(nh * hd, 1) > 0, "the int8 / int4 row forms need K = nh * hd in whole 512-k chunks");
+        FMCHECK(quant != FM_QUANT_INT4 || (gs >= 8 && gs % 8 == 0 && (nh * hd) % gs == 0), "bad int4 group size");
+        for (int i = 0; i < nrun; ++i) {
+            FMCHECK(pos[i] >= 0 && pos[i] < S && gens[i] >= 1 && gens[i] <= 40, "bad position / gen");
+            check_slot_rows(1, &slots[i], nullptr, nslots, layers, layer, S);
+        }
+        StreamGuard g(device);
+        const SlowAttnWoOp o{quant, gs, q_out, scale_out, zero_out, fused, rp, qkv, nh, nkv, hd, qn, kn, qk_norm, eps,
+                             rope_base, slots, pos, gens, nrun, restore, nslots, layers, layer, kcache, vcache, S, w, nullptr,
+                             res, N, xt_init, y, k_rows, v_rows, status};
         slow_attn_wo_op(g.s, o);
     });
 }

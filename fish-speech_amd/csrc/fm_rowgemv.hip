@@ -1169,7 +1169,8 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
 }
 
 // =========================================================================================
-// Slow-model attention + wo in ONE launch (batch 1, bf16, unquantised; fm_tune slow_attn_wo).
+// Slow-model attention + wo in ONE launch (batch 1, bf16 compute; fm_tune slow_attn_wo on unquantised handles,
+// slow_attn_wo_q on weight-only int8 / int4 ones).
 //
 // The same arrangement as fattn_wo_kernel with the slow decode attention as the producer.  Linear block indices
 // 0 .. nh * maxsplit - 1 are attn_fd's blocks at 8 waves and one q head per block -- index b is block
@@ -1178,11 +1179,15 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
 // store, which goes out as tagged write-through words.  They never wait for another block: a split past nsp leaves
 // after its first round trip and the combine is done by the last arriver.  The remaining blocks are wo's: two
 // independent 4-wave groups per 512-thread block, each the TX row block of rowgemv_body on RP rows (its own red
-// slice; per output row the operations of rowgemv_kernel<U, 2, false, 1, false, 0> in their order, which do not
-// depend on RP).  A wo group issues its whole weight run, then re-reads its x words until every tag is current.
-// It waits on attention blocks only, which have lower block indices and are dispatched first; every wait is
-// bounded and sets *err.
-template <int U, int HD, int RP>
+// slice; per output row the operations of rowgemv_kernel<U, 2, false, 1, false, QM> in their order, which do not
+// depend on RP nor on the group's place in the block).  QM 1 (int8 codes): the lane's xs over its chunks in chunk
+// order, the four wave sums of xs added in wave order and the epilogue round(round(v - 128 * sum x) * scale[row])
+// are the stand-alone kernel's; the scale is row n0 + tid % RP's, loaded in the first round trip.  QM 2 (int4 code
+// words): per word the dot8r pair (B and the lane's sum of x) and the two fmas of the word's group (scale, zero), of
+// row n0 + r, in chunk order.  A wo group issues its whole weight run (int4: its (scale, zero) words too), then
+// re-reads its x words until every tag is current.  It waits on attention blocks only, which have lower block
+// indices and are dispatched first; every wait is bounded and sets *err.
+template <int U, int HD, int RP, int QM = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
 void slow_attn_wo_kernel(SlowAttnWoArgs A) {
     const AttnDecArgs<bf16_t>& at = A.at;
@@ -1206,14 +1211,17 @@ void slow_attn_wo_kernel(SlowAttnWoArgs A) {
     }
     pw.sleep = A.sleep;
     pw.cheap = A.cheap;
-    rowgemv_body<U, RP, false, 1, false, 0, true, 1, 2>(A.wo, 2 * ((int)blockIdx.x - natt) + (int)(threadIdx.x >> 8), A.xt, gen,
+    rowgemv_body<U, RP, false, 1, false, QM, true, 1, 2>(A.wo, 2 * ((int)blockIdx.x - natt) + (int)(threadIdx.x >> 8), A.xt, gen,
                                                         A.err, pw);
 }
 
 // the instantiated forms: head_dim 128, at most 4 q heads per kv head, wo rows in whole blocks of both forms (8 rows),
-// depths 2 and 4 (S2-Pro: 32 / 8 heads x 128, K 4096: depth 4)
-bool slow_attn_wo_ok(int nh, int nkv, int hd, int N, int K) {
-    const int U = rowgemv_u(K, 0);
+// depths 2 and 4 (S2-Pro: 32 / 8 heads x 128, K 4096: depth 4 of 256-k chunks on bf16 weights, depth 2 of 512-k
+// chunks on int8 / int4 codes).  Every form, qm 1 / 2 included, holds the gate: 115 VGPRs, no scratch, LDS that lets
+// two 512-thread blocks share a CU (profiles/slow_attn_wo_q_regs.txt)
+bool slow_attn_wo_ok(int nh, int nkv, int hd, int N, int K, int qm) {
+    if (qm < 0 || qm > 2) return false;
+    const int U = rowgemv_u(K, qm);
     return nkv > 0 && nh % nkv == 0 && attn_fd_ok(hd, nh / nkv) && hd == 128 && K == nh * hd && N > 0 && N % 8 == 0 &&
            (U == 2 || U == 4);
 }
@@ -1223,19 +1231,30 @@ void launch_slow_attn_wo(hipStream_t s, const SlowAttnWoArgs& A0) {
     AttnDecArgs<bf16_t>& at = A.at;
     at.dbg = A.wo.dbg = fm_tuning().dbg;
     if (A.sleep < 1) A.sleep = 1;
+    const int qm = A.wo.Wq4 ? 2 : (A.wo.Wq ? 1 : 0);
     FMCHECK(A.delay_pct >= 0 && A.delay_pct <= 300, "fused slow attention + wo: first-read delay of 0 .. 300 per cent");
-    FMCHECK(slow_attn_wo_ok(at.nh, at.nkv, at.hd, A.wo.N, A.wo.K) && A.xt && A.err && A.gen > 0 && A.gen <= 40 && at.row_pos &&
-                at.row_slot && at.cap >= 16 && at.cnt && at.part && !at.qslab && (A.rp == 2 || A.rp == 4) && A.wo.W && A.wo.X &&
-                !A.wo.Wq && !A.wo.Wq4 && A.wo.res && A.wo.res_out && !A.wo.residx && A.wo.xr != 2,
+    FMCHECK(slow_attn_wo_ok(at.nh, at.nkv, at.hd, A.wo.N, A.wo.K, qm) && A.xt && A.err && A.gen > 0 && A.gen <= 40 && at.row_pos &&
+                at.row_slot && at.cap >= 16 && at.cnt && at.part && !at.qslab && (A.rp == 2 || A.rp == 4) && A.wo.X &&
+                A.wo.res && A.wo.res_out && !A.wo.residx && A.wo.xr != 2,
             "fused slow attention + wo: shapes, tag and buffers");
+    FMCHECK(qm == 2 ? (A.wo.wsz && A.wo.gs > 0 && A.wo.gs % 8 == 0 && A.wo.K % A.wo.gs == 0 && !A.wo.bias && !A.wo.Wq && !A.wo.W)
+                    : (qm == 1 ? (A.wo.wscale && !A.wo.bias && !A.wo.W) : A.wo.W != nullptr),
+            "fused slow attention + wo: bf16 weights, int8 codes + row scales or int4 code words + group (scale, zero), "
+            "the code forms without bias");
     at.maxsplit = std::min(FD_NSP, FM_CEIL(at.S, at.cap));
     at.nwb = 8;
     at.hpb = 1;
     const dim3 grid(at.nh * at.maxsplit + A.wo.N / (2 * A.rp)), block(512);
-    const int U = rowgemv_u(A.wo.K, 0);
-#define SW(u, hd)                                                                   \
-    (A.rp == 4 ? slow_attn_wo_kernel<u, hd, 4><<<grid, block, 0, s>>>(A) : slow_attn_wo_kernel<u, hd, 2><<<grid, block, 0, s>>>(A))
-    if (U == 2) SW(2, 128);
-    else SW(4, 128);
+    const int U = rowgemv_u(A.wo.K, qm);
+    auto go = [&](auto q) {
+        constexpr int Q = decltype(q)::value;
+#define SW(u, hd) \
+    (A.rp == 4 ? slow_attn_wo_kernel<u, hd, 4, Q><<<grid, block, 0, s>>>(A) : slow_attn_wo_kernel<u, hd, 2, Q><<<grid, block, 0, s>>>(A))
+        if (U == 2) SW(2, 128);
+        else SW(4, 128);
 #undef SW
+    };
+    if (qm == 2) go(std::integral_constant<int, 2>{});
+    else if (qm == 1) go(std::integral_constant<int, 1>{});
+    else go(std::integral_constant<int, 0>{});
 }

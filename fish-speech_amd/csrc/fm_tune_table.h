@@ -139,4 +139,9 @@ FM_KNOB(slow_aw_delay, 40, FM_RANGE(0, 300))  // slow_attn_wo 2: a wo wave's fir
 FM_KNOB(slow_aw_sleep, 1, FM_SET(1, 4, 16))  // slow_attn_wo: s_sleep argument between a wo wave's reads of x (1, 4 or 16; no difference measured)
 FM_KNOB(slow_aw_cheap, 1, FM_BOOL)         // slow_attn_wo: 1: a wo wave polls one word per 128 elements of its range before its full reads (8 cache
                                            // lines per poll, not 32; -27 us per frame)
+FM_KNOB(slow_attn_wo_q, 0, FM_RANGE(0, 2)) // slow_attn_wo's launch on weight-only int8 / int4 handles (bf16 compute, layers without an o-bias; slow_attn_wo
+                                           // keeps governing unquantised bf16 and nothing else, this knob is inert there): wo's row blocks read the row-major
+                                           // codes (QM 1 / 2 of rowgemv_body).  0 the two launches, 1 two rows per 4-wave group, 2 four; the three wait knobs
+                                           // above are shared (bit-identical).  S2-Pro frame, int8 / int4: 2 loses 17 / 26 us
+                                           // (0.6 / 0.9 %), 1 loses 84 / 96 us, at baseline spreads of 3 / 4 us: off
 #endif

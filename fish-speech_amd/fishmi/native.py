@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "fm_op_codec_conv", "fm_op_codec_resunit", "fm_op_codec_window_attn", "fm_op_codec_rope_qk", "fm_op_codec_dwconv_ln",
     "fm_op_codec_rvq_decode", "fm_op_codec_snake", "fm_op_codec_silu_mul", "fm_op_codec_wn_fold", "fm_op_codec_vq_encode",
     "fm_op_decode_attn_ex", "fm_op_prompt_attn_ex", "fm_op_qk_rope_cache", "fm_op_fast_attn", "fm_op_fattn_wo",
-    "fm_op_slow_attn_wo",
+    "fm_op_slow_attn_wo", "fm_op_slow_attn_wo_q",
 ]
 
 
@@ -179,6 +179,10 @@ def lib():
     L.fm_op_slow_attn_wo.argtypes = [i32, i32, i32, pf32, i32, i32, i32, pf32, pf32, i32, f32, f32, pi32, pi32, pi32, i32, i32,
                                      i32, i32, i32, pf32, pf32, i32, pf32, pf32, pf32, i32, ctypes.POINTER(ctypes.c_uint32),
                                      pf32, pf32, pf32, pi32]
+    L.fm_op_slow_attn_wo_q.argtypes = [i32, i32, i32, i32, i32, pf32, i32, i32, i32, pf32, pf32, i32, f32, f32, pi32, pi32, pi32,
+                                       i32, i32, i32, i32, i32, pf32, pf32, i32, pf32, pf32, pf32, i32,
+                                       ctypes.POINTER(ctypes.c_uint32), pf32, pf32, pf32, pi32, ctypes.POINTER(ctypes.c_int8),
+                                       pf32, pf32]
     L.fm_op_embed.argtypes = [i32, i32, pi32, i32, pf32, i32, pf32, i32, i32, i32, i32, i32, i32, pf32]
     L.fm_op_quant4.argtypes = [i32, pf32, i32, i32, i32, ctypes.POINTER(ctypes.c_uint8), pf32, pf32, pf32, pf32, i32,
                                pf32, pf32]

@@ -287,6 +287,47 @@ def slow_attn_wo(qkv, nh, nkv, hd, slots, pos, kcache, vcache, rope_base, w, res
     return y, kr, vr, bool(status[0]), int(status[1])
 
 
+def slow_attn_wo_q(qkv, nh, nkv, hd, slots, pos, kcache, vcache, rope_base, w, res, quant="int8", gs=128, bias=None,
+                   qn=None, kn=None, eps=1e-6, layer=0, fused=True, rp=2, gens=None, restore=True, xt_init=None, device=0):
+    """fm_op_slow_attn_wo_q: slow_attn_wo on weight-only codes -- w (N, nh*hd) is quantised on the device ("int8": row
+    scales; "int4": groups of gs) and both compositions read the row-major codes.  Returns (y (nrun, N), k_rows, v_rows
+    (nrun, nkv, hd), ok, err, q, scale, zero): q (N, K) int8 codes (int4: 0..15), scale (N,) / (N, K/gs), zero (N, K/gs)
+    or None; ok False with fused = not dispatchable, nothing was launched (q, scale, zero are then zeros)."""
+    raw = np.ascontiguousarray(qkv, np.float32).reshape(-1, (nh + 2 * nkv) * hd)
+    n = raw.shape[0]
+    sl = np.ascontiguousarray(np.broadcast_to(np.asarray(slots, np.int32), (n,)))
+    ps = np.ascontiguousarray(np.broadcast_to(np.asarray(pos, np.int32), (n,)))
+    ge = np.ascontiguousarray(np.broadcast_to(np.asarray(1 if gens is None else gens, np.int32), (n,)))
+    kc, vc = _caches(kcache, vcache, nkv, hd)
+    nslots, layers, _, S, _ = kc.shape
+    ww = np.ascontiguousarray(w, np.float32)
+    N, K = ww.shape[0], nh * hd
+    assert ww.shape == (N, K)
+    rr = np.ascontiguousarray(res, np.float32).reshape(N)
+    bi = None if bias is None else np.ascontiguousarray(bias, np.float32)
+    xt = None if xt_init is None else np.ascontiguousarray(xt_init, np.uint32)
+    assert xt is None or xt.shape == (K,)
+    qk, qn_, kn_ = _norm_w(qn, kn, hd)
+    q4 = quant == "int4"
+    assert quant in ("int8", "int4")
+    y = np.zeros((n, N), np.float32)
+    kr = np.zeros((n, nkv, hd), np.float32)
+    vr = np.zeros((n, nkv, hd), np.float32)
+    q = np.zeros((N, K), np.int8)
+    ng = max(K // gs, 1) if q4 and gs > 0 else 1
+    sc = np.zeros((N, ng) if q4 else (N,), np.float32)
+    zr = np.zeros((N, ng), np.float32) if q4 else None
+    status = np.zeros(2, np.int32)
+    native.check(native.lib().fm_op_slow_attn_wo_q(
+        device, 2 if q4 else 1, int(gs), int(fused), int(rp), native.f32p(raw), nh, nkv, hd, native.f32p(qn_),
+        native.f32p(kn_), qk, float(eps), float(rope_base), native.i32p(sl), native.i32p(ps), native.i32p(ge), n,
+        int(restore), nslots, layers, int(layer), native.f32p(kc), native.f32p(vc), S, native.f32p(ww), _opt(bi),
+        native.f32p(rr), N, None if xt is None else xt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), native.f32p(y),
+        native.f32p(kr), native.f32p(vr), native.i32p(status), q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+        native.f32p(sc), None if zr is None else native.f32p(zr)))
+    return y, kr, vr, bool(status[0]), int(status[1]), q, sc, zr
+
+
 def embed(tok, emb, cbemb, num_codebooks, codebook_size, semantic_begin_id, semantic_end_id, scale,
           precision="bf16", device=0):
     """tok: (R, C+1) rows (row r = one position's [text/semantic token, codes...])."""

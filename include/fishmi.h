@@ -291,6 +291,14 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    same way, by the quantised model's own launch), bit 1 (2) K / V only at codebook 0.  They act at batch
    1 in bf16 compute where the fused fast attention + wo launch runs, on models configured without an
    o-bias, and change no output bit; inert on unquantised models and everywhere else.
+   "slow_attn_wo" 0..2 (default 2): a batch-1 bf16 unquantised frame runs each slow layer's attention and
+   its wo as one launch (1: two wo rows per 4-wave group, 2: four) where the attention is attn_fd at 8 waves
+   and one q head per block, wo is on the row-block GEMV, "gemv_chain" is off and head_dim is 128; anywhere
+   else, and at 0, the two launches.  "slow_attn_wo_q" 0..2 (default 0): the same launch, with the same
+   meaning of 1 and 2, on weight-only int8 / int4 handles (compact ones too) whose slow layers have no
+   o-bias: wo's row blocks read the row-major codes.  Each of the two knobs is inert on the other's
+   handles; both share "slow_aw_delay", "slow_aw_sleep" and "slow_aw_cheap" (how wo's waves wait: speed
+   only) and change no output bit.
    Compact handles (fm_llm_set_quant_compact) hold no bf16 copy of their quantised linears, so the six knobs
    that would pick a reader of that copy are ignored for such a handle, which keeps its default routing:
    "bstream" 0 and "bstream_acc" 0 (its batched frames stay on the accumulating kernel's code forms),
@@ -401,6 +409,19 @@ int fm_op_slow_attn_wo(int device, int fused, int rp, const float* qkv, int nh, 
                        const int32_t* gens, int nrun, int restore, int nslots, int layers, int layer, const float* kcache,
                        const float* vcache, int S, const float* w, const float* bias, const float* res, int N,
                        const uint32_t* xt_init, float* y, float* k_rows, float* v_rows, int* status);
+/* fm_op_slow_attn_wo on weight-only codes (fm_tune slow_attn_wo_q): the bf16-valued w [N][nh hd] is quantised on the
+   device by the model's own rule -- quant FM_QUANT_INT8: row scales; FM_QUANT_INT4: groups of gs along K, (scale,
+   zero) per group -- and packed row-major as the model's row GEMV reads it; then, per (slots[i], pos[i]) pair, ONE
+   launch_slow_attn_wo on the codes (fused != 0) or attn_fd + the row GEMV (FIN) on the same codes (fused == 0).
+   status, restore, gens and xt_init as above.  q_out [N][nh hd] (int8: the codes; int4: the codes 0..15, one per
+   byte), scale_out (int8 [N]; int4 [N][nh hd / gs]) and zero_out (int4) may be NULL.  FM_ERR_ARG for a bias, for
+   nh hd not in whole 512-k chunks and for a gs that is no multiple of 8 or does not divide nh hd. */
+int fm_op_slow_attn_wo_q(int device, int quant, int gs, int fused, int rp, const float* qkv, int nh, int nkv, int hd,
+                         const float* qn, const float* kn, int qk_norm, float eps, float rope_base, const int32_t* slots,
+                         const int32_t* pos, const int32_t* gens, int nrun, int restore, int nslots, int layers, int layer,
+                         const float* kcache, const float* vcache, int S, const float* w, const float* bias,
+                         const float* res, int N, const uint32_t* xt_init, float* y, float* k_rows, float* v_rows,
+                         int* status, int8_t* q_out, float* scale_out, float* zero_out);
 /* Dual-AR input embedding (llama.py:399-420): tok R x (C+1) row-major, x R x dim. */
 int fm_op_embed(int device, int precision, const int32_t* tok, int R, const float* emb, int vocab,
                 const float* cbemb, int dim, int num_codebooks, int codebook_size, int semantic_begin_id,

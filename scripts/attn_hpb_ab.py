@@ -3,9 +3,10 @@ fd_min16: its split length) in ONE process, as scripts/fast_pair_ab.py does it: 
 as bench.py makes them, batch 1, graph-replayed frames after a PROMPT-token prompt, the settings
 interleaved (A B C A B C ...).  Prints ms per frame per repetition, each setting's mean and its own
 max - min, and whether the gain over the first setting clears three times that setting's spread (this
-project's bar for keeping a default).  Every setting must sample the first one's columns.
+project's bar for keeping a default).  Every setting must sample the first one's columns.  QUANT=int8 / int4
+(GROUPSIZE, default 128) times a weight-only handle (fm_tune slow_attn_wo_q and its like).
 
-usage: [SETTINGS="fd_hpb=4;fd_hpb=1;fd_hpb=2"] [PROMPT=64] python scripts/attn_hpb_ab.py [repetitions >= 3] [frames]"""
+usage: [SETTINGS="fd_hpb=4;fd_hpb=1;fd_hpb=2"] [PROMPT=64] [QUANT=int8|int4] python scripts/attn_hpb_ab.py [repetitions >= 3] [frames]"""
 import os
 import sys
 import time
@@ -21,6 +22,8 @@ from fishmi.llm import DualARModel  # noqa: E402
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 6
 FRAMES = int(sys.argv[2]) if len(sys.argv) > 2 else 400
 PROMPT = int(os.environ.get("PROMPT", "64"))
+QUANT = os.environ.get("QUANT") or None
+GROUPSIZE = int(os.environ.get("GROUPSIZE", "128"))
 SETTINGS = [dict((k, int(v)) for k, v in (kv.split("=") for kv in s.split(",") if kv))
             for s in os.environ.get("SETTINGS", "fd_hpb=4;fd_hpb=1;fd_hpb=2").split(";")]
 NAMES = [",".join(f"{k}={v}" for k, v in s.items()) for s in SETTINGS]
@@ -30,8 +33,9 @@ cfg = DualARConfig._from_fish_qwen3_omni(S2_PRO_CONFIG)
 cfg.im_end_id = S2_PRO_IM_END_ID
 cfg.max_seq_len = 1024
 t0 = time.perf_counter()
-m = DualARModel.synthetic(cfg, seed=0, log2_half=5, device=0, precision="bf16", max_slots=1)
-print(f"model ready in {time.perf_counter() - t0:.1f} s; prompt {PROMPT}, {FRAMES} frames, {REPS} repetitions")
+m = DualARModel.synthetic(cfg, seed=0, log2_half=5, device=0, precision="bf16", max_slots=1, quant=QUANT,
+                          groupsize=GROUPSIZE)
+print(f"model ready in {time.perf_counter() - t0:.1f} s; quant {QUANT}; prompt {PROMPT}, {FRAMES} frames, {REPS} repetitions")
 p = np.zeros((cfg.num_codebooks + 1, PROMPT), np.int32)
 p[0] = np.random.default_rng(1).integers(16, cfg.semantic_begin_id, PROMPT)
 sp = DualARModel.sampling(mask_im_end=True)

@@ -24,6 +24,7 @@ cfg.max_seq_len = 4096
 # the attention launch alone: under fm_tune slow_attn_wo 1 / 2 a batch-1 bf16 frame has no attention launch of its
 # own (it runs inside slow_attn_wo_kernel; kernel_bench "slow_attn_wo" replays those), and no "attn_slow" record
 native.tune("slow_attn_wo", 0)
+native.tune("slow_attn_wo_q", 0)  # (the same on a weight-only handle: kernel_bench "slow_attn_wo_q")
 rng = np.random.default_rng(1)
 sp = DualARModel.sampling(temperature=0.7, top_p=0.9, top_k=30, seed=0, mask_im_end=True)
 cases = [(1, (60, 120, 180, 250, 500, 1000, 3000)), (32, (150, 400))]

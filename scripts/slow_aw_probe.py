@@ -4,8 +4,8 @@ output or partial stored; 0xFFFB: the combiner's end) and the wo groups' first w
 x words current, dot products done, end; aux = full reads of x | one-word polls << 16), per launch, relative to the launch's first block start
 (us), at several context lengths.
 
-usage: python scripts/slow_aw_probe.py [slow_attn_wo value, default 2] [context ...  default 64 180 280 600]
-(the wait knobs slow_aw_cheap / slow_aw_delay / slow_aw_sleep as in force: their defaults, or FISHMI_TUNE's)"""
+usage: [QUANT=int8|int4] python scripts/slow_aw_probe.py [slow_attn_wo value, default 2] [context ...  default 64 180 280 600]
+(QUANT: a weight-only handle, the value is slow_attn_wo_q's, GROUPSIZE default 128; the wait knobs slow_aw_cheap / slow_aw_delay / slow_aw_sleep as in force: their defaults, or FISHMI_TUNE's)"""
 import os
 import sys
 
@@ -22,9 +22,12 @@ CTX = [int(a) for a in sys.argv[2:]] or [64, 180, 280, 600]
 cfg = DualARConfig._from_fish_qwen3_omni(S2_PRO_CONFIG)
 cfg.im_end_id = S2_PRO_IM_END_ID
 cfg.max_seq_len = 1024
-native.tune("slow_attn_wo", KNOB)
-print(f"fm_tune slow_attn_wo {KNOB}")
-m = DualARModel.synthetic(cfg, seed=0, log2_half=5, device=0, precision="bf16", max_slots=1)
+QUANT = os.environ.get("QUANT") or None
+KEY = "slow_attn_wo_q" if QUANT else "slow_attn_wo"
+native.tune(KEY, KNOB)
+print(f"fm_tune {KEY} {KNOB}" + (f" (weight-only {QUANT})" if QUANT else ""))
+m = DualARModel.synthetic(cfg, seed=0, log2_half=5, device=0, precision="bf16", max_slots=1, quant=QUANT,
+                          groupsize=int(os.environ.get("GROUPSIZE", "128")))
 names = ["att rows ready(max)", "att passes done(max)", "att stored(max)", "wo last start", "wo weights issued",
          "wo x current", "wo x current(max)", "wo dots done", "wo end(mean)", "wo end(max)", "wo reads of x",
          "wo reads of x(max)", "wo one-word polls", "wo one-word polls(max)"]
