@@ -90,6 +90,13 @@ struct fm_codec {
     };
     std::map<int, StreamCtx> sctx;
     int active_sid = 0, next_sid = 1;
+    // batched pass (fm_codec_stream_decode_batch): the frames between segments, the device descriptor
+    // table (one upload per call) and the host staging of the table, the codes and the waveform
+    int batch_gap = 0, batch_nmax = 0;
+    void* d_table = nullptr;
+    std::vector<uint8_t> h_table;
+    std::vector<int32_t> h_codes;
+    std::vector<float> h_wave;
     // encode side (fm_codec_enable_encoder / fm_codec_encode)
     int enc_dim = 0, enc_layers = 0;        // enc_dim 0: encoder not enabled
     EBlock eblk[4];
@@ -600,16 +607,27 @@ static void finalize(fm_codec* m) {
     for (int l = 0; l < c.t_layers; ++l) m->dstate(&m->st_kv[l], (size_t)(c.window - 1) * 3 * HD * E);
     for (int u = 0; u < 2; ++u) m->dstate(&m->st_dw[u], (size_t)6 * D * E);
     m->dstate(&m->st_c0, (size_t)6 * D * E);
+    // (the conv sites with the rows per code frame of the buffer each reads: the gap of a batched pass)
+    std::vector<CodecSite> sites = {{6, 2}, {6, 4}, {6, 4}};
     {
-        int cc = ch;
+        int cc = ch, Lb = 4;
         const int dl[3] = {1, 3, 9};
         for (int b = 0; b < 4; ++b) {
             m->dstate(&m->st_ct[b], (size_t)cc * E);
-            for (int r = 0; r < 3; ++r) m->dstate(&m->st_c7[b][r], (size_t)6 * dl[r] * (cc / 2) * E);
+            sites.push_back({1, Lb});
+            Lb *= rates[b];
+            for (int r = 0; r < 3; ++r) {
+                m->dstate(&m->st_c7[b][r], (size_t)6 * dl[r] * (cc / 2) * E);
+                sites.push_back({6 * dl[r], Lb});
+            }
             cc /= 2;
         }
         m->dstate(&m->st_cf, (size_t)6 * cc * E);
+        sites.push_back({6, Lb});
     }
+    m->batch_gap = codec_batch_gap(sites.data(), (int)sites.size());
+    m->batch_nmax = codec_batch_max_segments(m->max_frames, m->batch_gap);
+    m->d_table = m->dalloc(codec_batch_layout(m->batch_nmax, m->max_frames, (int)m->st_all.size()).bytes);
     {
         auto& c0 = m->sctx[0];
         for (auto& pb : m->st_all) c0.bufs.push_back(pb.first);
@@ -636,6 +654,8 @@ template <typename T> struct CRun {
     explicit CRun(fm_codec* mm) : m(mm), s(mm->stream) {}
     int rope_pos0_ = 0, rope_nqk_ = 0, rope_hd_ = 0;  // CE_ROPE operands of the next gemm()
     const void* norm_w_ = nullptr;                     // CE_NORM: the norm weight of the next gemm()
+    const SegTable* sb_ = nullptr;                     // batched pass: the segment table (else one stream)
+    int span_ = 0;                                     // frames of the pass (site rows per frame = L / span_)
 
     // out = res + gamma * (W x) (the transformer's residual linears), then xn = RMSNorm(out, nw) --
     // in the split-K epilogue when the layer splits K (fm_tune codec_norm), else a rmsnorm launch
@@ -814,19 +834,39 @@ template <typename T> struct CRun {
     }
 
     // streamed chunk: a causal reader's carried rows -> the prefix of its input buffer, and back
-    void site_in(bool on, const void* base, int width, int rows, void* st) {
+    // (batched pass: every segment's carried rows in one launch, into the rows in front of the segment
+    // and back from the rows that end with it; the site is the state slot's index in the table)
+    int site_of(void* const* slot) const {
+        for (size_t i = 0; i < m->st_slots.size(); ++i)
+            if (m->st_slots[i] == slot) return (int)i;
+        FMCHECK(false, "codec: not a stream state slot");
+        return -1;
+    }
+    void site_seg(const void* base, int width, int rows, int L, void* const* slot, int dir) {
+        FMCHECK(span_ > 0 && L % span_ == 0 && rows <= m->batch_gap * (L / span_) && rows <= CODEC_HALO,
+                "codec batch: a site's carried rows do not fit the gap");
+        launch_seg_rows(s, *sb_, site_of(slot), (void*)base, width * (int)sizeof(T), rows, L / span_, dir);
+    }
+    void site_in(bool on, const void* base, int width, int rows, int L, void** slot) {
         if (!on || rows <= 0) return;
+        if (sb_) return site_seg(base, width, rows, L, slot, 0);
+        void* st = *slot;
         const size_t b = (size_t)rows * width * sizeof(T);
         HIPCHK(hipMemcpyAsync((char*)base - b, st, b, hipMemcpyDeviceToDevice, s));
     }
-    void site_out(bool on, const void* base, int width, int rows, int L, void* st) {
+    void site_out(bool on, const void* base, int width, int rows, int L, void** slot) {
         if (!on || rows <= 0) return;
+        if (sb_) return site_seg(base, width, rows, L, slot, 1);
+        void* st = *slot;
         const size_t b = (size_t)rows * width * sizeof(T);
         HIPCHK(hipMemcpyAsync(st, (const char*)base + ((ptrdiff_t)L - rows) * width * (ptrdiff_t)sizeof(T), b,
                               hipMemcpyDeviceToDevice, s));
     }
 
-    void decode(int Tn, bool stream = false) {
+    // sb: the batched pass over the table's segments (Tn their span; stream is set), else one sequence
+    void decode(int Tn, bool stream = false, const SegTable* sb = nullptr) {
+        sb_ = sb;
+        span_ = Tn;
         const fm_codec_config& c = m->c;
         const int D = c.latent, H = c.t_heads, hd = c.t_head_dim, I = c.t_inter;
         const int W1 = c.window - 1, pos0 = stream ? m->spos : 0, npre = stream ? std::min(m->spos, W1) : 0;
@@ -838,6 +878,20 @@ template <typename T> struct CRun {
             launch_rmsnorm<T>(s, (const T*)m->z, D, (const T*)m->tl[0].an, D, c.norm_eps, (T*)m->xn, D, Tn);
         for (int l = 0; l < c.t_layers; ++l) {
             const TLayer& L = m->tl[l];
+            if (sb) {
+                // per-segment positions and carried keys / values: the projection, then the segment forms
+                // of RoPE (bit-identical to the epilogue form), attention and the state refresh
+                gemm(L.wqkv, m->xn, D, Tn, Tn, m->qkv, 3 * H * hd, CE_STORE);
+                launch_rope_qk_seg<T>(s, (T*)m->qkv, H, hd, m->rope, *sb);
+                const int site = site_of(&m->st_kv[l]);
+                launch_window_attn_seg<T>(s, (const T*)m->qkv, H, hd, c.window, (T*)m->att, *sb, site);
+                if (W1 > 0) launch_kv_roll_seg<T>(s, (const T*)m->qkv, H, hd, c.window, *sb, site);
+                res_linear_norm(L.wo, m->att, H * hd, Tn, m->z, D, L.ag, L.fn, m->xn);
+                ffn13(L, m->xn, D, Tn, I, m->g1, m->g3);
+                res_linear_norm(L.w2, m->g3, I, Tn, m->z, D, L.fg, l + 1 < c.t_layers ? m->tl[l + 1].an : m->tnorm,
+                                m->xn);
+                continue;
+            }
             if (fm_tuning().codec_rope && fm_tuning().conv_splitk && L.wqkv.ks > 1 && hd % 8 == 0) {
                 // RoPE in the projection's split-K epilogue (rope_qk_kernel's arithmetic)
                 rope_pos0_ = pos0;
@@ -848,9 +902,9 @@ template <typename T> struct CRun {
                 gemm(L.wqkv, m->xn, D, Tn, Tn, m->qkv, 3 * H * hd, CE_STORE);
                 launch_rope_qk<T>(s, (T*)m->qkv, Tn, H, hd, m->rope, pos0);
             }
-            site_in(stream, m->qkv, 3 * H * hd, W1, m->st_kv[l]);
+            site_in(stream, m->qkv, 3 * H * hd, W1, Tn, &m->st_kv[l]);
             launch_window_attn<T>(s, (const T*)m->qkv, Tn, H, hd, c.window, (T*)m->att, npre);
-            site_out(stream, m->qkv, 3 * H * hd, W1, Tn, m->st_kv[l]);
+            site_out(stream, m->qkv, 3 * H * hd, W1, Tn, &m->st_kv[l]);
             res_linear_norm(L.wo, m->att, H * hd, Tn, m->z, D, L.ag, L.fn, m->xn);
             ffn13(L, m->xn, D, Tn, I, m->g1, m->g3);
             res_linear_norm(L.w2, m->g3, I, Tn, m->z, D, L.fg, l + 1 < c.t_layers ? m->tl[l + 1].an : m->tnorm,
@@ -866,19 +920,19 @@ template <typename T> struct CRun {
             void* uo = ubuf[u];
             gemm(m->up_ct[u], xin, D, L, L, uo, D, CE_STORE);
             L *= 2;
-            site_in(stream, uo, D, 6, m->st_dw[u]);
+            site_in(stream, uo, D, 6, L, &m->st_dw[u]);
             launch_dwconv_ln<T>(s, (const T*)uo, L, D, (const T*)m->up_dw[u], (const T*)m->up_db[u],
                                 (const T*)m->up_lw[u], (const T*)m->up_lb[u], (T*)m->hh, stream ? -6 : 0);
-            site_out(stream, uo, D, 6, L, m->st_dw[u]);
+            site_out(stream, uo, D, 6, L, &m->st_dw[u]);
             gemm(m->up_pw1[u], m->hh, D, L, L, m->gb, 4 * D, CE_STORE | CE_GELU);
             gemm(m->up_pw2[u], m->gb, 4 * D, L, L, uo, D, CE_STORE | CE_RES | CE_GAMMA, uo, D, m->up_gm[u]);
             xin = uo;
         }
         // decoder
         const int ch = c.decoder_dim;
-        site_in(stream, xin, D, 6, m->st_c0);
+        site_in(stream, xin, D, 6, L, &m->st_c0);
         gemm(m->conv0, xin, D, L, L, nullptr, 0, 0, nullptr, 0, nullptr, m->blk[0].alpha, m->A, ch, stream ? -6 : 0);
-        site_out(stream, xin, D, 6, L, m->st_c0);
+        site_out(stream, xin, D, 6, L, &m->st_c0);
         void* in = m->A;
         void* alt = m->B;
         void* spare = m->Cb;  // fused units: alt -> spare, then the two swap
@@ -887,19 +941,19 @@ template <typename T> struct CRun {
         for (int b = 0; b < 4; ++b) {
             const DBlock& Bk = m->blk[b];
             const int cout = cin / 2, st_ = rates[b];
-            site_in(stream, in, cin, 1, m->st_ct[b]);
+            site_in(stream, in, cin, 1, L, &m->st_ct[b]);
             gemm(Bk.ct, in, cin, L, L, m->xb, cout, CE_STORE, nullptr, 0, nullptr, Bk.ru[0].a0, alt, cout,
                  stream ? -1 : 0);
-            site_out(stream, in, cin, 1, L, m->st_ct[b]);
+            site_out(stream, in, cin, 1, L, &m->st_ct[b]);
             L *= st_;
             const int dl[3] = {1, 3, 9};
             for (int r = 0; r < 3; ++r) {
                 const RU& R = Bk.ru[r];
                 const int hr = 6 * dl[r];
                 const void* an = r < 2 ? Bk.ru[r + 1].a0 : (b < 3 ? m->blk[b + 1].alpha : m->falpha);
-                site_in(stream, alt, cout, hr, m->st_c7[b][r]);
+                site_in(stream, alt, cout, hr, L, &m->st_c7[b][r]);
                 if (resunit(R, dl[r], alt, L, stream ? -hr : 0, r < 2, an, spare, cout, m->xb)) {
-                    site_out(stream, alt, cout, hr, L, m->st_c7[b][r]);
+                    site_out(stream, alt, cout, hr, L, &m->st_c7[b][r]);
                     std::swap(alt, spare);
                     continue;
                 }
@@ -907,17 +961,17 @@ template <typename T> struct CRun {
                 // the pair, alt may be m->Cb itself)
                 FMCHECK(spare != alt && spare != in, "codec: ResidualUnit scratch aliases its input");
                 gemm(R.c7, alt, cout, L, L, nullptr, 0, 0, nullptr, 0, nullptr, R.a2, spare, cout, stream ? -hr : 0);
-                site_out(stream, alt, cout, hr, L, m->st_c7[b][r]);
+                site_out(stream, alt, cout, hr, L, &m->st_c7[b][r]);
                 gemm(R.c1, spare, cout, L, L, m->xb, cout, (r < 2 ? CE_STORE : 0) | CE_RES, m->xb, cout, nullptr,
                      an, alt, cout);
             }
             std::swap(in, alt);
             cin = cout;
         }
-        site_in(stream, in, cin, 6, m->st_cf);
+        site_in(stream, in, cin, 6, L, &m->st_cf);
         gemm(m->convf, in, cin, L, L, m->wave, 1, CE_STORE | CE_TANH | CE_F32OUT, nullptr, 0, nullptr, nullptr,
              nullptr, 0, stream ? -6 : 0);
-        site_out(stream, in, cin, 6, L, m->st_cf);
+        site_out(stream, in, cin, 6, L, &m->st_cf);
     }
 };
 
@@ -1121,6 +1175,79 @@ int fm_codec_stream_decode(fm_codec* m, int sid, const int32_t* codes, int T, fl
         FMCHECK(m->spos + (int64_t)T <= CODEC_STREAM_MAX, "stream longer than the RoPE table: reset it");
         codec_decode(m, codes, T, pcm, true);
         m->spos += T;
+    });
+}
+
+int fm_codec_stream_batch_gap(fm_codec* m, int* gap_frames) {
+    return fm_guard([&] {
+        FMCHECK(m && gap_frames, "null argument");
+        HIPCHK(hipSetDevice(m->device));
+        finalize(m);
+        *gap_frames = m->batch_gap;
+    });
+}
+
+int fm_codec_stream_decode_batch(fm_codec* m, int n, const int32_t* sids, const int32_t* codes, const int32_t* T,
+                                 float* pcm) {
+    return fm_guard([&] {
+        FMCHECK(m, "null handle");
+        HIPCHK(hipSetDevice(m->device));
+        finalize(m);
+        m->sctx[m->active_sid].spos = m->spos;  // (the active context's position lives in the handle)
+        const int nq1 = m->c.n_codebooks + 1, gap = m->batch_gap, nsites = (int)m->st_all.size();
+        // every check before the first copy or launch: a refused batch leaves the contexts as they were
+        const char* bad = codec_batch_check(n, sids, codes, T, pcm, nq1, gap, m->max_frames, CODEC_STREAM_MAX, [&](int sid) {
+            auto it = m->sctx.find(sid);
+            return it == m->sctx.end() ? -1 : it->second.spos;
+        });
+        FMCHECK(!bad, bad ? bad : "");
+        std::vector<int32_t> pos(n);
+        std::vector<void* const*> bufs(n);
+        for (int i = 0; i < n; ++i) {
+            const fm_codec::StreamCtx& cx = m->sctx.find(sids[i])->second;
+            pos[i] = cx.spos;
+            bufs[i] = cx.bufs.data();
+        }
+        CodecBatchLayout lay;
+        const int span = codec_batch_fill(m->h_table, lay, n, T, pos.data(), gap, m->c.window - 1, nsites, bufs.data());
+        codec_batch_codes(m->h_codes, n, T, codes, nq1, gap);
+        HIPCHK(hipMemcpyAsync(m->d_codes, m->h_codes.data(), m->h_codes.size() * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->d_table, m->h_table.data(), lay.bytes, hipMemcpyHostToDevice, m->stream));
+        SegTable tb{};
+        tb.seg = (const CodecSeg*)((char*)m->d_table + lay.seg_off);
+        tb.rowseg = (const int32_t*)((char*)m->d_table + lay.rowseg_off);
+        tb.st = (void* const*)((char*)m->d_table + lay.st_off);
+        tb.n = n;
+        tb.span = span;
+        tb.nsites = nsites;
+        m->flops = 0;
+        HIPCHK(hipEventRecord(m->e0, m->stream));
+        if (m->prec == FM_PREC_BF16) {
+            CRun<bf16_t> r(m);
+            r.decode(span, true, &tb);
+        } else {
+            CRun<float> r(m);
+            r.decode(span, true, &tb);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(m->e1, m->stream));
+        m->h_wave.resize((size_t)span * 2048);
+        HIPCHK(hipMemcpyAsync(m->h_wave.data(), m->wave, m->h_wave.size() * 4, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipStreamSynchronize(m->stream));
+        size_t o = 0;
+        int off = 0;
+        for (int i = 0; i < n; ++i) {
+            memcpy(pcm + o, m->h_wave.data() + (size_t)off * 2048, (size_t)T[i] * 2048 * 4);
+            o += (size_t)T[i] * 2048;
+            off += T[i] + gap;
+            m->sctx.find(sids[i])->second.spos += T[i];
+        }
+        m->spos = m->sctx[m->active_sid].spos;
+        float ms = 0;
+        HIPCHK(hipEventElapsedTime(&ms, m->e0, m->e1));
+        m->last_ms = ms;
+        m->total_ms += ms;
+        m->total_flops += m->flops;
     });
 }
 

@@ -1,5 +1,6 @@
 // fm_codec.h -- kernel argument blocks of the modded-DAC decode path (fm_codec_kernels.hip).
 #pragma once
+#include "fm_codec_batch.h"
 #include "fm_kernels.h"
 
 // epilogue flags of conv_gemm_kernel (combined bitwise)
@@ -144,6 +145,27 @@ void launch_rope_qk(hipStream_t s, T* qkv, int Tn, int H, int hd, const float* t
 // npre: rows [-npre, 0) of qkv hold the carried (post-RoPE) keys / values of earlier frames
 template <typename T>
 void launch_window_attn(hipStream_t s, const T* qkv, int Tn, int H, int hd, int window, T* out, int npre = 0);
+// ---- batched streamed decode: one launch over the segments of several stream contexts ----------
+// The device descriptor table of a pass (fm_codec_batch.h): seg[n], rowseg[span] (segment of a frame,
+// -1 in a gap) and st[n][nsites], every segment's state buffers in site order.
+struct SegTable {
+    const CodecSeg* seg;
+    const int32_t* rowseg;
+    void* const* st;
+    int n, span, nsites;
+};
+// carried rows of conv site `site` for all segments: dir 0 the state buffers -> the `rows` rows in front
+// of each segment of `base` (rows of row_bytes bytes, `scale` rows per frame), dir 1 the last `rows`
+// rows ending with each segment's last row -> the state buffers
+void launch_seg_rows(hipStream_t s, const SegTable& tb, int site, void* base, int row_bytes, int rows, int scale, int dir);
+// launch_rope_qk on the span's rows, each at its segment's position (pos0 + row within the segment)
+template <typename T> void launch_rope_qk_seg(hipStream_t s, T* qkv, int H, int hd, const float* tab, const SegTable& tb);
+// launch_window_attn on every segment's rows of qkv [span][3 H hd]; the keys / values in front of a
+// segment are the window - 1 rows of its st[.][site] (the last npre of them in use); out [span][H hd]
+template <typename T>
+void launch_window_attn_seg(hipStream_t s, const T* qkv, int H, int hd, int window, T* out, const SegTable& tb, int site);
+// st[.][site] <- its last window - 1 rows once the segment's T rows of qkv are appended, in place
+template <typename T> void launch_kv_roll_seg(hipStream_t s, const T* qkv, int H, int hd, int window, const SegTable& tb, int site);
 void launch_wn_fold(hipStream_t s, const float* g, const float* v, int rows, int per, float* w);
 template <typename T>
 void launch_conv_weight(hipStream_t s, const float* w, int kind, int Ci, int Co, int k, int st_, T* out);

@@ -485,6 +485,140 @@ __global__ __launch_bounds__(64) void window_attn_kernel(const T* __restrict__ q
     }
 }
 
+// ---- batched streamed decode (fm_codec_stream_decode_batch; layout in fm_codec_batch.h) ----------
+// One launch covers every segment of the pass; `seg`, `rowseg` and `st` are the device table.
+
+// Carried rows of one conv site, all segments at once.  dir 0 (gather): the site's state buffer ->
+// the `rows` rows in front of the segment; dir 1 (scatter): the last `rows` rows that end with the
+// segment's last row (carried rows, then its own: one contiguous range) -> the state buffer.
+// grid (x, n), 16-byte chunks; row_bytes a multiple of 16.
+__global__ __launch_bounds__(256) void seg_rows_kernel(const CodecSeg* __restrict__ seg, void* const* __restrict__ st,
+                                                       int nsites, int site, char* __restrict__ base, int row_bytes,
+                                                       int rows, int scale, int dir) {
+    const CodecSeg sg = seg[blockIdx.y];
+    char* state = (char*)st[(size_t)blockIdx.y * nsites + site];
+    const ptrdiff_t r0 = (ptrdiff_t)(dir ? sg.off + sg.T : sg.off) * scale - rows;
+    char* buf = base + r0 * row_bytes;
+    const uint4* src = (const uint4*)(dir ? buf : state);
+    uint4* dst = (uint4*)(dir ? state : buf);
+    const int n16 = rows * (row_bytes / 16);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) dst[i] = src[i];
+}
+
+// rope_qk_kernel with the position of each row taken from its segment (gap rows left alone)
+template <typename T>
+__global__ void rope_qk_seg_kernel(T* __restrict__ qkv, int H, int hd, const float* __restrict__ tab,
+                                   const CodecSeg* __restrict__ seg, const int* __restrict__ rowseg) {
+    const int t = blockIdx.x, si = rowseg[t];
+    if (si < 0) return;
+    const int tp = t - seg[si].off + seg[si].pos0;
+    const int half = hd >> 1;
+    for (int idx = threadIdx.x; idx < 2 * H * half; idx += blockDim.x) {
+        const int head = idx / half, p = idx - head * half;
+        T* v = qkv + (size_t)t * 3 * H * hd + (size_t)head * hd;
+        const float x0 = ld(v, 2 * p), x1 = ld(v, 2 * p + 1);
+        const float c = tab[((size_t)tp * half + p) * 2], s = tab[((size_t)tp * half + p) * 2 + 1];
+        const float y0 = x0 * c - x1 * s;
+        const float y1 = x1 * c + x0 * s;
+        st(v, 2 * p, y0);
+        st(v, 2 * p + 1, y1);
+    }
+}
+
+// window_attn_kernel over the rows of every segment: grid (span, H), one wave.  Row t of segment s
+// is the segment's row tl = t - off; its keys / values j in [j0, tl] (segment-relative, j0 as in
+// window_attn_kernel with the segment's npre) come from the pass's qkv rows for j >= 0 and from the
+// stream's carried rows, state row (window - 1) + j, for j < 0.  Lanes, scores and the order of
+// both sums are window_attn_kernel's, so a row's output is bit-identical to the single-stream
+// pass with the state copied in front.  Gap rows store zeros.
+template <typename T, int NS>
+__global__ __launch_bounds__(64) void window_attn_seg_kernel(const T* __restrict__ qkv, int H, int hd, int window,
+                                                             T* __restrict__ out, const CodecSeg* __restrict__ seg,
+                                                             const int* __restrict__ rowseg, void* const* __restrict__ stp,
+                                                             int nsites, int site) {
+    __shared__ float qs[64];
+    __shared__ float ps[64 * NS];
+    const int lane = threadIdx.x;
+    const int t = blockIdx.x, h = blockIdx.y;
+    const int si = rowseg[t];
+    if (si < 0) {
+        if (lane < hd) st(out, (size_t)t * H * hd + (size_t)h * hd + lane, 0.f);
+        return;
+    }
+    const CodecSeg sg = seg[si];
+    const size_t ld3 = (size_t)3 * H * hd;
+    const T* cur = qkv + (size_t)sg.off * ld3;                                          // segment row 0
+    const T* old = (const T*)stp[(size_t)si * nsites + site] + (size_t)(window - 1) * ld3;  // row "0" of the carried rows
+    const int tl = t - sg.off;
+    const T* q = cur + (size_t)tl * ld3 + (size_t)h * hd;
+    if (lane < hd) qs[lane] = ld(q, lane);
+    __syncthreads();
+    int j0 = tl - window + 1;
+    if (j0 < -sg.npre) j0 = -sg.npre;
+    const int nj = tl - j0 + 1;
+    const float scale = 1.0f / sqrtf((float)hd);
+    float sc[NS];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        sc[i] = -INFINITY;
+        const int jj = lane + 64 * i;
+        if (jj < nj) {
+            const int j = j0 + jj;
+            const T* k = (j < 0 ? old : cur) + (ptrdiff_t)j * (ptrdiff_t)ld3 + (size_t)(H + h) * hd;
+            float dot = 0.f;
+            for (int e = 0; e < hd; e += 8) {
+                float kv[8];
+                load8(k + e, kv);
+#pragma unroll
+                for (int u = 0; u < 8; ++u) dot += qs[e + u] * kv[u];
+            }
+            sc[i] = dot * scale;
+        }
+        mx = fmaxf(mx, sc[i]);
+    }
+    const float m = wave_max(mx);
+    float psum = 0.f;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const float p = lane + 64 * i < nj ? expf(sc[i] - m) : 0.f;
+        ps[lane + 64 * i] = p;
+        psum += p;
+    }
+    const float l = wave_sum(psum);
+    __syncthreads();
+    if (lane < hd) {
+        float o = 0.f;
+        for (int jj = 0; jj < nj; ++jj) {
+            const int j = j0 + jj;
+            o += ps[jj] * ld((j < 0 ? old : cur) + (ptrdiff_t)j * (ptrdiff_t)ld3 + (size_t)(2 * H + h) * hd, lane);
+        }
+        st(out, (size_t)t * H * hd + (size_t)h * hd + lane, o / l);
+    }
+}
+
+// The carried key / value rows after the pass: new[i] = i + T < W1 ? old[i + T] : fresh[i + T - W1]
+// for the W1 = window - 1 state rows of every segment, in place.  A block owns 8 16-byte columns of
+// one segment's state for ALL its rows (thread = (row, column), W1 <= 128): every thread loads its
+// source, the block meets at a barrier, then every thread stores -- no row is read after it was
+// overwritten, and no other block touches these columns.  grid (ceil(chunks / 8), n), block (8, 128).
+__global__ __launch_bounds__(1024) void kv_roll_seg_kernel(const char* __restrict__ qkv, int row_bytes, int w1,
+                                                           const CodecSeg* __restrict__ seg, void* const* __restrict__ stp,
+                                                           int nsites, int site) {
+    const CodecSeg sg = seg[blockIdx.y];
+    char* state = (char*)stp[(size_t)blockIdx.y * nsites + site];
+    const int col = blockIdx.x * 8 + threadIdx.x, i = threadIdx.y;
+    const bool on = i < w1 && col < row_bytes / 16;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (on) {
+        const int j = i + sg.T;
+        const char* src = j < w1 ? state + (size_t)j * row_bytes : qkv + ((size_t)sg.off + (j - w1)) * row_bytes;
+        v = ((const uint4*)src)[col];
+    }
+    __syncthreads();
+    if (on) ((uint4*)(state + (size_t)i * row_bytes))[col] = v;
+}
+
 // mono fp32 samples -> the encoder's [n_pad][8] input (channel 0 live, right pad = causal zeros of
 // DAC.encode's pad to a multiple of frame_length, modded_dac.py:906-909)
 template <typename T>
@@ -1321,6 +1455,42 @@ void launch_window_attn(hipStream_t s, const T* qkv, int Tn, int H, int hd, int 
     else
         window_attn_kernel<T, 8><<<dim3(Tn, H), 64, 0, s>>>(qkv, Tn, H, hd, window, out, npre);
 }
+static void seg_table_check(const SegTable& tb, int site) {
+    FMCHECK(tb.seg && tb.rowseg && tb.st && tb.n >= 1 && tb.span >= tb.n && tb.nsites >= 1 && site >= 0 && site < tb.nsites,
+            "segment table: n >= 1 segments over span >= n frames, site inside the table");
+}
+void launch_seg_rows(hipStream_t s, const SegTable& tb, int site, void* base, int row_bytes, int rows, int scale, int dir) {
+    seg_table_check(tb, site);
+    FMCHECK(base && ((uintptr_t)base & 15) == 0 && row_bytes >= 16 && row_bytes % 16 == 0 && rows >= 1 && scale >= 1 &&
+                (dir == 0 || dir == 1),
+            "segment rows: a 16-byte aligned buffer, rows of whole 16-byte chunks, rows and scale >= 1");
+    const int n16 = rows * (row_bytes / 16);
+    seg_rows_kernel<<<dim3(std::min(FM_CEIL(n16, 256), 64), tb.n), 256, 0, s>>>(tb.seg, tb.st, tb.nsites, site, (char*)base,
+                                                                               row_bytes, rows, scale, dir);
+}
+template <typename T>
+void launch_rope_qk_seg(hipStream_t s, T* qkv, int H, int hd, const float* tab, const SegTable& tb) {
+    seg_table_check(tb, 0);
+    FMCHECK(hd >= 2 && hd % 2 == 0, "rope: an even head_dim");
+    rope_qk_seg_kernel<T><<<tb.span, 256, 0, s>>>(qkv, H, hd, tab, tb.seg, tb.rowseg);
+}
+template <typename T>
+void launch_window_attn_seg(hipStream_t s, const T* qkv, int H, int hd, int window, T* out, const SegTable& tb, int site) {
+    seg_table_check(tb, site);
+    FMCHECK(hd >= 8 && hd <= 64 && hd % 8 == 0 && window >= 2 && window <= 128,
+            "segment window attention: head_dim a multiple of 8 up to 64, 2 <= window <= 128");
+    window_attn_seg_kernel<T, 2><<<dim3(tb.span, H), 64, 0, s>>>(qkv, H, hd, window, out, tb.seg, tb.rowseg, tb.st, tb.nsites,
+                                                                site);
+}
+template <typename T>
+void launch_kv_roll_seg(hipStream_t s, const T* qkv, int H, int hd, int window, const SegTable& tb, int site) {
+    seg_table_check(tb, site);
+    const int row_bytes = 3 * H * hd * (int)sizeof(T);
+    FMCHECK(window >= 2 && window <= 129 && row_bytes % 16 == 0 && ((uintptr_t)qkv & 15) == 0,
+            "segment K/V roll: 2 <= window <= 129, qkv rows of whole 16-byte chunks");
+    kv_roll_seg_kernel<<<dim3(FM_CEIL(row_bytes / 16, 8), tb.n), dim3(8, 128), 0, s>>>((const char*)qkv, row_bytes, window - 1,
+                                                                                      tb.seg, tb.st, tb.nsites, site);
+}
 template <typename T>
 void launch_audio8(hipStream_t s, const float* a, int64_t n, int64_t npad, T* y) {
     audio8_kernel<T><<<(unsigned)std::min<int64_t>((npad * 8 + 255) / 256, 8192), 256, 0, s>>>(a, n, npad, y);
@@ -1352,6 +1522,9 @@ void launch_conv_weight(hipStream_t s, const float* w, int kind, int Ci, int Co,
                                       const T*, T*, int);                                            \
     template void launch_rope_qk<T>(hipStream_t, T*, int, int, int, const float*, int);              \
     template void launch_window_attn<T>(hipStream_t, const T*, int, int, int, int, T*, int);         \
+    template void launch_rope_qk_seg<T>(hipStream_t, T*, int, int, const float*, const SegTable&);   \
+    template void launch_window_attn_seg<T>(hipStream_t, const T*, int, int, int, T*, const SegTable&, int); \
+    template void launch_kv_roll_seg<T>(hipStream_t, const T*, int, int, int, const SegTable&, int); \
     template void launch_snake<T>(hipStream_t, const T*, int, size_t, const T*, T*);                 \
     template void launch_snake_inv<T>(hipStream_t, const T*, int64_t, float*);                       \
     template void launch_audio8<T>(hipStream_t, const float*, int64_t, int64_t, T*);                 \

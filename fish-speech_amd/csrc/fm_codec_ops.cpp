@@ -208,6 +208,40 @@ void codec_window_attn_t(hipStream_t s, const float* qkv, int Tn, int H, int hd,
     o.get(s);
 }
 
+// the batched pass's attention and K/V state refresh on a table built like the model's (fm_codec_batch.h)
+template <typename T>
+void codec_window_attn_seg_t(hipStream_t s, int n, const int32_t* Tn, const int32_t* npre, int gap, const float* qkv, int H,
+                             int hd, int window, float* state, int state_rows, float* out, int out_rows) {
+    DevBufs b(s);
+    const size_t ld3 = (size_t)3 * H * hd;
+    const int span = (int)codec_batch_span(n, Tn, gap);
+    T* q = b.upload<T>(qkv, (size_t)span * ld3);
+    InOut<T> o(b, out, (size_t)out_rows * H * hd);
+    std::vector<InOut<T>> st;
+    std::vector<void*> ptr(n);
+    std::vector<void* const*> bufs(n);
+    st.reserve(n);
+    for (int i = 0; i < n; ++i) {
+        st.emplace_back(b, state + (size_t)i * state_rows * ld3, (size_t)state_rows * ld3);
+        ptr[i] = st[i].d;
+        bufs[i] = &ptr[i];
+    }
+    // (the table's pos0 only feeds npre = min(pos0, window - 1): the caller's npre stands in for it)
+    std::vector<uint8_t> blob;
+    CodecBatchLayout lay;
+    codec_batch_fill(blob, lay, n, Tn, npre, gap, window - 1, 1, bufs.data());
+    char* d = (char*)b.alloc(lay.bytes);
+    b.put(d, blob.data(), lay.bytes);
+    SegTable tb{(const CodecSeg*)(d + lay.seg_off), (const int32_t*)(d + lay.rowseg_off), (void* const*)(d + lay.st_off), n,
+                span, 1};
+    launch_window_attn_seg<T>(s, q, H, hd, window, o.d, tb, 0);
+    HIPCHK(hipGetLastError());
+    launch_kv_roll_seg<T>(s, q, H, hd, window, tb, 0);
+    HIPCHK(hipGetLastError());
+    o.get(s);
+    for (int i = 0; i < n; ++i) st[i].get(s);
+}
+
 template <typename T>
 void codec_rope_qk_t(hipStream_t s, float* qkv, int rows, int Tn, int H, int hd, float base, int pos0, int reps,
                      int* changed) {
@@ -346,6 +380,27 @@ int fm_op_codec_window_attn(int device, int precision, const float* qkv, int Tn,
         StreamGuard g(device);
         if (precision == FM_PREC_BF16) codec_window_attn_t<bf16_t>(g.s, qkv, Tn, H, hd, window, npre, out, out_rows, reps, changed);
         else codec_window_attn_t<float>(g.s, qkv, Tn, H, hd, window, npre, out, out_rows, reps, changed);
+    });
+}
+
+int fm_op_codec_window_attn_seg(int device, int precision, int n, const int32_t* T, const int32_t* npre, int gap,
+                                const float* qkv, int H, int hd, int window, float* state, int state_rows, float* out,
+                                int out_rows) {
+    return fm_guard([&] {
+        FMCHECK(T && npre && qkv && state && out, "null argument");
+        FMCHECK(n >= 1 && n <= 1024 && gap >= 0 && gap <= 64 && H >= 1 && H <= 64 && hd >= 1 && hd <= 1024 && window >= 2 &&
+                    window <= 129 && state_rows >= window - 1 && state_rows <= 4096,
+                "1 <= n <= 1024, 0 <= gap <= 64, 1 <= H <= 64, 2 <= window <= 129, window - 1 <= state rows <= 4096");
+        for (int i = 0; i < n; ++i)
+            FMCHECK(T[i] >= 1 && T[i] <= (1 << 16) && npre[i] >= 0 && npre[i] <= window - 1,
+                    "1 <= T[i] <= 65536, 0 <= npre[i] <= window - 1");
+        const int64_t span = codec_batch_span(n, T, gap);
+        FMCHECK(span <= (1 << 20) && out_rows >= span && out_rows <= (1 << 21), "span <= 2^20 rows, out rows >= span");
+        StreamGuard g(device);
+        if (precision == FM_PREC_BF16)
+            codec_window_attn_seg_t<bf16_t>(g.s, n, T, npre, gap, qkv, H, hd, window, state, state_rows, out, out_rows);
+        else
+            codec_window_attn_seg_t<float>(g.s, n, T, npre, gap, qkv, H, hd, window, state, state_rows, out, out_rows);
     });
 }
 

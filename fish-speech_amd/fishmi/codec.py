@@ -162,6 +162,61 @@ class FishMICodec:
         native.check(native.lib().fm_codec_stream_open(self.h, ctypes.byref(sid)))
         return CodecStream(self, sid.value)
 
+    @property
+    def batch_gap(self) -> int:
+        """Frames a batched pass puts between two segments (fm_codec_stream_batch_gap): n chunks of
+        T[i] frames fit one pass when sum(T) + batch_gap * (n - 1) <= max_frames."""
+        g = getattr(self, "_batch_gap", None)
+        if g is None:
+            v = ctypes.c_int32(0)
+            native.check(native.lib().fm_codec_stream_batch_gap(self.h, ctypes.byref(v)))
+            g = self._batch_gap = v.value
+        return g
+
+    def _decode_one(self, sid, cd):
+        out = np.zeros(cd.shape[1] * self.frame_length, np.float32)
+        native.check(native.lib().fm_codec_stream_decode(self.h, sid, native.i32p(cd), cd.shape[1], native.f32p(out)))
+        return out
+
+    def _decode_batch(self, sids, chunks):
+        T = np.array([c.shape[1] for c in chunks], np.int32)
+        codes = np.concatenate([c.reshape(-1) for c in chunks])
+        pcm = np.zeros(int(T.sum()) * self.frame_length, np.float32)
+        native.check(native.lib().fm_codec_stream_decode_batch(
+            self.h, len(chunks), native.i32p(np.array(sids, np.int32)), native.i32p(codes), native.i32p(T),
+            native.f32p(pcm)))
+        return np.split(pcm, np.cumsum(T[:-1]) * self.frame_length)
+
+    def decode_chunks(self, streams, codes_list) -> "list[np.ndarray]":
+        """The next chunk of several stream contexts in one causal pass each
+        (fm_codec_stream_decode_batch): streams[i] (a CodecStream of this codec, or None for the
+        handle's own stream) gets codes_list[i] (C, T_i) appended and result i is its PCM
+        (2048*T_i,), bit for bit what streams[i].decode_chunk gives.  The list is cut greedily, in
+        order, into as many native passes as batch_gap and max_frames require; a context that
+        appears again starts a new pass, so its chunks stay in order.  A pass left with one chunk
+        takes the single-stream call (fm_codec_stream_decode: the same state and PCM, and measured
+        faster for one segment, profiles/codec_batch.md)."""
+        assert len(streams) == len(codes_list)
+        chunks = []
+        for c in codes_list:
+            cd = np.ascontiguousarray(c, dtype=np.int32)
+            assert cd.ndim == 2 and cd.shape[0] == self.cfg.n_codebooks + 1
+            chunks.append(cd)
+        sids = [0 if s is None else s.sid for s in streams]
+        assert all(s is None or s.codec is self for s in streams)
+        out, gap, i = [], self.batch_gap, 0
+        while i < len(chunks):
+            j, span = i, 0
+            while j < len(chunks) and sids[j] not in sids[i:j]:
+                need = chunks[j].shape[1] + (gap if j > i else 0)
+                if j > i and span + need > self.max_frames:
+                    break
+                span += need
+                j += 1
+            out += self._decode_batch(sids[i:j], chunks[i:j]) if j - i > 1 else [self._decode_one(sids[i], chunks[i])]
+            i = j
+        return out
+
     def from_indices(self, indices) -> np.ndarray:
         idx = np.asarray(indices)
         if idx.ndim == 2:

@@ -26,14 +26,14 @@ ABI_SYMBOLS = [
     "fm_llm_frame_bytes", "fm_llm_profile", "fm_llm_profile_read", "fm_llm_kernel_bench", "fm_llm_use_graph", "fm_llm_debug_vec", "fm_tune", "fm_tune_get", "fm_debug_ts_read",
     "fm_llm_close", "fm_source_hash", "fm_codec_open", "fm_codec_set_tensor", "fm_codec_synth_tensor",
     "fm_codec_finalize", "fm_codec_decode", "fm_codec_stream_reset", "fm_codec_decode_chunk",
-    "fm_codec_stream_open", "fm_codec_stream_decode", "fm_codec_stream_rewind", "fm_codec_stream_close",
+    "fm_codec_stream_open", "fm_codec_stream_decode", "fm_codec_stream_decode_batch", "fm_codec_stream_batch_gap", "fm_codec_stream_rewind", "fm_codec_stream_close",
     "fm_codec_profile_read", "fm_codec_debug_read", "fm_codec_enable_encoder", "fm_codec_encode",
     "fm_codec_close", "fm_llm_force", "fm_llm_read_logits", "fm_op_rmsnorm", "fm_op_qk_rope", "fm_op_decode_attn", "fm_op_prompt_attn",
     "fm_op_embed", "fm_op_quant4", "fm_op_batched_linear_q8", "fm_op_batched_linear_q4", "fm_rope_table",
     "fm_op_linear", "fm_op_gemv", "fm_op_rowgemv", "fm_op_rowgemv_pair", "fm_op_bstream", "fm_op_finalize_norm", "fm_op_prompt_skinny", "fm_op_sample",
     "fm_llm_prefix_save", "fm_llm_prefix_load", "fm_llm_prefix_drop", "fm_llm_prefix_info", "fm_llm_prefill_batch_at",
     "fm_llm_set_quant_compact", "fm_llm_memory_info", "fm_op_linear_q", "fm_op_prompt_skinny_q", "fm_op_prompt_gemm_q",
-    "fm_op_codec_conv", "fm_op_codec_resunit", "fm_op_codec_window_attn", "fm_op_codec_rope_qk", "fm_op_codec_dwconv_ln",
+    "fm_op_codec_conv", "fm_op_codec_resunit", "fm_op_codec_window_attn", "fm_op_codec_window_attn_seg", "fm_op_codec_rope_qk", "fm_op_codec_dwconv_ln",
     "fm_op_codec_rvq_decode", "fm_op_codec_snake", "fm_op_codec_silu_mul", "fm_op_codec_wn_fold", "fm_op_codec_vq_encode",
     "fm_op_decode_attn_ex", "fm_op_prompt_attn_ex", "fm_op_qk_rope_cache", "fm_op_fast_attn", "fm_op_fattn_wo",
     "fm_op_slow_attn_wo", "fm_op_slow_attn_wo_q",
@@ -220,6 +220,7 @@ def lib():
                                       pf32, i32, i32, pi32, pi32]
     L.fm_op_codec_window_attn.argtypes = [i32, i32, pf32, i32, i32, i32, i32, i32, pf32, i32, i32, pi32]
     L.fm_op_codec_rope_qk.argtypes = [i32, i32, pf32, i32, i32, i32, i32, f32, i32, i32, pi32]
+    L.fm_op_codec_window_attn_seg.argtypes = [i32, i32, i32, pi32, pi32, i32, pf32, i32, i32, i32, pf32, i32, pf32, i32]
     L.fm_op_codec_dwconv_ln.argtypes = [i32, i32, pf32, i32, i32, i32, pf32, pf32, pf32, pf32, pf32, i32, i32, pi32]
     L.fm_op_codec_rvq_decode.argtypes = [i32, i32, pi32, i32, i32, i32, i32, i32, pf32, pf32, pf32, pf32, i32, pf32, i32,
                                          i32, pi32]
@@ -237,6 +238,8 @@ def lib():
         L.fm_codec_decode_chunk.argtypes = [vp, pi32, i32, pf32]
         L.fm_codec_stream_open.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
         L.fm_codec_stream_decode.argtypes = [vp, i32, pi32, i32, pf32]
+        L.fm_codec_stream_decode_batch.argtypes = [vp, i32, pi32, pi32, pi32, pf32]
+        L.fm_codec_stream_batch_gap.argtypes = [vp, pi32]
         L.fm_codec_stream_rewind.argtypes = [vp, i32]
         L.fm_codec_stream_close.argtypes = [vp, i32]
         L.fm_codec_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double),

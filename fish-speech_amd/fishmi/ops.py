@@ -784,6 +784,18 @@ def codec_window_attn(qkv, Tn, H, hd, window, out, npre=0, precision="bf16", rep
                                                       int(npre), _p(_out(out)), out.shape[0], *r), reps)
 
 
+def codec_window_attn_seg(qkv, T, npre, gap, H, hd, window, state, out, precision="bf16", device=0):
+    """fm_op_codec_window_attn_seg (the batched streamed decode's attention and K/V state refresh): segment i
+    at row off[i] (off[i + 1] = off[i] + T[i] + gap) of qkv [span][3 H hd]; out [rows >= span][H hd] and state
+    [n][rows >= window - 1][3 H hd] are filled in place."""
+    qkv = _f(qkv)
+    T, npre = np.ascontiguousarray(T, np.int32), np.ascontiguousarray(npre, np.int32)
+    assert state.ndim == 3 and state.shape[0] == T.size == npre.size and qkv.shape[0] == int(T.sum()) + gap * (T.size - 1)
+    native.check(native.lib().fm_op_codec_window_attn_seg(device, _prec(precision), int(T.size), native.i32p(T),
+                                                          native.i32p(npre), int(gap), _p(qkv), int(H), int(hd), int(window),
+                                                          _p(_out(state)), state.shape[1], _p(_out(out)), out.shape[0]))
+
+
 def codec_rope_qk(qkv, Tn, H, hd, base, pos0=0, precision="bf16", reps=1, device=0):
     """fm_op_codec_rope_qk in place on qkv [rows >= Tn][3 H hd]"""
     L = native.lib()

@@ -278,6 +278,15 @@ class _VocState:
         self.ctx, self.sent, self.pcm, self.err = None, 0, [], None
 
 
+class _VocChunk:
+    """A chunk of one request in StreamVocoder's FIFO (batch > 1): unlike a plain callable it may
+    share a codec pass with the chunks of other requests queued right behind it."""
+    __slots__ = ("v", "codes")
+
+    def __init__(self, v, codes):
+        self.v, self.codes = v, codes
+
+
 class StreamVocoder:
     """serve()'s vocoder off the decode's critical path.  The codec runs on a host thread of its
     own, on the codec handle's HIP stream (separate from the LLM's), so a tick's vocoding overlaps
@@ -287,11 +296,18 @@ class StreamVocoder:
     one-shot decode's, bit for bit); `finish` vocodes the rest and returns the request's float32
     PCM.  Contexts are pooled and rewound (fm_codec_stream_rewind) instead of freed per request.
     Every codec call runs on the one thread, in submission order (the handle is single-threaded).
-    busy_s: the thread's time inside codec calls."""
+    busy_s: the thread's time inside codec calls.
+    batch > 1 (and a codec with decode_chunks): the thread takes up to `batch` chunk items that
+    stand next to each other at the head of its FIFO and belong to distinct requests, and decodes
+    them in one batched pass (FishMICodec.decode_chunks: bit for bit the per-chunk PCM).  A second
+    chunk of a request already in the batch, or anything that is not a chunk, ends the batch and
+    runs after it, so every request's items keep their submission order.  An exception fails the
+    requests of that batch only.  batch = 0 (the default): one codec call per chunk, as before."""
 
-    def __init__(self, codec, chunk: int = 128):
+    def __init__(self, codec, chunk: int = 128, batch: int = 0):
         self.codec = codec
         self.chunk = max(1, min(int(chunk), codec.max_frames))
+        self.batch = int(batch) if int(batch) > 1 and hasattr(codec, "decode_chunks") else 0
         self.fifo: "_queue.Queue" = _queue.Queue()
         self.live: Dict[int, _VocState] = {}
         self.pool: list = []   # rewound contexts (vocoder thread only)
@@ -308,11 +324,30 @@ class StreamVocoder:
         return ev, box
 
     def _run(self):
+        held = []  # the item that ended a batch: it runs next
         while True:
-            it = self.fifo.get()
+            it = held.pop() if held else self.fifo.get()
             if it is None:
                 return
             fn, ev, box = it
+            if isinstance(fn, _VocChunk):
+                group = [it]
+                while len(group) < self.batch:
+                    try:
+                        nx = self.fifo.get_nowait()
+                    except _queue.Empty:
+                        break
+                    if nx is None or not isinstance(nx[0], _VocChunk) or any(nx[0].v is g[0].v for g in group):
+                        held.append(nx)
+                        break
+                    group.append(nx)
+                t = time.perf_counter()
+                self._chunk_batch([g[0] for g in group])
+                self.busy_s += time.perf_counter() - t
+                for g in group:
+                    g[2].append(None)
+                    g[1].set()
+                continue
             t = time.perf_counter()
             try:
                 box.append(fn())
@@ -321,20 +356,48 @@ class StreamVocoder:
             self.busy_s += time.perf_counter() - t
             ev.set()
 
+    def _ctx(self, v: _VocState):
+        if v.ctx is None:
+            if self.pool:
+                v.ctx = self.pool.pop()
+            else:
+                v.ctx = self.codec.open_stream()
+                self.ctxs.append(v.ctx)
+        return v.ctx
+
     def _chunk(self, v: _VocState, codes: np.ndarray):
         if v.err is not None:
             return None
         try:
-            if v.ctx is None:
-                if self.pool:
-                    v.ctx = self.pool.pop()
-                else:
-                    v.ctx = self.codec.open_stream()
-                    self.ctxs.append(v.ctx)
-            v.pcm.append(v.ctx.decode_chunk(codes))
+            v.pcm.append(self._ctx(v).decode_chunk(codes))
         except BaseException as e:
             v.err = e
         return None
+
+    def _chunk_batch(self, items: "List[_VocChunk]"):
+        live = []
+        for it in items:
+            if it.v.err is not None:
+                continue
+            try:
+                self._ctx(it.v)
+                live.append(it)
+            except BaseException as e:
+                it.v.err = e
+        if not live:
+            return
+        try:
+            pcm = self.codec.decode_chunks([it.v.ctx for it in live], [it.codes for it in live])
+            for it, p in zip(live, pcm):
+                it.v.pcm.append(p)
+        except BaseException as e:  # the requests of this batch only
+            for it in live:
+                it.v.err = e
+
+    def _submit_chunk(self, v: _VocState, codes: np.ndarray):
+        if self.batch:
+            return self.submit(_VocChunk(v, codes))
+        return self.submit(lambda v=v, c=codes: self._chunk(v, c))
 
     def _release(self, v: _VocState):
         if v.ctx is not None:
@@ -347,7 +410,7 @@ class StreamVocoder:
         ready = len(cols) - 1  # the newest column may be the dropped last one
         while ready - v.sent >= self.chunk:
             codes = np.ascontiguousarray(np.stack(cols[v.sent: v.sent + self.chunk], 1)[1:])
-            self.submit(lambda v=v, c=codes: self._chunk(v, c))
+            self._submit_chunk(v, codes)
             v.sent += self.chunk
 
     def finish(self, slot: int, req: Request, cols: np.ndarray) -> np.ndarray:
@@ -356,7 +419,7 @@ class StreamVocoder:
         mx = self.codec.max_frames
         for t in range(v.sent, cols.shape[1], mx):
             codes = np.ascontiguousarray(cols[1:, t: t + mx])
-            self.submit(lambda v=v, c=codes: self._chunk(v, c))
+            self._submit_chunk(v, codes)
         ev, box = self.submit(lambda v=v: self._release(v))
         ev.wait()
         if v.err is not None:

@@ -303,6 +303,17 @@ def build_engine(llama_checkpoint_path: str, decoder_checkpoint_path: str, devic
     return TTS.TTSInferenceEngine(q, codec, precision, compile, reuse_prefix=reuse_prefix)
 
 
+VOCODE_BATCH = 0  # --vocode-batch of this process (main sets it)
+
+
+def stream_vocoder(codec, chunk: int = 128):
+    """The StreamVocoder of a scheduler.serve() loop in this process, with the server's
+    --vocode-batch (0, the default: one codec pass per chunk)."""
+    from .scheduler import StreamVocoder
+
+    return StreamVocoder(codec, chunk, batch=VOCODE_BATCH)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["tts"], default="tts")
@@ -326,6 +337,9 @@ def main(argv=None):
     ap.add_argument("--quant-compact", action="store_true",
                     help="weight-only (int8) checkpoints: keep only the codes on the device, no bf16 copy of the "
                          "quantised linears (bit-identical output, less device memory; refused on a bf16 checkpoint)")
+    ap.add_argument("--vocode-batch", type=int, default=0,
+                    help="streamed vocoding: chunks of up to N distinct requests share one batched codec pass "
+                         "(scheduler.StreamVocoder(codec, chunk, batch=N); bit-identical audio); 0 = one pass per chunk")
     a = ap.parse_args(argv)
     import uvicorn
 
@@ -344,15 +358,21 @@ def main(argv=None):
         log.info("--compile: decode frames are always hipGraph-captured; the flag changes nothing")
     if a.voice_cache_mb < 0:
         ap.error("--voice-cache-mb must be >= 0")
+    if a.vocode_batch < 0:
+        ap.error("--vocode-batch must be >= 0")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         if a.voice_cache_mb:
             ap.error("--voice-cache-mb: the voice prefix cache is not wired through the multi-GPU worker")
         if a.quant_compact:
             ap.error("--quant-compact is not wired through the multi-GPU worker")
+        if a.vocode_batch:
+            ap.error("--vocode-batch: the multi-GPU worker vocodes each response on its own (no StreamVocoder)")
         return _main_distributed(a)
     engine = build_engine(a.llama_checkpoint_path, a.decoder_checkpoint_path, _device_index(a.device), "bf16",
                           slots=a.slots, reuse_prefix=a.reuse_prefix, voice_cache_mb=a.voice_cache_mb,
                           quant_compact=a.quant_compact)
+    global VOCODE_BATCH
+    VOCODE_BATCH = a.vocode_batch  # every StreamVocoder this process builds (stream_vocoder)
     host, port = a.listen.rsplit(":", 1)
     uvicorn.run(create_app(engine, a.max_text_length, a.api_key), host=host, port=int(port), workers=1)
 

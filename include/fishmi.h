@@ -619,6 +619,15 @@ int fm_op_codec_window_attn(int device, int precision, const float* qkv, int Tn,
 /* launch_rope_qk in place on qkv [rows >= Tn][3 H hd], row t at position pos0 + t of fm_rope_table */
 int fm_op_codec_rope_qk(int device, int precision, float* qkv, int rows, int Tn, int H, int hd, float base, int pos0,
                         int reps, int* changed);
+/* launch_window_attn_seg, then launch_kv_roll_seg (the batched streamed decode's attention): n segments
+   laid out like a batched pass, segment i at row off[i] (off[0] = 0, off[i+1] = off[i] + T[i] + gap) of
+   qkv [span][3 H hd] (post-RoPE) and out [out_rows >= span][H hd] (gap rows are stored as zeros).  state
+   [n][state_rows >= window-1][3 H hd], in/out: segment i's carried rows (the last npre[i] in use), one
+   device buffer per segment; afterwards its first window-1 rows are the last window-1 rows of (those
+   rows, then the segment's T[i] qkv rows). */
+int fm_op_codec_window_attn_seg(int device, int precision, int n, const int32_t* T, const int32_t* npre, int gap,
+                                const float* qkv, int H, int hd, int window, float* state, int state_rows, float* out,
+                                int out_rows);
 /* launch_dwconv_ln: x [npre + L][D], depthwise weight [D][7] and bias, LayerNorm weight and bias, y [y_rows][D] */
 int fm_op_codec_dwconv_ln(int device, int precision, const float* x, int L, int D, int npre, const float* dw,
                           const float* db, const float* lw, const float* lb, float* y, int y_rows, int reps, int* changed);
@@ -681,6 +690,25 @@ int fm_codec_stream_open(fm_codec* h, int* stream_id);
 int fm_codec_stream_decode(fm_codec* h, int stream_id, const int32_t* codes, int T, float* pcm);
 int fm_codec_stream_rewind(fm_codec* h, int stream_id);
 int fm_codec_stream_close(fm_codec* h, int stream_id);
+/* One causal pass over n stream contexts of this handle.  Segment i is the next T[i] frames of
+   stream sids[i].  codes is the segments back to back, each (n_codebooks+1, T[i]) row-major.
+   pcm is the segments back to back, 2048*T[i] floats each.
+   Afterwards every context is exactly where n calls of the single-stream decode would have left it
+   (carried rows and position), and the PCM is theirs bit for bit: every row-independent kernel runs
+   once over all segments' rows (gap frames of throw-away rows between segments hold each conv's
+   carried rows), the attention reads each segment's carried keys / values from its own context.
+   sids are distinct and open.  Id 0, the handle's own stream, is allowed.
+   T[i] >= 1, and the positions may differ between segments.
+   Fails (FM_ERR_ARG) with nothing changed -- every check runs before the first launch -- on a
+   duplicate or unknown id, T[i] < 1, a negative code, a position past the RoPE table, or when the
+   segments do not fit: a batch fits when sum(T[i]) + gap*(n-1) <= max_frames (see batch_gap).
+   The launch count of profile_read counts a batched pass's GEMM / ResidualUnit launches once,
+   like a single-stream pass's. */
+int fm_codec_stream_decode_batch(fm_codec* h, int n, const int32_t* sids, const int32_t* codes,
+                                 const int32_t* T, float* pcm);
+/* Frames of separation a batched pass inserts between segments: the smallest frame count whose
+   rows, at every causal conv's level, cover the rows that conv carries (3 for the shipped config). */
+int fm_codec_stream_batch_gap(fm_codec* h, int* gap_frames);
 int fm_codec_profile_read(fm_codec* h, double* total_ms, int64_t* launches, double* flops);
 /* test hook: intermediate of the last decode as fp32, time-major (1 transformer out [T][latent],
    2 first upsample [2T][latent], 3 decoder input [4T][latent]); other stages' buffers are
