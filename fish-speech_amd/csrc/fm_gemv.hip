@@ -139,7 +139,9 @@ template <typename T> __device__ __forceinline__ void st_sc1_run(T* p, size_t i,
 // PR2 (fm_tune fast_pair: bf16 PRO_PRENORM + EPI_SWIGLU8, R == 2, whole K, ss_gran 1): the ss_gran 1 prologue at two
 // rows.  A thread holds, of EACH row, the chunks the one-row form gives it (threadIdx.x and threadIdx.x + NTH), so
 // each row's sum of squares is taken over the same values in the same order; the norm weight chunks serve both rows,
-// which keeps the preload at the one-row form's 24 registers.
+// which keeps the preload at the one-row form's 24 registers.  QM 1 (fm_tune fast_pair_q bit 0: weight-only int8, EPI_STORE
+// for wqkv and EPI_SWIGLU8 for w1 || w3): the same prologue ahead of the int8 ring; the ring, the MFMAs and the epilogue
+// are the R-row code the int8 kernel runs at any R <= 8.
 template <typename T, int PRO, int EPI, bool NT, int U, int WPB, int QM, bool CH, bool PR2 = false>
 __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, const int ks, const int nks,
                                           const ChainWait& cw) {
@@ -153,7 +155,8 @@ __device__ __forceinline__ void gemv_body(const GemvArgs<T>& a, const int bxi, c
     // row per stream (2 items per thread at R = 1), and its register budget is what lets the
     // 1216-block W1||W3 grid stay resident (5 waves per SIMD)
     constexpr int PRE_N = PRO == PRO_PRENORM ? 3 : GEMV_PRE;
-    static_assert(!PR2 || (PRO == PRO_PRENORM && EPI == EPI_SWIGLU8 && QM == 0 && !CH && sizeof(T) == 2), "two-row ss_gran 1 form");
+    static_assert(!PR2 || (PRO == PRO_PRENORM && (EPI == EPI_SWIGLU8 || (QM == 1 && EPI == EPI_STORE)) && QM <= 1 && !CH && sizeof(T) == 2),
+                  "two-row ss_gran 1 form: bf16 w1 || w3, int8 w1 || w3 and wqkv");
     using G = Frag<T>;
     constexpr int NACC = (EPI == EPI_SWIGLU) ? 2 : 1;
     constexpr int NTH = WPB * 64;
@@ -771,6 +774,14 @@ void gemv_pair_kernel(GemvArgs<bf16_t> a) {
     gemv_body<bf16_t, PRO_PRENORM, EPI_SWIGLU8, NT, U, WPB, 0, false, true>(a, blockIdx.x, 0, 1, ChainWait{});
 }
 
+// ... on weight-only int8 codes (fm_tune fast_pair_q): w1 || w3 (EPI_SWIGLU8) and wqkv (EPI_STORE), the int8 kernel's
+// configuration (non-temporal, 4 waves, fm_tune q_u units in flight)
+template <int EPI, int U>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(gemv_wpe(PRO_PRENORM, EPI))))
+void gemv_pair_q8_kernel(GemvArgs<bf16_t> a) {
+    gemv_body<bf16_t, PRO_PRENORM, EPI, true, U, 4, 1, false, true>(a, blockIdx.x, 0, 1, ChainWait{});
+}
+
 // One launch running up to GEMV_CHAIN_MAX dependent batch-1 GEMVs (fm_llm.cpp: a layer's wo, w1||w3,
 // w2 and the next layer's qkv).  Stage s owns blocks [off[s], off[s+1]) (dispatch is in block
 // order, so a waiting block only waits on blocks already resident or done); a stage's blocks
@@ -918,16 +929,39 @@ static void gemv_pair_go(hipStream_t s, const GemvArgs<bf16_t>& a0) {
     else gemv_pair_u<false>(s, a, grid, lds);
 }
 
+template <int EPI> static void gemv_pair_q8_go(hipStream_t s, const GemvArgs<bf16_t>& a0) {
+    GemvArgs<bf16_t> a = a0;
+    a.dbg = fm_tuning().dbg;
+    FMCHECK(a.K % 64 == 0 && a.wscale && !a.wsz, "int8 GEMV, two rows: K in whole 64-k units, scales set");
+    const dim3 grid(FM_CEIL(a.N, 16), 1);
+    const size_t lds = gemv_lds_bytes(2, a.K, sizeof(bf16_t));
+    // (16 units in flight: the SwiGLU8 form spills 208 B per lane under its 5 waves per SIMD and is not instantiated;
+    // the frame keeps its one-row passes under q_u 16)
+    if (fm_tuning().q_u == 16) {
+        if constexpr (EPI == EPI_STORE) gemv_pair_q8_kernel<EPI, 16><<<grid, 256, lds, s>>>(a);
+        else FMCHECK(false, "int8 GEMV, two rows, SwiGLU8: no form at q_u 16");
+    } else if (fm_tuning().q_u == 8) gemv_pair_q8_kernel<EPI, 8><<<grid, 256, lds, s>>>(a);
+    else if (fm_tuning().q_u == 2) gemv_pair_q8_kernel<EPI, 2><<<grid, 256, lds, s>>>(a);
+    else gemv_pair_q8_kernel<EPI, 4><<<grid, 256, lds, s>>>(a);
+}
+
 template <typename T> void launch_gemv(hipStream_t s, const GemvArgs<T>& a, int pro, int epi, int ksb) {
     // PRO_PRENORM stages the [K/16][R] tile sums in the 256 * R floats of the reduction buffer
     FMCHECK(pro != PRO_PRENORM || (a.K <= 4096 && a.R <= GEMV_RMAX), "PRO_PRENORM needs K <= 4096, R <= 8");
-    // ss_gran 1 at two rows: bf16 w1 || w3 only (K <= 4096: two 8-element chunks per thread and row)
+    // ss_gran 1 at two rows: bf16 w1 || w3, int8 w1 || w3 and wqkv (K <= 4096: two 8-element chunks per thread and row)
     const bool pair = pro == PRO_PRENORM && a.ss_gran == 1 && a.R == 2;
+    const bool q8 = a.Wq && !a.wsz;
     FMCHECK(pro != PRO_PRENORM ||
                 (a.ss_in && (a.ss_gran != 1 || (a.R == 1 && ksb == 1 && a.K <= 3 * 8 * 256) ||
-                             (pair && sizeof(T) == 2 && epi == EPI_SWIGLU8 && ksb == 1 && !a.Wq))),
-            "PRO_PRENORM: ss_in set (also with ss_gran 1: one row, or two for bf16 w1 || w3; whole K staged)");
+                             (pair && sizeof(T) == 2 && ksb == 1 &&
+                              (q8 ? epi == EPI_SWIGLU8 || epi == EPI_STORE : epi == EPI_SWIGLU8 && !a.Wq)))),
+            "PRO_PRENORM: ss_in set (also with ss_gran 1: one row, or two for bf16 w1 || w3 and int8 w1 || w3 / wqkv; whole K staged)");
     if constexpr (sizeof(T) == 2) {
+        if (pair && q8) {
+            if (epi == EPI_SWIGLU8) gemv_pair_q8_go<EPI_SWIGLU8>(s, a);
+            else gemv_pair_q8_go<EPI_STORE>(s, a);
+            return;
+        }
         if (pair) {
             gemv_pair_go(s, a);
             return;

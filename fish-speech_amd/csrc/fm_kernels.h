@@ -331,7 +331,8 @@ struct RowGemvArgs {
     size_t pf_slot_stride, pf_layer_off;
     int pf_S, pf_nkv, pf_hd;
     unsigned long long* dbg;  // developer timestamps (launcher: fm_tune debug_ts)
-    // two activation rows against one pass over the weights (fm_tune fast_pair; bf16 FIN / NORM_STORE, no x gather):
+    // two activation rows against one pass over the weights (fm_tune fast_pair: bf16 FIN / NORM_STORE; fast_pair_q: int8 FIN,
+    // int4 FIN / NORM_STORE / NORM_SWIGLU; no x gather):
     // xr = 2, row 1's x, residual row (residx gathers this row only; row 0's is res as it stands), and outputs.
     // NORM_STORE: blocks whose rows all lie in [0, skip0) compute row 1 only, and row 0's outputs below skip0
     // are never stored (the Q rows of codebook 0's pass)
@@ -345,7 +346,8 @@ struct RowGemvArgs {
 int rowgemv_u(int K, int qm);  // per-wave chunk depth for K (qm 1: int8 codes; 0: not eligible)
 void launch_rowgemv(hipStream_t s, const RowGemvArgs& a, int kind);
 // whether the two-row form (RowGemvArgs::xr = 2) of this kind exists at depth K (kind -1: the fused attention + wo pair form)
-bool rowgemv_pair_ok(int kind, int K, bool gathered);
+// on bf16 weights (qm 0), int8 (1) or int4 (2) codes
+bool rowgemv_pair_ok(int kind, int K, bool gathered, int qm = 0);
 // batch-1 fast-model attention + wo in one launch (fm_rowgemv.hip fattn_wo_kernel; wo in bf16, int8 or int4): the
 // attention blocks store their output as tagged words (bf16 << 16 | gen) into xt [nh * hd]; the wo
 // row-pair blocks (RowGemvArgs FIN; its X is unused) poll them.  gen: the launch's index in the
@@ -369,7 +371,7 @@ struct FattnWoArgs {
     int qcol, qrows;
     // fm_tune rowgemv bit 6 / fast_dead_q bit 1 (at.cpos == 0): Q was not computed; the attention output is 0 + v
     int kv0;
-    // fm_tune fast_pair (bf16, at.cpos == 1): codebook positions 0 and 1 in one launch; at.qkv holds two rows
+    // fm_tune fast_pair / fast_pair_q (at.cpos == 1): codebook positions 0 and 1 in one launch; at.qkv holds two rows
     // (row 0: the K / V part only), qtab set: row 1's row comes from the table instead.  1: both rows' outputs
     // go to xt (2 K words) and wo runs on two rows (RowGemvArgs::xr = 2); 2 (the last layer): row 0 ends at
     // its K / V cache write and wo runs on row 1 alone (A.wo: row 1's residual and output)

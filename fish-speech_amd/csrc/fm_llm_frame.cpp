@@ -902,6 +902,7 @@ template <typename T> struct Run {
         bool row_here;  // this layer's QKV on the row-block GEMV (a stack's first layer: only with rowgemv bit 4)
         bool tab;       // rowgemv bit 5 / fast_dead_q bit 0: the first fast layer at codebook > 0 inside fw: its q|k|v row comes from the table, no QKV launch
         bool kv0;       // rowgemv bit 6 / fast_dead_q bit 1: codebook 0: only K / V are projected (row path; int8: the tile path) and the attention reads no Q (one position: output = v)
+        bool kv0_ok;    // weight-only handles: the K / V-only forms fast_dead_q bit 1 uses exist at this layer's shape (whether or not the bit is set)
         bool kv_only;   // the layer ends after its K / V cache write (fm_tune fast_tail: its output would be discarded)
         bool sw;        // slow model: attention + wo as one launch (slow_attn_wo_kernel), no attention launch (fm_tune slow_attn_wo / slow_attn_wo_q)
     };
@@ -944,14 +945,16 @@ template <typename T> struct Run {
         // fm_tune fast_dead_q: the same two forms on weight-only int8 / int4 handles, only where the fused launch is
         // the layer's form and its table / K-V-only instantiation is one that stays resident (fattn_wo_dead_ok).
         // K / V only: int4 on the row form as bf16 (8 rows per block), int8 on the tile form from tile nq / 16
-        const int dq = sizeof(T) == 2 && c.is_fast && c.n == 1 && fw_any && fattn_wo_dead_ok(d.nq(), fq) ? dead_q_bits(m) : 0;
+        const bool dqf = sizeof(T) == 2 && c.is_fast && c.n == 1 && fw_any && fattn_wo_dead_ok(d.nq(), fq);
+        const int dq = dqf ? dead_q_bits(m) : 0;
         p.tab = (bits56 || (dq & 1)) && c.first && c.xidx && p.fw && qkv0_live();
         p.kv0 = bits56 && c.cpos == 0 && (row_bits() & 64) && p.row_here && !p.att_wo && d.hd <= 256 &&
                 (d.nqkv() - d.nq()) % fm_tuning().row_qkv_rp == 0;
-        if ((dq & 2) && c.cpos == 0 && !p.att_wo && d.hd <= 256)
-            p.kv0 = m->quant == FM_QUANT_INT4
+        p.kv0_ok = dqf && m->quant && !m->fdm.o_bias && c.cpos == 0 && !p.att_wo && d.hd <= 256 &&
+                   (m->quant == FM_QUANT_INT4
                         ? p.row_here && (d.nqkv() - d.nq()) % fm_tuning().row_qkv_rp == 0 && (d.nqkv() - d.nq()) % 8 == 0
-                        : !p.row_here && d.nq() % 16 == 0 && d.nqkv() % 16 == 0;
+                        : !p.row_here && d.nq() % 16 == 0 && d.nqkv() % 16 == 0);
+        if ((dq & 2) && c.cpos == 0 && !p.att_wo && d.hd <= 256) p.kv0 = p.kv0_ok;
         return p;
     }
     // the fast model's attention operands at this layer (the attention launch, fattn_wo, PRO_FATT)
@@ -988,6 +991,9 @@ template <typename T> struct Run {
             a.ldx = d.dim;
             a.ss_in = m->ssX;
             a.ss_gran = p.rf ? 1 : 0;
+            // (fm_tune fast_pair_q, int8: both rows through the whole wqkv -- row 0's Q outputs are stored and never read;
+            // its K / V tiles are what the one-row launch from tile nq / 16 computes)
+            if (c.pair) a.R = 2;
             gemv(c.L.wqkv, a, PRO_PRENORM, EPI_STORE, 1, "linear", p.kv0 ? d.nq() / 16 : 0);  // (kv0 here: weight-only int8)
         }
     }
@@ -1152,6 +1158,11 @@ template <typename T> struct Run {
             r.Y = (bf16_t*)row1(c, m->act, d.inter);
             r.N = 2 * d.inter;
             r.K = d.dim;
+            if (c.pair == 1) {  // (fm_tune fast_pair_q, int4: the two-row form; the pair's last layer runs row 1 alone)
+                r.xr = 2;
+                r.X1 = r.X + d.dim;
+                r.Y1 = r.Y + d.inter;
+            }
             rowgemv(r, ROWGEMV_NORM_SWIGLU);
             return;
         }
@@ -1327,6 +1338,7 @@ template <typename T> struct Run {
     bool fast_pair_live(int n) const {
         const FmTuning& t = fm_tuning();
         const StackDims& d = m->fdm;
+        if (m->quant) return fast_pair_q_live(n);  // (fast_pair itself is inert on weight-only handles)
         // (two fast layers at least: consecutive writers of the pair's row-1 tagged words then always differ in tag)
         if (!(sizeof(T) == 2 && !m->quant && n == 1 && m->C >= 2 && d.n_layer >= 2 && t.fast_pair && t.fast_tail && !t.gemv_chain &&
               !row_w13(n) && d.dim <= 4096 && rowgemv_pair_ok(-1, d.nq(), false) && rowgemv_pair_ok(ROWGEMV_FIN, d.nq(), true) &&
@@ -1338,6 +1350,35 @@ template <typename T> struct Run {
             const Small c1{d, m->fast[l], n, l == 0, nullptr, 0, m->cols, 1, nullptr, nullptr, true, 1, l, kp, nullptr};
             const SmallPath p0 = small_path(c0, false), p1 = small_path(c1, false);
             if (!(p0.kv0 && p1.fw && p1.rf && !p1.att_wo && (l == 0 ? p1.tab : p1.row_here))) return false;
+        }
+        return true;
+    }
+    // fm_tune fast_pair_q: the same pass on a weight-only handle (a compact one too: the row-major codes and the GEMV
+    // units are not what compact frees), bf16 compute, on the default routing of each mode.  Bit 0, int8: wo and w2 on the
+    // row-block GEMV, wqkv and w1 || w3 on the tile kernel under ss_gran 1 (its two-row prologue stages K <= 4096).  Bit
+    // 1, int4: every linear on the row-block GEMV (rowgemv_q4 bits 0, 1, 2 and 4 -- the first layer's K / V rows come
+    // from its row form) streaming the codes.  Both: a fast stack without an o-bias, the QKV table (fast_dead_q bit 0)
+    // live, the fused launch every layer's form at position 1, codebook 0's K / V-only launch available at the shape
+    // (the forms of fast_dead_q bit 1, whether or not that bit is set) and two-row forms instantiated at the model's
+    // depths.  Anywhere else the one-row passes run.
+    bool fast_pair_q_live(int n) const {
+        const FmTuning& t = fm_tuning();
+        const StackDims& d = m->fdm;
+        const int qm = m->qmode();
+        if (!(sizeof(T) == 2 && qm && (t.fast_pair_q & qm) && n == 1 && m->C >= 2 && d.n_layer >= 2 && t.fast_tail &&
+              !t.gemv_chain && !d.o_bias && row_fin(n) && rowgemv_pair_ok(-1, d.nq(), false, qm) &&
+              rowgemv_pair_ok(ROWGEMV_FIN, d.nq(), true, qm) && rowgemv_pair_ok(ROWGEMV_FIN, d.inter, false, qm)))
+            return false;
+        if (qm == 2 ? !((row_bits() & 23) == 23 && row_qkv(n) && row_w13(n) && rowgemv_pair_ok(ROWGEMV_NORM_STORE, d.dim, false, qm) &&
+                        rowgemv_pair_ok(ROWGEMV_NORM_SWIGLU, d.dim, false, qm))
+                    : !(!row_qkv(n) && !row_w13(n) && d.dim <= 4096 && d.dim % 64 == 0 && t.q_u <= 8))  // (q_u 16: no two-row SwiGLU8 form)
+            return false;
+        const KsbPlan kp{1, 1};
+        for (int l = 0; l < d.n_layer; ++l) {
+            const Small c0{d, m->fast[l], n, l == 0, nullptr, 0, nullptr, 0, nullptr, nullptr, true, 0, l, kp, nullptr};
+            const Small c1{d, m->fast[l], n, l == 0, nullptr, 0, m->cols, 1, nullptr, nullptr, true, 1, l, kp, nullptr};
+            const SmallPath p0 = small_path(c0, false), p1 = small_path(c1, false);
+            if (!(p0.kv0_ok && p1.fw && p1.rf && !p1.att_wo && (l == 0 ? p1.tab : p1.row_here == (qm == 2)))) return false;
         }
         return true;
     }

@@ -497,8 +497,11 @@ void fattn_wo_op(hipStream_t s, const FattnWoOp& o) {
     const int nh = o.nh, nkv = o.nkv, hd = o.hd, S = o.S, N = o.N, K = nh * hd, ld = (nh + 2 * nkv) * hd;
     const int qm = o.quant == FM_QUANT_INT4 ? 2 : (o.quant == FM_QUANT_INT8 ? 1 : 0);
     // "not dispatchable" is a status, not a launch: what small_path asks before it takes the fused launch
+    // (status[0]: the dispatched depth -- rowgemv_u's chunks per wave -- or 0 where the form is not instantiated)
     o.status[0] = fattn_wo_ok(nh, nkv, hd, o.cpos, N, K, qm) && (!(o.qtab || o.kv0) || fattn_wo_dead_ok(K, qm)) &&
-                  (!o.pair || rowgemv_pair_ok(-1, K, false));
+                          (!o.pair || rowgemv_pair_ok(-1, K, false, qm))
+                      ? rowgemv_u(K, qm)
+                      : 0;
     o.status[1] = 0;
     if (!o.status[0]) return;
     RowGemvArgs r{};
@@ -1206,6 +1209,129 @@ void rowgemv_pair_op(hipStream_t s, const RowGemvPairOp& o) {
     yt.get(s);
 }
 
+// the two-row forms on weight-only codes (fm_tune fast_pair_q): w quantised on the device by the model's rule (int8:
+// launch_quant_rows; int4: launch_quant4 + launch_pack_q4_rows), then on the same device operands the two-row launch
+// (y2 [2][y_ld]) and the one-row production launcher once per row (y1 [2][y_ld]; row 0 with skip0 > 0 still computes
+// every output: the caller compares from skip0 on).  Both outputs in/out.
+struct RowGemvPairQOp {
+    int quant, gs, kind;
+    const float *w, *nw;
+    float eps;
+    const float *x, *res0, *res1;
+    int res_rows, ldr;
+    const int32_t* idx;
+    int idx_n, idx_col, skip0, N, K;
+    float *y2, *y1;
+    int y_ld;
+    int8_t* q_out;
+    float *scale_out, *zero_out;
+};
+
+void rowgemv_pair_q_op(hipStream_t s, const RowGemvPairQOp& o) {
+    DevBufs b(s);
+    const int N = o.N, K = o.K;
+    const bool q4 = o.quant == FM_QUANT_INT4, fin = o.kind == ROWGEMV_FIN;
+    RowGemvArgs a{};
+    bf16_t* wd = b.upload<bf16_t>(o.w, (size_t)N * K);
+    if (q4) {
+        const int ng = K / o.gs;
+        uint8_t* dq = (uint8_t*)b.alloc((size_t)N * K);
+        uint32_t* dsz = (uint32_t*)b.alloc((size_t)N * ng * 4);
+        uint32_t* words = (uint32_t*)b.alloc((size_t)N * K / 2);
+        launch_quant4(s, wd, N, K, o.gs, dq, dsz);
+        launch_pack_q4_rows(s, dq, N, K, words);
+        HIPCHK(hipGetLastError());
+        a.Wq4 = words;
+        a.wsz = dsz;
+        a.gs = o.gs;
+        if (o.q_out) {
+            HIPCHK(hipMemcpyAsync(o.q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        if (o.scale_out || o.zero_out) {
+            std::vector<uint32_t> hs((size_t)N * ng);
+            HIPCHK(hipMemcpyAsync(hs.data(), dsz, hs.size() * 4, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            for (size_t i = 0; i < hs.size(); ++i) {
+                const uint32_t us = hs[i] << 16, uz = hs[i] & 0xffff0000u;
+                if (o.scale_out) memcpy(&o.scale_out[i], &us, 4);
+                if (o.zero_out) memcpy(&o.zero_out[i], &uz, 4);
+            }
+        }
+    } else {
+        int8_t* dq = (int8_t*)b.alloc((size_t)N * K);
+        bf16_t* ds = (bf16_t*)b.alloc((size_t)N * 2);
+        launch_quant_rows<bf16_t>(s, wd, N, K, dq, ds);
+        HIPCHK(hipGetLastError());
+        a.Wq = dq;
+        a.wscale = ds;
+        if (o.q_out) {
+            HIPCHK(hipMemcpyAsync(o.q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        if (o.scale_out) download<bf16_t>(ds, (size_t)N, o.scale_out, s);
+    }
+    const bf16_t* X = b.upload<bf16_t>(o.x, (size_t)2 * K);
+    a.ldx = K;
+    if (o.nw) a.nw = b.upload<bf16_t>(o.nw, (size_t)K);
+    a.eps = o.eps;
+    a.N = N;
+    a.K = K;
+    const bf16_t *r0 = nullptr, *r1 = nullptr;
+    int32_t* id = nullptr;
+    if (fin) {
+        r0 = b.upload<bf16_t>(o.res0, (size_t)N);
+        r1 = b.upload<bf16_t>(o.res1, (size_t)o.res_rows * o.ldr);
+        if (o.idx) {
+            id = (int32_t*)b.alloc((size_t)o.idx_n * 4);
+            b.put(id, o.idx, (size_t)o.idx_n * 4);
+        }
+    }
+    InOut<bf16_t> y2(b, o.y2, (size_t)2 * o.y_ld), y1(b, o.y1, (size_t)2 * o.y_ld);
+    {  // the two-row launch
+        RowGemvArgs t = a;
+        t.X = X;
+        t.X1 = X + K;
+        t.xr = 2;
+        if (fin) {
+            t.res = r0;
+            t.res1 = r1;
+            t.ldr = o.ldr;
+            t.residx = id;
+            t.res_col = o.idx_col;
+            t.res_rows = id ? o.res_rows : 0;
+            t.res_out = y2.d;
+            t.res_out1 = y2.d + o.y_ld;
+        } else {
+            t.Y = y2.d;
+            t.Y1 = y2.d + o.y_ld;
+            t.skip0 = o.kind == ROWGEMV_NORM_STORE ? o.skip0 : 0;
+        }
+        launch_rowgemv(s, t, o.kind);
+        HIPCHK(hipGetLastError());
+    }
+    for (int r = 0; r < 2; ++r) {  // the one-row production launcher, row by row
+        RowGemvArgs t = a;
+        t.X = X + (size_t)r * K;
+        if (fin) {
+            t.res = r ? r1 : r0;
+            t.ldr = r ? o.ldr : N;
+            if (r) {
+                t.residx = id;
+                t.res_col = o.idx_col;
+                t.res_rows = id ? o.res_rows : 0;
+            }
+            t.res_out = y1.d + (size_t)r * o.y_ld;
+        } else {
+            t.Y = y1.d + (size_t)r * o.y_ld;
+        }
+        launch_rowgemv(s, t, o.kind);
+        HIPCHK(hipGetLastError());
+    }
+    y2.get(s);
+    y1.get(s);
+}
+
 void prompt_skinny_op(hipStream_t s, const float* w, const float* x, int ldx, int R, int N, int K, int ks, int act,
                       float* out, int out_rows, int ldo, int reps) {
     DevBufs b(s);
@@ -1417,9 +1543,9 @@ int fm_op_fattn_wo(int device, int quant, int gs, int fused, const float* qkv, c
         FMCHECK(!qtab || (idx && !kv0 && qrows >= 1 && qrows == res_rows), "the table form is gathered by the residual's index");
         FMCHECK(!kv0 || (!idx && cpos == 0), "the K / V-only form runs at codebook 0, no gather");
         FMCHECK(pair >= 0 && pair <= 2, "pair must be 0, 1 or 2");
-        FMCHECK(!pair || (fused && quant == FM_QUANT_NONE && !kv0 && cpos == 1 && (qtab != nullptr) == (idx != nullptr) &&
+        FMCHECK(!pair || (fused && !kv0 && cpos == 1 && (qtab != nullptr) == (idx != nullptr) &&
                           (pair == 1 ? res0 != nullptr : !qtab)),
-                "pair form: fused, bf16, positions 0 and 1, row 0's residual (pair 1), no table in the last layer (pair 2)");
+                "pair form: fused, positions 0 and 1, row 0's residual (pair 1), no table in the last layer (pair 2)");
         check_slot_rows(1, &slot, nullptr, nslots, layers, layer, S);
         StreamGuard g(device);
         const FattnWoOp o{quant, gs, fused, qkv, qtab, qrows, idx, idx_n, idx_col, nh, nkv, hd, qn, kn, qk_norm, eps,
@@ -1927,6 +2053,94 @@ int fm_op_rowgemv_pair(int device, int kind, const float* w, const float* bias, 
         RowGemvPairOp o{kind, w, bias, nw, eps, x, res0, res1, res_rows, ldr, idx, idx_n, idx_col, skip0, N, K, y, y_ld};
         StreamGuard g(device);
         rowgemv_pair_op(g.s, o);
+    });
+}
+
+int fm_op_rowgemv_pair_q(int device, int quant, int gs, int kind, const float* w, const float* nw, float eps, const float* x,
+                         const float* res0, const float* res1, int res_rows, int ldr, const int32_t* idx, int idx_n,
+                         int idx_col, int skip0, int N, int K, float* y2, float* y1, int y_ld, int8_t* q_out, float* scale_out,
+                         float* zero_out) {
+    return fm_guard([&] {
+        FMCHECK(w && x && y2 && y1, "null argument");
+        FMCHECK(quant == FM_QUANT_INT8 || quant == FM_QUANT_INT4, "quant must be int8 or int4");
+        const bool q4 = quant == FM_QUANT_INT4, fin = kind == ROWGEMV_FIN;
+        FMCHECK(fin || kind == ROWGEMV_NORM_STORE || kind == ROWGEMV_NORM_SWIGLU, "kind must be 0 (fin), 1 (norm, store) or 2 (norm, swiglu)");
+        FMCHECK(!q4 || (gs >= 8 && gs % 8 == 0 && K % gs == 0), "int4: a group size in whole 8-k lane runs that divides K");
+        FMCHECK(rowgemv_pair_ok(kind, K, fin && idx != nullptr, q4 ? 2 : 1),
+                "no two-row code form of this kind at this depth (K: whole chunks of 512; int8: fin only, at most 5 per wave; int4: "
+                "fin at most 5, the norm kinds at most 3)");
+        const int rp = fin ? 2 : 8;
+        FMCHECK(N >= rp && N % rp == 0 && y_ld >= (kind == ROWGEMV_NORM_SWIGLU ? N / 2 : N),
+                "N must be whole row blocks (fin 2, else 8), y rows at least as wide as the outputs");
+        FMCHECK(fin == (nw == nullptr) && fin == (res0 != nullptr) && fin == (res1 != nullptr),
+                "fin takes both residual rows, the norm kinds a norm weight");
+        FMCHECK(!fin || (res_rows >= 1 && ldr >= N && (idx || res_rows == 1)), "bad residual table / stride");
+        FMCHECK(!idx || (fin && idx_n >= 1 && idx_col >= 0 && idx_col < idx_n), "bad gather (fin only)");
+        FMCHECK(kind != ROWGEMV_NORM_STORE || (skip0 >= 0 && skip0 <= N), "skip0 outside 0..N");
+        RowGemvPairQOp o{quant, gs, kind, w, nw, eps, x, res0, res1, res_rows, ldr, idx, idx_n, idx_col, skip0, N, K, y2, y1, y_ld,
+                         q_out, scale_out, zero_out};
+        StreamGuard g(device);
+        rowgemv_pair_q_op(g.s, o);
+    });
+}
+
+// the tile kernel's two-row ss_gran 1 form on weight-only int8 codes (fm_tune fast_pair_q): w quantised on the device
+// by the model's rule (launch_quant_rows) and packed by the model's launcher (launch_pack_q8); then on the same device
+// operands the two-row launch (y2) and the one-row production launch once per row (y1)
+int fm_op_gemv_pair_q(int device, int quant, int epi, const float* w, const float* nw, float eps, const float* x, int N,
+                      int K, float* y2, int y2_rows, float* y1, int ldy, int8_t* q_out, float* scale_out) {
+    return fm_guard([&] {
+        FMCHECK(w && nw && x && y2 && y1, "null argument");
+        FMCHECK(quant == FM_QUANT_INT8, "the two-row tile form exists on int8 codes (int4 models run these linears on the row GEMV)");
+        FMCHECK(epi == EPI_STORE || epi == EPI_SWIGLU8, "epi must be 0 (store) or 7 (SwiGLU8)");
+        FMCHECK(N >= 16 && N % 16 == 0 && K >= 64 && K % 64 == 0 && K <= 4096, "N in whole 16-row tiles, K in whole 64-k units, at most 4096");
+        FMCHECK(ldy >= (epi == EPI_SWIGLU8 ? N / 2 : N) && y2_rows >= 2, "output rows too short or too few");
+        StreamGuard g(device);
+        DevBufs b(g.s);
+        bf16_t* dw = b.upload<bf16_t>(w, (size_t)N * K);
+        int8_t* dq = (int8_t*)b.alloc((size_t)N * K);
+        bf16_t* ds = (bf16_t*)b.alloc((size_t)N * 2);
+        launch_quant_rows<bf16_t>(g.s, dw, N, K, dq, ds);
+        int8_t* pq = (int8_t*)b.alloc((size_t)N * K);
+        launch_pack_q8(g.s, dq, N, K, pq);
+        HIPCHK(hipGetLastError());
+        if (q_out) {
+            HIPCHK(hipMemcpyAsync(q_out, dq, (size_t)N * K, hipMemcpyDeviceToHost, g.s));
+            HIPCHK(hipStreamSynchronize(g.s));
+        }
+        if (scale_out) download<bf16_t>(ds, (size_t)N, scale_out, g.s);
+        GemvArgs<bf16_t> a{};
+        a.Wq = (const unsigned char*)pq;
+        a.wscale = ds;
+        a.nw = b.upload<bf16_t>(nw, (size_t)K);
+        a.eps = eps;
+        const bf16_t* X = b.upload<bf16_t>(x, (size_t)2 * K);
+        a.ldx = K;
+        a.N = N;
+        a.K = K;
+        a.ldy = ldy;
+        a.ss_in = (float*)b.alloc((size_t)(K / 16) * 2 * 4);  // (set, never read under ss_gran 1)
+        a.ss_gran = 1;
+        a.tickets = (int*)b.alloc((size_t)(N / 16 + 16) * 4);
+        InOut<bf16_t> o2(b, y2, (size_t)y2_rows * ldy), o1(b, y1, (size_t)2 * ldy);
+        {
+            GemvArgs<bf16_t> t = a;
+            t.X = X;
+            t.R = 2;
+            t.Y = o2.d;
+            launch_gemv<bf16_t>(g.s, t, PRO_PRENORM, epi, 1);
+            HIPCHK(hipGetLastError());
+        }
+        for (int r = 0; r < 2; ++r) {
+            GemvArgs<bf16_t> t = a;
+            t.X = X + (size_t)r * K;
+            t.R = 1;
+            t.Y = o1.d + (size_t)r * ldy;
+            launch_gemv<bf16_t>(g.s, t, PRO_PRENORM, epi, 1);
+            HIPCHK(hipGetLastError());
+        }
+        o2.get(g.s);
+        o1.get(g.s);
     });
 }
 

@@ -90,10 +90,12 @@ template <int QM> struct RowT {
 // TX (tagged x, fattn_wo_kernel): x is read after the weights, from 32-bit words (bf16 << 16 | gen)
 // that a producer in the same launch stores write-through; the wave re-reads its words (sc1) until
 // every tag equals gen (bounded; *err set on timeout).  blk: the row block's index.
-// XR 2 (fm_tune fast_pair; bf16, STORE / FIN): two activation rows against one pass over the weights.  Row 1's
-// operands are RowGemvArgs::X1 / res1 / res_out1 / Y1 (TX: the second K words of xt); G gathers row 1's residual
-// only.  One accumulator set, one RMSNorm statistic and one epilogue thread per (x row, weight row): every output
-// is the one-row form's operations on the same inputs in the same order.
+// XR 2 (fm_tune fast_pair: bf16, STORE / FIN; fast_pair_q: int8 / int4 codes, SWIGLU too): two activation rows against one
+// pass over the weights.  Row 1's operands are RowGemvArgs::X1 / res1 / res_out1 / Y1 (TX: the second K words of xt); G
+// gathers row 1's residual only.  One accumulator set, one RMSNorm statistic and one epilogue thread per (x row, weight
+// row): every output is the one-row form's operations on the same inputs in the same order.  The code forms load the
+// codes, row scales and group (scale, zero) words once for both rows; int8 keeps its 128 * sum(x) and int4 its
+// s * B + (z - 136 s) * sum x per x row.
 // TxPoll (NG 2 only; speed, never correctness -- every full read checks every tag): delay, 10-ns ticks from the wave's
 // start to its first read of x; sleep, the s_sleep argument between reads (1, 4 or 16); cheap, one word per 128
 // elements of the wave's range is polled until current before the first full read.
@@ -105,7 +107,8 @@ template <int U, int RP, bool PRENORM, int EPI, bool G, int QM, bool TX, int XR 
 __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk, const uint32_t* xt, const uint32_t gen,
                                              int* err, const TxPoll pw = TxPoll{}) {
     static_assert(!TX || (!PRENORM && EPI == 1), "tagged x: the residual form only");
-    static_assert(XR == 1 || (XR == 2 && QM == 0 && EPI <= 1 && (!G || EPI == 1)), "two x rows: bf16 STORE / FIN");
+    static_assert(XR == 1 || (XR == 2 && (EPI == 1 || (QM != 1 && EPI <= (QM ? 2 : 0))) && (!G || EPI == 1)),
+                  "two x rows: FIN; bf16 and int4 STORE; int4 SWIGLU");
     constexpr bool FIN = EPI == 1;
     using R = RowT<QM>;
     using XV = typename R::XV;
@@ -113,7 +116,7 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     constexpr int SB = XR * 4 * RP;            // red: [XR][4 waves][RP] partials, then the statistics
     // deep runs (w2): row 1's x chunk is loaded into the registers row 0's chunk leaves, after its dot products, so
     // the two-row form keeps the one-row form's register budget (no scratch under waves_per_eu 5)
-    constexpr bool LATE = XR == 2 && !TX && !PRENORM && U >= 10;
+    constexpr bool LATE = XR == 2 && QM == 0 && !TX && !PRENORM && U >= 10;
     static_assert(NG == 1 || (NG == 2 && TX), "two row blocks per 512-thread block: the tagged-x form only");
     // NG 2 (slow_attn_wo_kernel): a 512-thread block holds two independent 4-wave groups, each one row block with its
     // own red slice; tid is the thread's index in its group (NG 1: threadIdx.x itself)
@@ -361,7 +364,9 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
     for (int x = 0; x < XR; ++x)
 #pragma unroll
         for (int r = 0; r < RP; ++r) acc[x][r] = 0.f;
-    float xs = 0.f;  // int8: this lane's sum of x (the 128 offset of the codes)
+    float xs[XR];  // int8: this lane's sum of each x row (the 128 offset of the codes)
+#pragma unroll
+    for (int x = 0; x < XR; ++x) xs[x] = 0.f;
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (u < nmy) {
@@ -373,6 +378,8 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
             } else if constexpr (QM == 2) {
                 const u32x4_t ones = {0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};
                 const float xl = dot8r(ones, xv[0][u], 0.f);  // sum of the lane's 8 x
+                float xl1 = 0.f;
+                if constexpr (XR == 2) xl1 = dot8r(ones, xv[1][u], 0.f);
 #pragma unroll
                 for (int r = 0; r < RP; ++r) {
                     const uint32_t w = w4[u][r];
@@ -383,24 +390,35 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
                     const float sc = lo16(szv[u][r]), zr = hi16(szv[u][r]);
                     acc[0][r] = fmaf(sc, B, acc[0][r]);
                     acc[0][r] = fmaf(zr - 136.f * sc, xl, acc[0][r]);
+                    if constexpr (XR == 2) {  // (the word unpacked once for both rows)
+                        const float B1 = dot8r(A, xv[1][u], 0.f);
+                        acc[1][r] = fmaf(sc, B1, acc[1][r]);
+                        acc[1][r] = fmaf(zr - 136.f * sc, xl1, acc[1][r]);
+                    }
                 }
             } else {
-                float xf[8];
+                float xf[XR][8];
 #pragma unroll
-                for (int h = 0; h < 4; ++h) {
-                    xf[2 * h] = lo16(xv[0][u][h]);
-                    xf[2 * h + 1] = hi16(xv[0][u][h]);
+                for (int x = 0; x < XR; ++x) {
+#pragma unroll
+                    for (int h = 0; h < 4; ++h) {
+                        xf[x][2 * h] = lo16(xv[x][u][h]);
+                        xf[x][2 * h + 1] = hi16(xv[x][u][h]);
+                    }
+                    xs[x] += ((xf[x][0] + xf[x][1]) + (xf[x][2] + xf[x][3])) + ((xf[x][4] + xf[x][5]) + (xf[x][6] + xf[x][7]));
                 }
-                xs += ((xf[0] + xf[1]) + (xf[2] + xf[3])) + ((xf[4] + xf[5]) + (xf[6] + xf[7]));
 #pragma unroll
                 for (int r = 0; r < RP; ++r) {
                     const uint32_t c0 = wv[u][r][0] ^ 0x80808080u, c1 = wv[u][r][1] ^ 0x80808080u;
-                    float t = acc[0][r];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) t = fmaf((float)((c0 >> (8 * e)) & 0xffu), xf[e], t);
+                    for (int x = 0; x < XR; ++x) {  // (the codes converted once for both rows)
+                        float t = acc[x][r];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) t = fmaf((float)((c1 >> (8 * e)) & 0xffu), xf[4 + e], t);
-                    acc[0][r] = t;
+                        for (int e = 0; e < 4; ++e) t = fmaf((float)((c0 >> (8 * e)) & 0xffu), xf[x][e], t);
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) t = fmaf((float)((c1 >> (8 * e)) & 0xffu), xf[x][4 + e], t);
+                        acc[x][r] = t;
+                    }
                 }
             }
         }
@@ -432,9 +450,14 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
             const float v = wave_sum(acc[x][r]);
             if (lane == 0) red[(4 * x + wave) * RP + r] = v;
         }
+    // int8: the four waves' sums of x, per x row (XR 1: behind the partials and the statistic; XR 2: behind both rows' of each)
+    constexpr int XSB = XR == 2 ? SB + 8 : 4 * RP + 4;
     if constexpr (QM == 1) {
-        const float v = wave_sum(xs);
-        if (lane == 0) red[4 * RP + 4 + wave] = v;
+#pragma unroll
+        for (int x = 0; x < XR; ++x) {
+            const float v = wave_sum(xs[x]);
+            if (lane == 0) red[XSB + 4 * x + wave] = v;
+        }
     }
     __syncthreads();
     if ((int)tid < XR * RP) {
@@ -442,7 +465,8 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         const float* rd = red + 4 * RP * ex;
         float v = ((rd[t] + rd[RP + t]) + rd[2 * RP + t]) + rd[3 * RP + t];
         if constexpr (QM == 1) {
-            const float xt = ((red[4 * RP + 4] + red[4 * RP + 5]) + red[4 * RP + 6]) + red[4 * RP + 7];
+            const float* rx = red + XSB + 4 * ex;
+            const float xt = ((rx[0] + rx[1]) + rx[2]) + rx[3];
             v = bfround(bfround(v - 128.f * xt) * bf2f(sv));
         }
         if (a.bias) v += bf2f(bv);
@@ -451,10 +475,10 @@ __device__ __forceinline__ void rowgemv_body(const RowGemvArgs& a, const int blk
         } else if constexpr (EPI == 3) {
             a.Yf[er] = bfround(v);
         } else if constexpr (EPI == 2) {  // gate rows t < RP / 2, up rows t >= RP / 2 (same wave)
-            const float up = __shfl_down(v, RP / 2, 64);
+            const float up = __shfl_down(v, RP / 2, 64);  // (XR 2: lanes ex RP + t, the partner in the same x row's group)
             if (t < RP / 2) {
                 const float g = bfround(v);
-                a.Y[blockIdx.x * (RP / 2) + t] = f2bf(bfround(g / (1.0f + expf(-g))) * bfround(up));
+                (ex ? a.Y1 : a.Y)[blockIdx.x * (RP / 2) + t] = f2bf(bfround(g / (1.0f + expf(-g))) * bfround(up));
             }
         } else if constexpr (XR == 2) {  // (row 0's outputs below skip0 are not wanted: a block straddling it)
             if (ex || er >= a.skip0) (ex ? a.Y1 : a.Y)[er] = f2bf(v);
@@ -508,6 +532,24 @@ void rowgemv2_kernel(RowGemvArgs a) {
         }
     }
     rowgemv_body<U, RP, PRENORM, EPI, G, 0, false, 2>(a, blockIdx.x, nullptr, 0u, nullptr);
+}
+
+// ... on int8 (QM 1) / int4 (QM 2) codes (fm_tune fast_pair_q): FIN, NORM_STORE and NORM_SWIGLU (EPI 2: no row is
+// skipped, both rows want every output).  The bf16 kernel above keeps its name and its code.
+template <int U, int RP, bool PRENORM, int EPI, bool G, int QM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RP == 2 ? 5 : 3)))
+void rowgemv2q_kernel(RowGemvArgs a) {
+    static_assert(QM == 1 || QM == 2, "the code forms");
+    if constexpr (EPI == 0) {
+        if (((int)blockIdx.x + 1) * RP <= a.skip0) {
+            RowGemvArgs b = a;
+            b.X = a.X1;
+            b.Y = a.Y1;
+            rowgemv_body<U, RP, PRENORM, EPI, false, QM, false>(b, blockIdx.x, nullptr, 0u, nullptr);
+            return;
+        }
+    }
+    rowgemv_body<U, RP, PRENORM, EPI, G, QM, false, 2>(a, blockIdx.x, nullptr, 0u, nullptr);
 }
 
 // smallest instantiated depth covering a wave's share of the K chunks (0: not eligible)
@@ -565,15 +607,65 @@ static void rowgemv2_go(hipStream_t s, const RowGemvArgs& a, int U) {
 // DESIGN section 3 round 9); a shape outside them runs the one-row passes.  NORM_STORE: 8 rows per block, runs
 // of at most 5 chunks; FIN: any depth, the gathered form (the first layer's wo, K = nq) at most 5; the fused
 // attention + wo pair form (kind -1): at most 5, within its 80 registers.
-bool rowgemv_pair_ok(int kind, int K, bool gathered) {
-    const int U = rowgemv_u(K, 0);
+// qm 1 / 2 (fm_tune fast_pair_q; chunks of 512 k): FIN on int8 and int4 codes at runs of at most 5 chunks (K <= 10240:
+// S2-Pro's w2 at 9728 is depth 5); NORM_STORE and NORM_SWIGLU on int4 codes (8 rows per block) at most 3 (K <= 6144;
+// 4 and 5 spill under their launch bounds); the fused pair form at depths 2 and, int4 only, 3 -- the ones that hold its
+// 80 registers without scratch (int8 depth 3 spills 28 B per lane).
+bool rowgemv_pair_ok(int kind, int K, bool gathered, int qm) {
+    const int U = rowgemv_u(K, qm);
     if (U <= 0) return false;
+    if (qm) {
+        if (kind == ROWGEMV_FIN) return U <= 5;
+        if (kind == ROWGEMV_NORM_STORE || kind == ROWGEMV_NORM_SWIGLU) return qm == 2 && U <= 3;
+        return kind == -1 && U <= (qm == 2 ? 3 : 2);
+    }
     if (kind == ROWGEMV_FIN) return U <= 5 || !gathered;
     if (kind == ROWGEMV_NORM_STORE) return U <= 5 && fm_tuning().row_qkv_rp == 8;
     return kind == -1 && U <= 5;
 }
 
+// the two-row code forms (rowgemv_pair_ok's depths: FIN 2 .. 5, the norm kinds 2 .. 3)
+template <int RP, bool PRENORM, int EPI, int QM>
+static void rowgemv2q_go(hipStream_t s, const RowGemvArgs& a, int U) {
+    const dim3 grid(a.N / RP), block(256);
+    const bool g = EPI == 1 && a.residx != nullptr;
+#define RG(u) (g ? rowgemv2q_kernel<u, RP, PRENORM, EPI, EPI == 1, QM> : rowgemv2q_kernel<u, RP, PRENORM, EPI, false, QM>)<<<grid, block, 0, s>>>(a)
+    if (U == 2) RG(2);
+    else if (U == 3) RG(3);
+    else if constexpr (EPI == 1) {
+        if (U == 4) RG(4);
+        else if (U == 5) RG(5);
+        else FMCHECK(false, "row GEMV, two rows on codes: fin has depths 2 .. 5");
+    } else {
+        FMCHECK(false, "row GEMV, two rows on codes: the norm kinds have depths 2 .. 3");
+    }
+#undef RG
+}
+
+static void launch_rowgemv2q(hipStream_t s, const RowGemvArgs& a, int kind, int U, int qm) {
+    FMCHECK(!a.W && !a.xidx && !a.bias && rowgemv_pair_ok(kind, a.K, a.residx != nullptr, qm),
+            "row GEMV, two rows on codes: int8 fin (depths 2 .. 5), int4 fin (2 .. 5) / norm + store / norm + swiglu (2 .. 3), no x gather, no bias");
+    if (kind == ROWGEMV_FIN) {
+        FMCHECK(a.N % 2 == 0 && a.X1 && a.res && a.res1 && a.res_out && a.res_out1,
+                "row GEMV (fin, two rows on codes): N even, both x and residual rows set");
+        if (qm == 2) rowgemv2q_go<2, false, 1, 2>(s, a, U);
+        else rowgemv2q_go<2, false, 1, 1>(s, a, U);
+    } else if (kind == ROWGEMV_NORM_STORE) {
+        FMCHECK(a.N % 8 == 0 && a.nw && a.X1 && a.Y && a.Y1 && a.skip0 >= 0,
+                "row GEMV (norm, store, two rows on int4 codes): N a whole number of 8-row blocks, norm weight, both rows set");
+        rowgemv2q_go<8, true, 0, 2>(s, a, U);
+    } else {
+        FMCHECK(a.N % 8 == 0 && a.nw && a.X1 && a.Y && a.Y1,
+                "row GEMV (norm, swiglu, two rows on int4 codes): N a whole number of 4 + 4-row blocks, norm weight, both rows set");
+        rowgemv2q_go<8, true, 2, 2>(s, a, U);
+    }
+}
+
 static void launch_rowgemv2(hipStream_t s, const RowGemvArgs& a, int kind, int U) {
+    if (a.Wq || a.Wq4) {
+        launch_rowgemv2q(s, a, kind, U, a.Wq4 ? 2 : 1);
+        return;
+    }
     FMCHECK(a.W && !a.Wq && !a.Wq4 && !a.xidx, "row GEMV, two rows: bf16, no x gather");
     if (kind == ROWGEMV_FIN) {
         FMCHECK(a.N % 2 == 0 && a.res && a.res1 && a.res_out && a.res_out1 && rowgemv_pair_ok(kind, a.K, a.residx != nullptr),
@@ -971,9 +1063,10 @@ void fattn_wo_kernel(FattnWoArgs A) {
 // (A.wo holds row 1's residual and output).  One gen per launch, the tag of position 1's launch index.
 // Each operation on each row is the one-row kernel's, in its order (the second RoPE pair of a lane, masked to
 // zero there because hd <= FW_MAXHD, only adds +0 to sums that are never -0 and is left out).
-template <int U, bool TAB, int XR>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
-void fattn_wo_pair_kernel(FattnWoArgs A) {
+// QM 1 / 2 (fm_tune fast_pair_q): the attention blocks are the same; the wo blocks run the two-row TX body on int8 /
+// int4 codes.  The hand-off, the tag, the poll bound and err are QM 0's.
+template <int U, bool TAB, int XR, int QM>
+__device__ __forceinline__ void fattn_wo_pair_body(const FattnWoArgs& A) {
     __shared__ __attribute__((aligned(16))) bf16_t kvs[4 * FW_MAXHD];  // K rows 0 .. 1, V rows 0 .. 1 (row 1: read, selected away)
     const FastFusedArgs<bf16_t>& at = A.at;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1071,7 +1164,18 @@ void fattn_wo_pair_kernel(FattnWoArgs A) {
         }
         return;
     }
-    rowgemv_body<U, 2, false, 1, TAB, 0, true, XR>(A.wo, (int)blockIdx.x - at.nkv, XR == 2 ? A.xt : A.xt + A.wo.K, gen, A.err);
+    rowgemv_body<U, 2, false, 1, TAB, QM, true, XR>(A.wo, (int)blockIdx.x - at.nkv, XR == 2 ? A.xt : A.xt + A.wo.K, gen, A.err);
+}
+template <int U, bool TAB, int XR>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
+void fattn_wo_pair_kernel(FattnWoArgs A) {
+    fattn_wo_pair_body<U, TAB, XR, 0>(A);
+}
+template <int U, bool TAB, int XR, int QM>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
+void fattn_wo_pair_q_kernel(FattnWoArgs A) {
+    static_assert(QM == 1 || QM == 2, "the code forms");
+    fattn_wo_pair_body<U, TAB, XR, QM>(A);
 }
 
 bool fattn_wo_ok(int nh, int nkv, int hd, int cpos, int N, int K, int qm) {
@@ -1110,12 +1214,32 @@ void launch_fattn_wo(hipStream_t s, const FattnWoArgs& A0) {
     FMCHECK(!(A.qtab || A.kv0) || fattn_wo_dead_ok(A.wo.K, qm),
             "fused fast attention + wo: no resident table / K-V-only form at this depth of int8 / int4 weights");
     if (A.pair) {
-        FMCHECK(qm == 0 && !A.kv0 && at.cpos == 1 && at.S >= 2 && rowgemv_pair_ok(-1, A.wo.K, false) && (A.qtab != nullptr) == G && (A.pair == 2 || (A.wo.res1 && A.wo.res_out1)),
-                "fused fast attention + wo, pair form: bf16, positions 0 and 1, both rows' residuals set");
+        FMCHECK(!A.kv0 && at.cpos == 1 && at.S >= 2 && rowgemv_pair_ok(-1, A.wo.K, false, qm) && (A.qtab != nullptr) == G && (A.pair == 2 || (A.wo.res1 && A.wo.res_out1)),
+                "fused fast attention + wo, pair form: positions 0 and 1, both rows' residuals set, an instantiated depth (bf16 2 .. 5 "
+                "chunks of 256 k per wave; int8 codes 2, int4 codes 2 .. 3 chunks of 512 k)");
         const bool two = A.pair != 2;
         // (a one-layer stack would pair the table form with the last-layer form; its row-1 words would also be
         // written by one launch index only, so two slots at one position could not tell each other's words apart)
         FMCHECK(two || !A.qtab, "fused fast attention + wo, pair form: the first layer is not the last");
+        if (qm) {  // fm_tune fast_pair_q: the resident depths (rowgemv_pair_ok)
+            auto pq = [&](auto q) {
+                constexpr int Q = decltype(q)::value;
+#define FW(u)                                                                                                    \
+    (A.qtab ? fattn_wo_pair_q_kernel<u, true, 2, Q>                                                              \
+            : (two ? fattn_wo_pair_q_kernel<u, false, 2, Q> : fattn_wo_pair_q_kernel<u, false, 1, Q>))<<<grid, block, 0, s>>>(A)
+                const int u = rowgemv_u(A.wo.K, Q);
+                if (u == 2) FW(2);
+                else if (Q == 2 && u == 3) {
+                    if constexpr (Q == 2) FW(3);
+                } else {
+                    FMCHECK(false, "fused fast attention + wo, pair form on codes: int8 has depth 2, int4 depths 2 .. 3");
+                }
+#undef FW
+            };
+            if (qm == 2) pq(std::integral_constant<int, 2>{});
+            else pq(std::integral_constant<int, 1>{});
+            return;
+        }
         switch (rowgemv_u(A.wo.K, 0)) {
 #define FW(u)                                                                                                            \
     case u:                                                                                                              \

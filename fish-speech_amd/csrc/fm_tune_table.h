@@ -144,4 +144,9 @@ FM_KNOB(slow_attn_wo_q, 0, FM_RANGE(0, 2)) // slow_attn_wo's launch on weight-on
                                            // codes (QM 1 / 2 of rowgemv_body).  0 the two launches, 1 two rows per 4-wave group, 2 four; the three wait knobs
                                            // above are shared (bit-identical).  S2-Pro frame, int8 / int4: 2 loses 17 / 26 us
                                            // (0.6 / 0.9 %), 1 loses 84 / 96 us, at baseline spreads of 3 / 4 us: off
+FM_KNOB(fast_pair_q, 0, FM_RANGE(0, 3))    // fast_pair's two-row pass on weight-only handles (fast_pair keeps governing unquantised bf16 and nothing else, this
+                                           // knob is inert there): bit 0 int8 handles, bit 1 int4 handles.  Needs fast_tail, fattn_wo, fast_dead_q bit 0, gemv_chain
+                                           // off, a fast stack without an o-bias and the mode's default routing (int8: wo / w2 on the row GEMV, wqkv and w1 || w3 on
+                                           // the tiles; int4: rowgemv_q4 bits 0, 1, 2 and 4, int4_stream 1); elsewhere, and at 0, the one-row passes
+                                           // (bit-identical; profiles/fast_pair_q.md)
 #endif

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     "fm_codec_profile_read", "fm_codec_debug_read", "fm_codec_enable_encoder", "fm_codec_encode",
     "fm_codec_close", "fm_llm_force", "fm_llm_read_logits", "fm_op_rmsnorm", "fm_op_qk_rope", "fm_op_decode_attn", "fm_op_prompt_attn",
     "fm_op_embed", "fm_op_quant4", "fm_op_batched_linear_q8", "fm_op_batched_linear_q4", "fm_rope_table",
-    "fm_op_linear", "fm_op_gemv", "fm_op_rowgemv", "fm_op_rowgemv_pair", "fm_op_bstream", "fm_op_finalize_norm", "fm_op_prompt_skinny", "fm_op_sample",
+    "fm_op_linear", "fm_op_gemv", "fm_op_rowgemv", "fm_op_rowgemv_pair", "fm_op_rowgemv_pair_q", "fm_op_gemv_pair_q", "fm_op_bstream", "fm_op_finalize_norm", "fm_op_prompt_skinny", "fm_op_sample",
     "fm_llm_prefix_save", "fm_llm_prefix_load", "fm_llm_prefix_drop", "fm_llm_prefix_info", "fm_llm_prefill_batch_at",
     "fm_llm_set_quant_compact", "fm_llm_memory_info", "fm_op_linear_q", "fm_op_prompt_skinny_q", "fm_op_prompt_gemm_q",
     "fm_op_codec_conv", "fm_op_codec_resunit", "fm_op_codec_window_attn", "fm_op_codec_window_attn_seg", "fm_op_codec_rope_qk", "fm_op_codec_dwconv_ln",
@@ -201,6 +201,10 @@ def lib():
                                 i32, i32, pf32, i32, i32, ctypes.POINTER(ctypes.c_int8), pf32]
     L.fm_op_rowgemv_pair.argtypes = [i32, i32, pf32, pf32, pf32, f32, pf32, pf32, pf32, i32, i32, pi32, i32, i32, i32, i32,
                                      i32, pf32, i32]
+    L.fm_op_rowgemv_pair_q.argtypes = [i32, i32, i32, i32, pf32, pf32, f32, pf32, pf32, pf32, i32, i32, pi32, i32, i32, i32,
+                                       i32, i32, pf32, pf32, i32, ctypes.POINTER(ctypes.c_int8), pf32, pf32]
+    L.fm_op_gemv_pair_q.argtypes = [i32, i32, i32, pf32, pf32, f32, pf32, i32, i32, pf32, i32, pf32, i32,
+                                    ctypes.POINTER(ctypes.c_int8), pf32]
     L.fm_op_bstream.argtypes = [i32, i32, i32, i32, pf32, pf32, pf32, f32, pf32, i32, pf32, i32, i32, i32, i32, pf32,
                                 i32, i32, pf32, i32, pi32, pi32]
     L.fm_op_finalize_norm.argtypes = [i32, i32, pf32, i32, i32, pf32, pf32, i32, pf32, pf32, f32, i32, i32, pf32, i32,

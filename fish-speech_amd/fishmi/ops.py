@@ -225,7 +225,9 @@ def fattn_wo(qkv, nh, nkv, hd, slot, cpos, kcache, vcache, rope_base, w, res, bi
              gen=1, pos0=0, xt_init=None, device=0):
     """fm_op_fattn_wo: the batch-1 fast decoder's attention + wo in one launch (fused) or as fast_attn2 + row GEMV.
     qkv (1 or 2, ld); w (N, nh*hd); res (res_rows, ldr) the residual table (row idx[idx_col], or row 0).  Returns
-    (y (N,) or (2, N) for pair 1, kcache, vcache, ok, err): ok False = not dispatchable, nothing was launched."""
+    (y (N,) or (2, N) for pair 1, kcache, vcache, ok, err): ok False = not dispatchable, nothing was launched.  The
+    pair forms take quant 1 / 2 (int8 / int4 wo) too.  fattn_wo.last_depth holds the last call's dispatched depth
+    (status[0]: rowgemv_u's chunks per wave, 0 when nothing was launched)."""
     raw = np.ascontiguousarray(qkv, np.float32).reshape(-1, (nh + 2 * nkv) * hd)
     assert raw.shape[0] == (2 if pair else 1)
     kc, vc = _caches(kcache, vcache, nkv, hd)
@@ -250,7 +252,11 @@ def fattn_wo(qkv, nh, nkv, hd, slot, cpos, kcache, vcache, rope_base, w, res, bi
         int(layer), native.f32p(kc), native.f32p(vc), S, native.f32p(ww), _opt(bi), native.f32p(rr), rr.shape[0],
         rr.shape[1], _opt(r0), N, int(kv0), int(pair), int(ilp), int(gen), int(pos0),
         None if xt is None else xt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), native.f32p(y), native.i32p(status)))
+    fattn_wo.last_depth = int(status[0])  # the dispatched depth (chunks per wave; 0: not dispatchable)
     return y, kc, vc, bool(status[0]), int(status[1])
+
+
+fattn_wo.last_depth = 0
 
 
 def slow_attn_wo(qkv, nh, nkv, hd, slots, pos, kcache, vcache, rope_base, w, res, bias=None, qn=None, kn=None, eps=1e-6,
@@ -531,6 +537,53 @@ def rowgemv_pair(w, x, y, kind, bias=None, nw=None, eps=1e-6, res0=None, res1=No
                                                  0 if res1 is None else res1.shape[1],
                                                  None if idx is None else native.i32p(idx), 0 if idx is None else idx.size,
                                                  int(idx_col), int(skip0), N, K, _p(y), y.shape[1]))
+
+
+def rowgemv_pair_q(w, x, y2, y1, kind, quant, gs=128, nw=None, eps=1e-6, res0=None, res1=None, idx=None, idx_col=0,
+                   skip0=0, device=0):
+    """fm_op_rowgemv_pair_q: the two-row forms on weight-only codes (fm_tune fast_pair_q).  w [N][K] is quantised on
+    the device (quant "int8", or "int4" with groups of gs); the two-row launch fills y2 [2][ld], the one-row production
+    launcher, once per row on the same device operands, y1 [2][ld] (both in/out).  kind 0 fin, 1 norm + store (skip0),
+    2 norm + swiglu; operands as rowgemv_pair.  Returns (q [N][K] int8 codes, scale, zero): scale [N] and zero None
+    for int8, both [N][K / gs] for int4."""
+    w, nw, x, res0, res1 = _f(w), _f(nw), _f(x), _f(res0), _f(res1)
+    N, K = w.shape
+    assert x.shape == (2, K)
+    if res1 is not None:
+        res1 = res1.reshape(-1, res1.shape[-1])
+    y2, y1 = _out(y2), _out(y1)
+    assert y2.ndim == 2 and y2.shape[0] == 2 and y1.shape == y2.shape
+    if idx is not None:
+        idx = np.ascontiguousarray(idx, np.int32).ravel()
+    q4 = quant == "int4"
+    assert q4 or quant == "int8"
+    q = np.zeros((N, K), np.int8)
+    sc = np.zeros((N, K // gs) if q4 else N, np.float32)
+    zr = np.zeros((N, K // gs), np.float32) if q4 else None
+    native.check(native.lib().fm_op_rowgemv_pair_q(
+        device, native.FM_QUANT_INT4 if q4 else native.FM_QUANT_INT8, int(gs), int(kind), _p(w), _p(nw), float(eps), _p(x),
+        _p(res0), _p(res1), 0 if res1 is None else res1.shape[0], 0 if res1 is None else res1.shape[1],
+        None if idx is None else native.i32p(idx), 0 if idx is None else idx.size, int(idx_col), int(skip0), N, K, _p(y2),
+        _p(y1), y2.shape[1], q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), _p(sc), _p(zr)))
+    return q, sc, zr
+
+
+def gemv_pair_q(w, x, y2, y1, epi, nw, eps=1e-6, quant="int8", device=0):
+    """fm_op_gemv_pair_q: the tile kernel's two-row ss_gran 1 form on int8 codes (fm_tune fast_pair_q).  w [N][K] is
+    quantised and packed on the device; the R = 2 launch fills y2 [rows >= 2][ld], the R = 1 production launch, once per
+    row on the same device operands, y1 [2][ld] (both in/out).  epi EPI_STORE or EPI_SWIGLU8.  Returns (q [N][K] int8,
+    scale [N])."""
+    w, nw, x = _f(w), _f(nw), _f(x)
+    N, K = w.shape
+    assert x.shape == (2, K) and quant == "int8"
+    y2, y1 = _out(y2), _out(y1)
+    assert y2.ndim == 2 and y1.ndim == 2 and y1.shape[0] == 2 and y1.shape[1] == y2.shape[1]
+    q = np.zeros((N, K), np.int8)
+    sc = np.zeros(N, np.float32)
+    native.check(native.lib().fm_op_gemv_pair_q(device, native.FM_QUANT_INT8, int(epi), _p(w), _p(nw), float(eps), _p(x), N, K,
+                                                _p(y2), y2.shape[0], _p(y1), y2.shape[1],
+                                                q.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), _p(sc)))
+    return q, sc
 
 
 PLAN_FIELDS = ("acc", "kparts", "nw", "spw", "tpi", "ntm", "grid")

@@ -314,6 +314,33 @@ def stream_vocoder(codec, chunk: int = 128):
     return StreamVocoder(codec, chunk, batch=VOCODE_BATCH)
 
 
+def parse_tune(items):
+    """--tune KEY=VALUE arguments -> [(key, int value)] in the order given (ValueError on a malformed one)."""
+    out = []
+    for kv in items:
+        k, sep, v = kv.partition("=")
+        k = k.strip()
+        try:
+            if not (sep and k):
+                raise ValueError
+            out.append((k, int(v, 0)))
+        except ValueError:
+            raise ValueError(f"--tune {kv!r}: expected KEY=VALUE with an integer value") from None
+    return out
+
+
+def apply_tune(pairs, native=None):
+    """fm_tune(key, value) for each pair, before any model handle of this process is opened (fishmi.native.tune
+    raises on an unknown key or a value the knob does not accept)."""
+    if not pairs:
+        return
+    if native is None:
+        from . import native
+    for k, v in pairs:
+        native.tune(k, v)
+        log.info("fm_tune %s = %d", k, v)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["tts"], default="tts")
@@ -340,7 +367,14 @@ def main(argv=None):
     ap.add_argument("--vocode-batch", type=int, default=0,
                     help="streamed vocoding: chunks of up to N distinct requests share one batched codec pass "
                          "(scheduler.StreamVocoder(codec, chunk, batch=N); bit-identical audio); 0 = one pass per chunk")
+    ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
+                    help="fm_tune knob set before the model opens (repeatable, in the order given; e.g. "
+                         "fast_pair_q=2); an unknown key or a value outside the knob's range stops the server")
     a = ap.parse_args(argv)
+    try:
+        tunes = parse_tune(a.tune)
+    except ValueError as e:
+        ap.error(str(e))
     import uvicorn
 
     from .engine import _device_index
@@ -367,6 +401,8 @@ def main(argv=None):
             ap.error("--quant-compact is not wired through the multi-GPU worker")
         if a.vocode_batch:
             ap.error("--vocode-batch: the multi-GPU worker vocodes each response on its own (no StreamVocoder)")
+    apply_tune(tunes)  # (every rank of a multi-GPU server runs main: each sets its own process's knobs)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         return _main_distributed(a)
     engine = build_engine(a.llama_checkpoint_path, a.decoder_checkpoint_path, _device_index(a.device), "bf16",
                           slots=a.slots, reuse_prefix=a.reuse_prefix, voice_cache_mb=a.voice_cache_mb,

@@ -286,6 +286,16 @@ int fm_llm_read_logits(fm_llm* h, int slot, float* slow_logits, float* fast_logi
    layers).  It engages on bf16 unquantised models at one row with "fast_tail" and "fattn_wo" on,
    "gemv_chain" off and "rowgemv" bits 0, 1, 5 and 6 set and bit 2 clear, at shapes whose two-row
    kernel forms exist; anywhere else, and at 0, the one-row passes run.  It changes no output bit.
+   "fast_pair_q" 0..3 (default 0): the same two-row pass on weight-only handles (compact ones too), which
+   "fast_pair" leaves alone -- bit 0 (1) int8 handles, bit 1 (2) int4 handles.  It engages at one row in
+   bf16 compute on a fast stack without an o-bias, with "fast_tail" and "fattn_wo" on, "gemv_chain" off and
+   "fast_dead_q" bit 0 set, on each mode's default routing -- int8: "rowgemv" bit 0 set and bits 1 and 2
+   as they act on int8 (wqkv and w1 || w3 on the tile kernel), dim <= 4096; int4: "int4_stream" on and
+   "rowgemv_q4" bits 0, 1, 2 and 4 set (bit 4: the pair's first layer projects row 0's K / V rows on the
+   row form) -- at shapes whose two-row code forms exist: a wave's run of 512-k chunks at most 2 (int8;
+   nq <= 4096) or 3 (int4; nq <= 6144) in the fused launch, at most 3 for the int4 wqkv and w1 || w3
+   (dim <= 6144), at most 5 for wo and w2 (intermediate <= 10240).  Anywhere else, and at 0, the one-row
+   passes run.  The knob is inert on unquantised handles and changes no output bit.
    "fast_dead_q" 0..3 (default 1): the two removals of "rowgemv" bits 5 and 6 for weight-only int8 /
    int4 handles, which those bits leave alone -- bit 0 (1) the first fast layer's QKV table (built the
    same way, by the quantised model's own launch), bit 1 (2) K / V only at codebook 0.  They act at batch
@@ -388,8 +398,9 @@ int fm_op_fast_attn(int device, int precision, int kernel, const float* qkv, int
    [res_rows][ldr] (NULL: row 0); kv0: the K / V-only form of codebook 0 (the Q part of qkv is not read); pair 1 / 2:
    codebooks 0 and 1 in one launch (res0 [N]: row 0's residual for pair 1; y [2][N]), else y [N]; ilp: fm_tune
    fattn_ilp; gen (1..40) and pos0 make the hand-off tag; xt_init [2 nh hd] or NULL pre-fills the tagged words.
-   w [N][nh hd], bias [N] or NULL.  status[2] out: {dispatchable (fattn_wo_ok, fattn_wo_dead_ok for the table and
-   K / V-only forms, the pair form's depth: 0 = nothing was launched), the err word after the launch}. */
+   w [N][nh hd], bias [N] or NULL.  The pair forms take int8 / int4 wo too (fm_tune "fast_pair_q").  status[2] out:
+   {0 = not dispatchable, nothing was launched (fattn_wo_ok, fattn_wo_dead_ok for the table and K / V-only forms,
+   the pair form's depth), else the dispatched depth in chunks per wave; the err word after the launch}. */
 int fm_op_fattn_wo(int device, int quant, int gs, int fused, const float* qkv, const float* qtab, int qrows,
                    const int32_t* idx, int idx_n, int idx_col, int nh, int nkv, int hd, const float* qn, const float* kn,
                    int qk_norm, float eps, float rope_base, int slot, int cpos, int nslots, int layers, int layer,
@@ -492,6 +503,23 @@ int fm_op_rowgemv(int device, int kind, int q8, const float* w, const float* bia
 int fm_op_rowgemv_pair(int device, int kind, const float* w, const float* bias, const float* nw, float eps, const float* x,
                        const float* res0, const float* res1, int res_rows, int ldr, const int32_t* idx, int idx_n,
                        int idx_col, int skip0, int N, int K, float* y, int y_ld);
+/* The two-row forms on weight-only codes (fm_tune "fast_pair_q"): w [N][K] is quantised on the device by the model's
+   rule (quant FM_QUANT_INT8: per row; FM_QUANT_INT4: groups of gs) and packed by the model's launchers; then, on the
+   same device operands, the two-row launch fills y2 [2][y_ld] and the one-row production launcher, once per row,
+   y1 [2][y_ld] (both in/out; row 0 of y1 holds every output, also below skip0).  kind 0 fin (int8, int4), 1 norm +
+   store, 2 norm + swiglu (int4; outputs N / 2 wide); operands as fm_op_rowgemv_pair, no bias.  Optional outputs:
+   q_out [N][K] (int8 codes, or int4 codes 0..15 one per byte), scale_out [N] ([N][K / gs]), zero_out [N][K / gs]. */
+int fm_op_rowgemv_pair_q(int device, int quant, int gs, int kind, const float* w, const float* nw, float eps, const float* x,
+                         const float* res0, const float* res1, int res_rows, int ldr, const int32_t* idx, int idx_n,
+                         int idx_col, int skip0, int N, int K, float* y2, float* y1, int y_ld, int8_t* q_out, float* scale_out,
+                         float* zero_out);
+/* The 16-row tile kernel's two-row form on weight-only int8 codes (fm_tune "fast_pair_q" bit 0; PRO_PRENORM with the
+   statistic from the staged rows, ss_gran 1): w [N][K] is quantised on the device by the model's rule and packed by
+   the model's launcher; then, on the same device operands, the R = 2 launch fills y2 [y2_rows >= 2][ldy] and the R = 1
+   production launch, once per row, y1 [2][ldy] (both in/out).  epi 0 (store: wqkv) or 7 (SwiGLU8: w1 || w3 in 8 + 8
+   interleaved rows, outputs N / 2 wide); quant FM_QUANT_INT8 only.  Optional outputs: q_out [N][K], scale_out [N]. */
+int fm_op_gemv_pair_q(int device, int quant, int epi, const float* w, const float* nw, float eps, const float* x, int N,
+                      int K, float* y2, int y2_rows, float* y1, int ldy, int8_t* q_out, float* scale_out);
 /* launch_bstream (8 < R <= 32) on bstream_plan's geometry, returned in plan[7] = {acc, kparts, nw, spw,
    tpi, ntm, grid} (acc 1: bsacc_kernel; fm_tune "bstream_acc" 0 or fp32: bstream_kernel).  pro 3 (bsacc,
    epi 0 / 7): the sums of squares come from a zero-weight epi-5 launch over x.  Outputs as fm_op_gemv's,
